@@ -6,6 +6,7 @@
 //   src/gauge/wflow.nim:92-149              plaquettes after gaugeFlow(6,.01) (golden set G2)
 // with the CPU oracle (oracle/qex_oracle.h, test infrastructure) as the checker.
 // Build + run: tests/test_cpp_host.py (g++ -Iinclude -Ioracle ... -lqexhip -lqexoracle).
+// argv[1]: directory for the SciDAC round-trip file (default /tmp).
 #include "qexhip.hpp"
 extern "C" {
 #include "qex_oracle.h"
@@ -26,7 +27,7 @@ static double relerr(const qex::Field &a, const qex::Field &b) {
   return std::sqrt(d / n);
 }
 
-int main() {
+int main(int argc, char **argv) {
   using namespace qex;
   const std::array<int, 4> lat = {8, 8, 8, 8};
   Context ctx(lat);
@@ -188,7 +189,7 @@ int main() {
       CHECK(relerr(p2, po) < 1e-11 && relerr(g2, go) < 1e-12, "resident MD step vs oracle");
     }
     // SciDAC file round trip
-    const std::string fn = "/tmp/qexhip_cpp_test.lime";
+    const std::string fn = std::string(argc > 1 ? argv[1] : "/tmp") + "/qexhip_cpp_test.lime";
     saveGauge(lo, gw, fn);
     Field gr = lo.newGauge();
     loadGauge(lo, gr, fn);

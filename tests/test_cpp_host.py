@@ -37,10 +37,10 @@ def test_cpp_host_layer_compiles_and_links():
 
 
 @pytest.mark.gpu
-def test_cpp_host_parity_program():
+def test_cpp_host_parity_program(tmp_path):
     build()
     env = dict(os.environ, OMP_NUM_THREADS="8")
-    p = subprocess.run([EXE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
+    p = subprocess.run([EXE, str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
     print(p.stdout)
     assert p.returncode == 0 and "Passed" in p.stdout, p.stdout
 
