@@ -282,6 +282,24 @@ int qexhip_dev_zero(qexhip_handle h, int id, int parity);
 int qexhip_dev_solve_batch(qexhip_handle h, int n, const int *x_ids, const int *b_ids, const double *mass,
                            const double *r2req, int maxits, int *iters, double *r2);
 
+/* ---------------- meson correlators on resident fields ----------------
+ * Local staggered mesons from point-source propagators (src/observables/fpvaMeas.nim, tests/examples/testStagProp.nim).
+ * Tables are rank-global and returned on the host; on a t-sharded context every rank receives the whole table.
+ *
+ * stagLocalMesons (fpvaMeas.nim:33-61) summed over n <= 4 field pairs in one launch, both parities:
+ *   out[tt*8 + s] = sum_k sum_{x: (t(x) - t0) mod nt = tt, corner(x) = s} Re<x_k(x), y_k(x)>,  corner = (x0&1) | (x1&1)<<1 | (x2&1)<<2
+ * with t the global time coordinate and nt the global t extent; out holds nt*8 doubles.  stagMesons(v)
+ * (src/physics/stagMesonLocal.nim:14-51) is x = y = v, t0 = 0.  The summation order is fixed and every entry is computed on the
+ * rank that owns its time slice: the table is bit-identical run to run and for any number of ranks. */
+int qexhip_dev_meson_corners(qexhip_handle h, int n, const int *x_ids, const int *y_ids, int t0, double *out);
+/* symShift (fpvaMeas.nim:16-31): r(x) = U_mu(x) x(x+mu) + U_mu(x-mu)^+ x(x-mu) for mu = 0, 1, 2 on both parities, r_id != x_id.
+ * U are the operator's one-hop links as qexhip_stag_set_links* left them (with boundary conditions and staggered phases: for
+ * newStag(g) the rephased g that fpvaMeas shifts with; for HISQ or nHYP operators the SMEARED one-hop links).  mu = 3 is refused:
+ * the reference shifts spatially only. */
+int qexhip_dev_sym_shift(qexhip_handle h, int r_id, int x_id, int mu);
+/* norm2slice (src/observables/sources.nim:10-18): out[v] = sum_{x: x_dir = v} |f(x)|^2 over the global extent of dir (dir 0..3) */
+int qexhip_dev_norm2slice(qexhip_handle h, int id, int dir, double *out);
+
 /* ---------------- gauge field, plaquette, Wilson flow ----------------
  * qexhip_gauge_set/get: the `g` of src/gauge/wflow.nim:21 (unphased links, periodic). */
 int qexhip_gauge_set(qexhip_handle h, const double *g);

@@ -118,6 +118,9 @@ SYMBOLS = [
     ("qexhip_md_refresh_momenta", _ci, [_vp, _vp]),
     ("qexhip_dev_zero", _ci, [_vp, _ci, _ci]),
     ("qexhip_dev_solve_batch", _ci, [_vp, _ci, _pi, _pi, _pd, _pd, _ci, _pi, _pd]),
+    ("qexhip_dev_meson_corners", _ci, [_vp, _ci, _pi, _pi, _ci, _vp]),
+    ("qexhip_dev_sym_shift", _ci, [_vp, _ci, _ci, _ci]),
+    ("qexhip_dev_norm2slice", _ci, [_vp, _ci, _ci, _vp]),
     ("qexhip_nhyp_fforce_dev", _ci, [_vp, _vp, _ci, _pi, _pd, _pd, _pd, _ci, _pi, _pi, _pi]),
     ("qexhip_rng_state_words", _ci, [_vp]),
     ("qexhip_rng_get_state", _ci, [_vp, _vp]),

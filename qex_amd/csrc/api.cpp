@@ -191,6 +191,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   if (c->tile_order) (void)hipFree(c->tile_order);
   for (int *&t : c->tile_order_pl) if (t) { (void)hipFree(t); t = nullptr; }
   if (c->cgm_scal) (void)hipFree(c->cgm_scal);
+  if (c->meson_buf) (void)hipFree(c->meson_buf);
   if (c->Wc) (void)hipFree(c->Wc);
   if (c->Ws) (void)hipFree(c->Ws);
   if (c->stage) (void)hipFree(c->stage);
@@ -653,6 +654,42 @@ extern "C" int qexhip_dev_D(qexhip_handle c, int r_id, int x_id, double m, doubl
   CHK(find_field(c, r_id, &fr));
   CHK(find_field(c, x_id, &fx));
   return op_D(c, *fr, *fx, m, sc);
+}
+
+// ---- meson tables, symmetric shift, slice norms (fpvaMeas.nim:16-61, stagMesonLocal.nim:14-51, sources.nim:10-18) ----
+extern "C" int qexhip_dev_meson_corners(qexhip_handle c, int n, const int *x_ids, const int *y_ids, int t0, double *out) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!x_ids || !y_ids || !out) { qexhip_set_error("dev_meson_corners: null argument"); return QEXHIP_ERR_ARG; }
+  if (n < 1 || n > 4) { qexhip_set_error("dev_meson_corners: n = %d, must be 1..4", n); return QEXHIP_ERR_ARG; }
+  const int ntg = c->g.X[3] * c->rankGeom[3];
+  if (t0 < 0 || t0 >= ntg) { qexhip_set_error("dev_meson_corners: t0 = %d outside [0, %d)", t0, ntg); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *xs[4], *ys[4];
+  for (int k = 0; k < n; k++) {
+    CHK(find_field(c, x_ids[k], &xs[k]));
+    CHK(find_field(c, y_ids[k], &ys[k]));
+  }
+  return meson_corners(c, n, xs, ys, t0, out);
+}
+extern "C" int qexhip_dev_sym_shift(qexhip_handle c, int r_id, int x_id, int mu) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (mu < 0 || mu > 2) { qexhip_set_error("dev_sym_shift: mu = %d, only the spatial directions 0..2 are shifted", mu); return QEXHIP_ERR_ARG; }
+  if (r_id == x_id) { qexhip_set_error("dev_sym_shift: r_id == x_id"); return QEXHIP_ERR_ARG; }
+  if (!c->W) { qexhip_set_error("dev_sym_shift: no links set (qexhip_stag_set_links first)"); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fr, *fx;
+  CHK(find_field(c, r_id, &fr));
+  CHK(find_field(c, x_id, &fx));
+  return sym_shift(c, *fr, *fx, mu);
+}
+extern "C" int qexhip_dev_norm2slice(qexhip_handle c, int id, int dir, double *out) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!out) { qexhip_set_error("dev_norm2slice: null argument"); return QEXHIP_ERR_ARG; }
+  if (dir < 0 || dir > 3) { qexhip_set_error("dev_norm2slice: dir = %d, must be 0..3", dir); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *f;
+  CHK(find_field(c, id, &f));
+  return norm2slice(c, *f, dir, out);
 }
 
 // ---- link smearing ----

@@ -51,3 +51,14 @@ __device__ __forceinline__ void recon_row2(double2 U[9], bool neg) {
   for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
 }
 
+
+// one link of the operator's storage as the sweep reads it: `w` points at this lane's element of the (tile, dir) row of W
+// (RECON 0: 9 double2) or Wc (RECON 1: rows 0,1; RECON 2: rows 0,1 + det), `sm` at the row's sign mask (RECON 1 only)
+template <int RECON>
+__device__ __forceinline__ void load_link(double2 U[9], const double2 *w, const unsigned long long *sm, int lane) {
+  constexpr int NLOAD = RECON == 1 ? 6 : (RECON == 2 ? 7 : 9);
+#pragma unroll
+  for (int k = 0; k < NLOAD; k++) U[k] = w[k * 64];
+  if (RECON == 1) recon_row2<1>(U, (*sm >> lane) & 1ull);
+  else if (RECON == 2) recon_row2<2>(U, false);
+}

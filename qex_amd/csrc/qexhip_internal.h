@@ -175,6 +175,7 @@ struct qexhip_ctx {
   void *batch = nullptr;                             // BatchState of the lock-step multi-system CG (batch.hip)
   int lds_attr_done = 0;                             // per context (= per device): which kernels had MaxDynamicSharedMemorySize raised (bit 0 k_force_lds, 1 k_flow_obs_clover, 2 k_flow_obs_clover2, 3 k_force_lds2, 4 k_projUderiv_batch)
   void *cgm_scal = nullptr;                          // CgmScal of the multi-shift solver (multishift.hip)
+  double *meson_buf = nullptr; size_t meson_cap = 0; // workgroup partials + global table of the meson / slice-norm reductions (meson.hip)
 };
 
 // work-field slots (get_work)
@@ -338,6 +339,11 @@ int pool_field(qexhip_ctx *c, int idx, DevField **f);
 
 // ---- force.hip ----
 int stag_outer_host(qexhip_ctx *c, double *f_host, const double *x_host, double se, double so, int accumulate);
+
+// ---- meson.hip ----
+int meson_corners(qexhip_ctx *c, int n, DevField *const *x, DevField *const *y, int t0, double *host_out);   // [nt_global][8], rank-global
+int sym_shift(qexhip_ctx *c, DevField &r, const DevField &x, int mu);                                      // mu < 3, links set
+int norm2slice(qexhip_ctx *c, const DevField &f, int dir, double *host_out);                                // [L_dir global], rank-global
 
 // ---- smear.hip ----
 int smear_fat7_host(qexhip_ctx *c, const double *g_host, const double coef[5], double *fl_host, double *ll_host, double naik);

@@ -74,6 +74,10 @@ proc qexhip_stag_solve_multi(h: QexhipHandle; xs: ptr ptr cdouble; b: ptr cdoubl
                              r2req: cdouble; maxits: cint; iters: ptr cint; r2: ptr cdouble): cint {.qh.}
 proc qexhip_stag_solve_batch(h: QexhipHandle; n: cint; x, b: ptr ptr cdouble; mass, r2req: ptr cdouble;
                              maxits: cint; iters: ptr cint; r2: ptr cdouble): cint {.qh.}
+# meson tables from resident propagators (fpvaMeas.nim:16-61, sources.nim:10-18)
+proc qexhip_dev_meson_corners(h: QexhipHandle; n: cint; xIds, yIds: ptr cint; t0: cint; o: ptr cdouble): cint {.qh.}
+proc qexhip_dev_sym_shift(h: QexhipHandle; rId, xId, mu: cint): cint {.qh.}
+proc qexhip_dev_norm2slice(h: QexhipHandle; id, dir: cint; o: ptr cdouble): cint {.qh.}
 proc qexhip_gauge_set(h: QexhipHandle; g: ptr cdouble): cint {.qh.}
 proc qexhip_gauge_get(h: QexhipHandle; g: ptr cdouble): cint {.qh.}
 proc qexhip_plaq(h: QexhipHandle; o: ptr cdouble): cint {.qh.}

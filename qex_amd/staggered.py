@@ -257,6 +257,28 @@ class Context:
         """r = m x + sc D x on resident fields (Staggered.D: sc = 1, Ddag: sc = -1)"""
         check(lib().qexhip_dev_D(self._h, r_id, x_id, float(m), float(sc)))
 
+    def dev_meson_corners(self, x_ids, y_ids, t0=0):
+        """stagLocalMesons (fpvaMeas.nim:33-61) summed over the pairs (x_ids[k], y_ids[k]), k < 4: (nt, 8) array, rank-global"""
+        n = len(x_ids)
+        if n != len(y_ids):
+            raise ValueError("x_ids and y_ids differ in length")
+        nt = self.lat[3] * self.rank_geom[3]
+        out = np.zeros((nt, 8))
+        check(lib().qexhip_dev_meson_corners(self._h, n, (C.c_int * max(n, 1))(*[int(v) for v in x_ids]),
+                                             (C.c_int * max(n, 1))(*[int(v) for v in y_ids]), int(t0), _p(out)))
+        return out
+
+    def dev_sym_shift(self, r_id, x_id, mu):
+        """symShift (fpvaMeas.nim:16-31) with the operator's one-hop links: r = U_mu x(+mu) + U_mu(-mu)^+ x(-mu), mu < 3"""
+        check(lib().qexhip_dev_sym_shift(self._h, int(r_id), int(x_id), int(mu)))
+
+    def dev_norm2slice(self, fid, dir):
+        """norm2slice (sources.nim:10-18): |f|^2 summed over the slices of direction dir, rank-global"""
+        n = self.lat[dir] * (self.rank_geom[3] if dir == 3 else 1) if 0 <= dir < 4 else 1     # (the library refuses any other dir)
+        out = np.zeros(n)
+        check(lib().qexhip_dev_norm2slice(self._h, int(fid), int(dir), _p(out)))
+        return out
+
     # field algebra hooks (fieldET.nim:605-625,704-724)
     def norm2(self, x, subset="all"):
         out = C.c_double(0)
@@ -314,6 +336,21 @@ class Staggered:
 
     def D(self, r, x, m):
         check(lib().qexhip_stag_D(self.ctx._h, _p(r), _p(x), float(m), 1.0))
+
+    def symShift(self, r, x, mu):
+        """symShift (fpvaMeas.nim:16-31): r = U_mu(x) x(x+mu) + U_mu(x-mu)^+ x(x-mu), mu in 0..2, with this operator's one-hop links
+        (the rephased g of newStag(g); the smeared one-hop links of a HISQ or nHYP operator).  r, x: field ids or host arrays."""
+        if isinstance(r, np.ndarray) or isinstance(x, np.ndarray):
+            ctx = self.ctx
+            fx, fr = ctx.field_new(x), ctx.field_new()
+            try:
+                ctx.dev_sym_shift(fr, fx, mu)
+                r[...] = ctx.field_download(fr)
+            finally:
+                ctx.field_free(fx)
+                ctx.field_free(fr)
+        else:
+            self.ctx.dev_sym_shift(r, x, mu)
 
     def Ddag(self, r, x, m):
         check(lib().qexhip_stag_D(self.ctx._h, _p(r), _p(x), float(m), -1.0))
