@@ -15,7 +15,7 @@
 #include "site_index.h"
 #include "reduce.h"
 #include "dslash_core.h"
-#include "peer_device.h"
+#include "fused_sweep.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -143,16 +143,12 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs(MrhsArgs A) {
 }
 
 // The lock-step sweep of a t-sharded slab on the peer transport as ONE launch on ONE stream -- k_dslash_fused (dslash.hip) for up to four
-// systems: push workgroups (the faces of all systems, one piece each) | interior | boundary (hops inside the slab, SHORT wait, hops from
-// the receive arena or park) | cleanup (parked blocks behind the one long wait).  A system's arithmetic is k_dslash_fused's: same hop
-// order (local first), same partial slots; parked or not a block gives the same bits.
+// systems, with the workgroup roles of fused_sweep.h (the push workgroups send the faces of all systems, one piece each).  A system's
+// arithmetic is k_dslash_fused's: same hop order (local first), same partial slots; parked or not a block gives the same bits.
 struct MrhsFusedArgs {
-  MrhsArgs a;                       // c0..c1 interior, d0..d1 low face (workgroups >= nb1), e0..e1 below
-  int e0, e1, nb2, nbA;
+  MrhsArgs a;                       // c0..c1 interior, d0..d1 low face (workgroups >= nb1)
+  FusedSweep fs;                    // e0..e1 high face, push, ghost words, bookkeeping
   const double2 *gh_hi[QX_MAXRHS], *gh_lo[QX_MAXRHS];
-  PeerGhost pg;
-  PeerPush push;
-  FusedCtl fz;
 };
 template <int NDIR, int RECON, bool SECOND>
 __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
@@ -162,52 +158,14 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
 #pragma unroll
   for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
   const bool skip = !any;              // every system has converged: nothing is pushed, the credits still go back
-  __shared__ int sh_n;
-  int bid = blockIdx.x;
-  if (bid < F.push.nblocks) {
-    if (!skip) peer_push_block(F.push, (unsigned)bid);
-    return;
-  }
-  bid -= F.push.nblocks;
-  const int ngrid = (int)gridDim.x - F.push.nblocks - F.fz.ncl;
-  const int nbnd = ngrid - A.nb1;
-  const bool cleanup = bid >= ngrid;
-  int npark = 0, jpark = 0;
-  if (cleanup) {
-    if (threadIdx.x == 0) {
-      int n = 0;
-      if (peer_poll_u32(F.fz.dec, (unsigned)nbnd, F.pg.err, F.pg.ticks, 0x520)) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        n = (int)__hip_atomic_load(F.fz.ndef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (n > 0) {
-          if (!peer_ghost_wait(F.pg)) n = -1;
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-      } else n = -1;
-      sh_n = n;
-    }
-    __syncthreads();
-    npark = sh_n;
-    jpark = bid - ngrid;
-  }
-  bool parked = false, bnd = false;
+  if (fused_push(F.fs, skip)) return;
+  FusedRole R;
+  fused_enter(F.fs, A.nb1, R);
   for (;;) {
-    int lb = bid;
-    if (cleanup) {
-      if (jpark >= npark) break;
-      lb = (int)F.fz.list[jpark];
-      jpark += F.fz.ncl;
-      bnd = true;
-    } else {
-      bnd = bid >= F.nbA && bid < F.nbA + nbnd;
-      lb = bnd ? A.nb1 + (bid - F.nbA) : (bid < F.nbA ? bid : bid - nbnd);
-    }
-    int c = A.c0 + lb * 256 + threadIdx.x, clim = A.c1;
-    if (bnd) {
-      c = A.d0 + (lb - A.nb1) * 256 + threadIdx.x; clim = A.d1;
-      if (lb >= F.nb2) { c = F.e0 + (lb - F.nb2) * 256 + threadIdx.x; clim = F.e1; }
-    }
+    int lb;
+    if (!fused_next_block(F.fs, R, lb)) break;
+    int clim;
+    const int c = fused_site(F.fs, R, lb, A.c0, A.c1, A.d0, A.d1, clim);
     double dotv[QX_MAXRHS] = {0, 0, 0, 0};
     const bool active = c < clim && !skip;
     const Geom &g = A.g;
@@ -289,7 +247,7 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
 #pragma unroll
           for (int k = 0; k < 3; k++) xsv[j][k] = A.xs[j][vec_off(c, k)];
         }
-        if (cleanup) {
+        if (R.cleanup) {
 #pragma unroll
           for (int k = 0; k < 3; k++) acc[j][k] = A.out[j][vec_off(c, k)];
         } else if (SECOND) {
@@ -303,33 +261,22 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
           for (int k = 0; k < 3; k++) acc[j][k] = make_double2(0.0, 0.0);
         }
       }
-      if (!bnd) {
+      if (!R.bnd) {
 #pragma unroll 1
         for (int pr = 0; pr < NDIR / 2; pr++) pair(pr, true, true);
-      } else if (!cleanup) {
+      } else if (!R.cleanup) {
         edge_pairs(false);
       }
     }
-    if (bnd && !skip) {
-      if (!cleanup) {
-        if (threadIdx.x == 0) {
-          const bool in = F.fz.spin_ticks >= 0 && peer_ghost_try(F.pg, F.fz.spin_ticks, F.fz.late);
-          if (in) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
-          sh_n = in ? 1 : 0;
-        }
-        __syncthreads();
-        parked = sh_n == 0;
-      }
-      if (active && !parked) edge_pairs(true);
+    if (R.bnd && !skip) {
+      fused_wait_faces(F.fs, R);
+      if (active && !R.parked) edge_pairs(true);
     }
     if (active) {
 #pragma unroll
       for (int j = 0; j < QX_MAXRHS; j++) {
         if (!act[j]) continue;
-        if (parked) {
+        if (R.parked) {
 #pragma unroll
           for (int k = 0; k < 3; k++) A.out[j][vec_off(c, k)] = acc[j][k];
         } else {
@@ -346,8 +293,8 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
         }
       }
     }
-    if (SECOND && !skip && !parked) {
-      const int pidx = cleanup ? F.nbA + (lb - A.nb1) : bid;
+    if (SECOND && !skip && !R.parked) {
+      const int pidx = fused_partial_slot(F.fs, R, lb);
 #pragma unroll
       for (int j = 0; j < QX_MAXRHS; j++) {
         if (!act[j]) continue;             // uniform over the grid
@@ -355,39 +302,9 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
         if (threadIdx.x == 0) A.partials[j][A.part_off + pidx] = r;
       }
     }
-    if (!cleanup) break;
+    if (!R.cleanup) break;
   }
-  if (!(bnd || cleanup)) return;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  bool credits = false;
-  if (!cleanup) {
-    if (parked) {
-      const unsigned idx = __hip_atomic_fetch_add(F.fz.ndef, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&F.fz.list[idx], (unsigned)(A.nb1 + (bid - F.nbA)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const unsigned a = __hip_atomic_fetch_add(F.fz.dec, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a == (unsigned)nbnd - 1) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      credits = __hip_atomic_load(F.fz.ndef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
-    }
-  } else {
-    const unsigned a = __hip_atomic_fetch_add(F.fz.cl_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a == (unsigned)F.fz.ncl - 1) {
-      credits = npark > 0;
-      __hip_atomic_store(F.fz.ndef, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(F.fz.dec, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(F.fz.late, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(F.fz.cl_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (credits) {
-    __hip_atomic_store(F.pg.credit[0], F.pg.credit_val[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(F.pg.credit[1], F.pg.credit_val[1], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  fused_finish(F.fs, R);
 }
 
 struct BatchBlas {
@@ -550,15 +467,10 @@ static int sweep_mrhs(qexhip_ctx *c, MrhsArgs &A, bool second, int *ndot, DevFie
     MrhsFusedArgs Fz;
     memset(&Fz, 0, sizeof Fz);
     CHK(devjoin_flush(c));
-    CHK(comm_halo_push_only_multi(c, A.nrhs, infield, inpar, Fz.gh_hi, Fz.gh_lo, &Fz.push));
-    CHK(peer_ghost_args(c, &Fz.pg));
-    const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
-    CHK(sweep_fused_ctl(c, nb_lo + nb_hi, &Fz.fz, A.nrhs));
-    A.c0 = lo_end; A.c1 = hi_beg; A.d0 = 0; A.d1 = lo_end; A.nb1 = nb_int; A.part_off = 0; A.swz = 0; A.ntstore = 1;
+    int grid;
+    CHK(fused_sweep_setup(c, A.nrhs, infield, inpar, lo_end, hi_beg, &Fz.fs, Fz.gh_hi, Fz.gh_lo, &grid, ndot));
+    A.c0 = lo_end; A.c1 = hi_beg; A.d0 = 0; A.d1 = lo_end; A.nb1 = (hi_beg - lo_end + 255) / 256; A.part_off = 0; A.swz = 0; A.ntstore = 1;
     Fz.a = A;
-    Fz.e0 = hi_beg; Fz.e1 = g.Vh; Fz.nb2 = nb_int + nb_lo;
-    Fz.nbA = (int)(sweep_push_fraction(c, hi_beg - lo_end, A.nrhs) * nb_int);
-    const int grid = Fz.push.nblocks + nb_int + nb_lo + nb_hi + Fz.fz.ncl;
     ScopedTimer tm(c, "dslash_batch", c->stream);
 #define QX_MF(ND, RC) \
     do { \
@@ -569,7 +481,6 @@ static int sweep_mrhs(qexhip_ctx *c, MrhsArgs &A, bool second, int *ndot, DevFie
     else { if (c->recon == 1) QX_MF(16, 1); else if (c->recon == 2) QX_MF(16, 2); else QX_MF(16, 0); }
 #undef QX_MF
     HIPCHK(hipGetLastError());
-    *ndot = nb_int + nb_lo + nb_hi;
     return 0;
   }
   if (g.halo && overlap) HIPCHK(hipEventRecord(c->ev_ready, c->stream));

@@ -287,7 +287,7 @@ int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool
   return 0;
 }
 
-// Peer transport, the fused sweeps: the faces of one parity half of n fields (n = 1: dslash.hip; up to 4: the lock-step batch) will be
+// Peer transport, the fused sweeps: the faces of one parity half of n fields (fused_sweep_setup: n = 1 for dslash_sweep, up to 4 for the lock-step batch) will be
 // pushed by the caller's OWN kernel (`push` is filled for its first workgroups) and what arrives STAYS in the receive arena.
 // gh_hi[j] / gh_lo[j] come back pre-offset so that gh[vec_off(pos, colour)] addresses the ghost POSITION pos of field j (ghost_hi: pos in
 // [Vh, Vh + depth F), ghost_lo: the depth F positions behind it) -- the kernel reads them instead of the fields' ghost tiles and returns
@@ -312,10 +312,6 @@ int comm_halo_push_only_multi(qexhip_ctx *c, int n, DevField *const *f, int pari
     gh_lo[j] = (const double2 *)from_dn + (size_t)j * face2 - (size_t)((g.Vh + g.depth * g.F) >> 6) * 192;
   }
   return 0;
-}
-int comm_halo_push_only(qexhip_ctx *c, DevField &f, int parity, const double2 **gh_hi, const double2 **gh_lo, PeerPush *push) {
-  DevField *fp = &f;
-  return comm_halo_push_only_multi(c, 1, &fp, parity, gh_hi, gh_lo, push);
 }
 
 // The same for the input fields of the n systems of a lock-step batch in ONE RCCL group (one kernel instead of n): per field

@@ -14,11 +14,11 @@
 //                                              transport's unpacking exchange): one launch behind it, or interior | both faces
 //   k_dslash_fused<NDIR, INIT, DOT, RECON>     the overlapped sweep of a t-sharded slab on the peer transport as ONE launch on ONE stream
 //                                              (shifts.nim:67-94,254-285: local terms while the faces travel, boundary terms when they
-//                                              are in): push | interior | boundary | cleanup workgroups, see below
+//                                              are in): push | interior | boundary | cleanup workgroups, fused_sweep.h
 #include "qexhip_internal.h"
 #include "site_index.h"
 #include "reduce.h"
-#include "peer_device.h"
+#include "fused_sweep.h"
 #include <hip/hip_ext.h>
 #include <cstring>
 #include <algorithm>
@@ -39,89 +39,31 @@ struct DslashArgs {
   double post;           // final scale, the `r := (0.5*sc)*r` of stagD (stagD.nim:409)
   int parity, c0, c1;    // first site range [c0,c1)
   int d0, d1, nb1;       // second range [d0,d1) handled by workgroups >= nb1 (both t-faces in one launch)
-  int e0, e1, nb2;       // fused: third range [e0,e1) handled by workgroups >= nb2 (interior | low face | high face)
-  int nbA;               // fused: position of the boundary workgroups in the dispatch order (interior workgroups before and behind them)
+  const double2 *gh_hi, *gh_lo;   // fused: where ghost POSITIONS are read from: the transport's receive arena (pre-offset: gh[vec_off(pos, k)])
   double *partials;
   const int *done;
   int swz;               // number of workgroups if XCD swizzle is on, else 0
   int ntstore;           // 1: non-temporal stores of the output
-  // fused only
-  const double2 *gh_hi, *gh_lo;   // where ghost POSITIONS are read from: the transport's receive arena (pre-offset: gh[vec_off(pos, k)])
-  PeerGhost pg;          // the inbound data words, the credits owed to the two senders
-  PeerPush push;         // the launch's FIRST push.nblocks workgroups send the faces
-  FusedCtl fz;           // who has decided, who has parked
+  FusedSweep fs;         // fused only: third range, push, ghost words, bookkeeping
 };
 
 #include "dslash_core.h"
 
-// The fused sweep, by workgroup number:
-//   [0, npush)            push this rank's two faces into the neighbours' receive arenas (credits, release, data words: peer_device.h)
-//   interior workgroups   every hop of their sites: the loop of the plain kernel
-//   boundary workgroups   (the `depth` outermost slices either side; placed at nbA of the dispatch order, interior workgroups before AND behind
-//                         them) the hops that stay inside the slab, then a SHORT wait for the inbound data words (about the transfer time):
-//                         faces in -> the 1-2 hops per site that leave the slab straight from the arena, accumulator in registers throughout;
-//                         faces late -> the raw accumulator is PARKED in `out`, the block appended to the parked list, the slot given up
-//   cleanup workgroups    (the last fz.ncl of the grid) once every boundary workgroup has decided: nothing parked -> exit; else the LONG
-//                         bounded wait for the faces (the only place a lost neighbour is noticed), then the parked blocks' remaining hops
-//                         on top of their raw accumulators, final scale, store and dot partial -- in the parked block's own partial slot
-// Whoever reads the arena last returns the credits.  The sum of a boundary site runs local hops first, then the others, parked or not:
-// a parked block gives the same bits as an unparked one (tests/test_gpu_parity.py), and the plain kernel's to rounding.
-// Why park (round 6): a boundary workgroup that spins until the faces are in holds its slot hostage to ANOTHER kernel's progress.  With
-// 16 links a 48^3 face has 6 x 216 = 1296 boundary workgroups, the chip 768 slots for this kernel: on a chip shared by two ranks'
-// processes the spinning ones kept the neighbour's push from ever becoming resident (profiles/r06_notes.md section 1).
+// The fused sweep's workgroup roles (push | interior | boundary | cleanup) are fused_sweep.h's; this is only the per-site arithmetic.
 template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON, bool FUSED>
 __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
   const bool skip = A.done && *A.done;
   // a finished solve turns the rest of its chunk into no-ops -- except that a fused launch still returns the credits it owes
   if (skip && !FUSED) return;
-  __shared__ int sh_n;                     // fused: faces arrived (boundary) / parked blocks to take (cleanup)
-  int bid = blockIdx.x;
-  int ngrid = (int)gridDim.x;              // workgroups that own sites
-  bool cleanup = false;
-  int npark = 0, jpark = 0;
-  if (FUSED) {
-    if (bid < A.push.nblocks) {
-      if (!skip) peer_push_block(A.push, (unsigned)bid);
-      return;
-    }
-    bid -= A.push.nblocks;
-    ngrid -= A.push.nblocks + A.fz.ncl;
-    cleanup = bid >= ngrid;
-    if (cleanup) {
-      if (threadIdx.x == 0) {
-        int n = 0;
-        if (peer_poll_u32(A.fz.dec, (unsigned)(ngrid - A.nb1), A.pg.err, A.pg.ticks, 0x520)) {
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // the parked accumulators, the list
-          n = (int)__hip_atomic_load(A.fz.ndef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (n > 0) {
-            if (!peer_ghost_wait(A.pg)) n = -1;                       // the neighbour is gone: error word set, nothing more to do here
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");             // what other devices wrote into the arena
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
-        } else n = -1;
-        sh_n = n;
-      }
-      __syncthreads();
-      npark = sh_n;
-      jpark = bid - ngrid;
-    }
-  }
-  const int nbnd = FUSED ? ngrid - A.nb1 : 0;
-  bool parked = false;                     // this (boundary) workgroup gave its block to the cleanup workgroups
-  bool bnd = false;
+  if (FUSED && fused_push(A.fs, skip)) return;
+  FusedRole R;
+  R.bid = blockIdx.x; R.cleanup = false; R.bnd = false; R.parked = false;
+  if (FUSED) fused_enter(A.fs, A.nb1, R);
+  const bool cleanup = FUSED && R.cleanup;
   for (;;) {                               // one pass; a cleanup workgroup takes every fz.ncl-th parked block
-    int lb = bid;                          // logical workgroup: [0, nb1) first range, [nb1, nb2) second, [nb2, ..) third
-    if (FUSED) {
-      if (cleanup) {
-        if (jpark >= npark) break;
-        lb = (int)A.fz.list[jpark];
-        jpark += A.fz.ncl;
-        bnd = true;
-      } else {
-        bnd = bid >= A.nbA && bid < A.nbA + nbnd;        // workgroup-uniform
-        lb = bnd ? A.nb1 + (bid - A.nbA) : (bid < A.nbA ? bid : bid - nbnd);
-      }
-    }
+    int lb = R.bid;                        // logical workgroup: [0, nb1) first range, [nb1, nb2) second, [nb2, ..) third
+    if (FUSED && !fused_next_block(A.fs, R, lb)) break;
+    const bool bnd = FUSED && R.bnd;
     if (A.swz && !bnd) {
       // XCD-aware remap: workgroups are dealt round-robin over the 8 XCDs; give every XCD a
       // contiguous run of tiles (= a contiguous t-range) so that y/z/t neighbours share its L2.
@@ -130,10 +72,8 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
     }
     int c = A.c0 + lb * 256 + threadIdx.x;
     int clim = A.c1;
-    if (FUSED ? bnd : lb >= A.nb1) {
-      c = A.d0 + (lb - A.nb1) * 256 + threadIdx.x; clim = A.d1;
-      if (FUSED && lb >= A.nb2) { c = A.e0 + (lb - A.nb2) * 256 + threadIdx.x; clim = A.e1; }
-    }
+    if (FUSED) c = fused_site(A.fs, R, lb, A.c0, A.c1, A.d0, A.d1, clim);
+    else if (lb >= A.nb1) { c = A.d0 + (lb - A.nb1) * 256 + threadIdx.x; clim = A.d1; }
     double dotv = 0;
     const bool active = c < clim && !skip;
     const Geom &g = A.g;
@@ -265,21 +205,10 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       }
     }
     if (edge && !skip) {
-      if (!cleanup) {
-        // the faces: a SHORT wait (one lane), then the acquire for what other devices wrote
-        if (threadIdx.x == 0) {
-          const bool in = A.fz.spin_ticks >= 0 && peer_ghost_try(A.pg, A.fz.spin_ticks, A.fz.late);
-          if (in) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
-          sh_n = in ? 1 : 0;
-        }
-        __syncthreads();
-        parked = sh_n == 0;
-      }
-      if (active && !parked) edge_pairs(true);
+      fused_wait_faces(A.fs, R);
+      if (active && !R.parked) edge_pairs(true);
     }
+    const bool parked = FUSED && R.parked;
     if (active) {
       if (parked) {
         // the raw accumulator waits in `out` for a cleanup workgroup (which re-reads it soon: plain stores)
@@ -303,46 +232,13 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       }
     }
     if (DOT && !skip && !parked) {
-      // (fused: the pushing workgroups have no partial; a parked block's partial goes where its boundary workgroup's would have gone)
-      const int pidx = !FUSED ? (int)blockIdx.x : (cleanup ? A.nbA + (lb - A.nb1) : bid);
+      const int pidx = !FUSED ? (int)blockIdx.x : fused_partial_slot(A.fs, R, lb);
       double r = block_sum_256(dotv);
       if (threadIdx.x == 0) A.partials[pidx] = r;
     }
-    if (!(FUSED && cleanup)) break;
+    if (!cleanup) break;
   }
-  if (!FUSED || !(bnd || cleanup)) return;
-  // every wave's loads of the arena have returned / its parked accumulators are on their way before the workgroup counts itself
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  bool credits = false;
-  if (!cleanup) {
-    if (parked) {
-      const unsigned idx = __hip_atomic_fetch_add(A.fz.ndef, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&A.fz.list[idx], (unsigned)(A.nb1 + (bid - A.nbA)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");     // accumulators and list entry before the count (the cleanup workgroup may sit on another XCD)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const unsigned a = __hip_atomic_fetch_add(A.fz.dec, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a == (unsigned)nbnd - 1) {
-      // the last to decide: if nobody parked, every reader of the arena is through -- the halves go back to the two senders
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      credits = __hip_atomic_load(A.fz.ndef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
-    }
-  } else {
-    const unsigned a = __hip_atomic_fetch_add(A.fz.cl_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a == (unsigned)A.fz.ncl - 1) {
-      credits = npark > 0;             // (npark < 0: a wait gave up -- the error word is set, the job is over)
-      __hip_atomic_store(A.fz.ndef, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.fz.dec, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.fz.late, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(A.fz.cl_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (credits) {
-    __hip_atomic_store(A.pg.credit[0], A.pg.credit_val[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.pg.credit[1], A.pg.credit_val[1], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (FUSED) fused_finish(A.fs, R);
 }
 
 template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON>
@@ -360,26 +256,25 @@ static void launch_timed(qexhip_ctx *c, const char *tname, K kernel, dim3 grid, 
   else hipLaunchKernelGGL(kernel, grid, block, 0, st, A);
 }
 
-// ranges [c0,c1) (+ [d0,d1) behind it; fused: + [e0,e1)); fused: the launch pushes, parks and cleans up as described above
+// ranges [c0,c1) (+ [d0,d1) behind it); fused_grid > 0: the fused launch of that many workgroups that fused_sweep_setup prepared in A.fs
 template <int NDIR, bool HALO>
 static int launch(qexhip_ctx *c, DslashArgs &A, int c0, int c1, bool init, bool dot, int part_off,
-                  int d0 = 0, int d1 = 0, const char *tname = "dslash", hipStream_t st = nullptr, bool fused = false, int e0 = 0, int e1 = 0) {
+                  int d0 = 0, int d1 = 0, const char *tname = "dslash", hipStream_t st = nullptr, int fused_grid = 0) {
   if (!st) st = c->stream;
+  const bool fused = fused_grid > 0;
   if (c1 <= c0 && d1 <= d0) return 0;
   if (c1 <= c0) { c0 = d0; c1 = d1; d0 = d1 = 0; }
-  A.c0 = c0; A.c1 = c1; A.d0 = d0; A.d1 = d1; A.e0 = e0; A.e1 = e1;
+  A.c0 = c0; A.c1 = c1; A.d0 = d0; A.d1 = d1;
   A.nb1 = (c1 - c0 + 255) / 256;
-  A.nb2 = A.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0);
-  const int nb = A.nb2 + (e1 > e0 ? (e1 - e0 + 255) / 256 : 0);
+  const int nb = A.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0);
   // XCD swizzle: measured on for compressed links, off for 18-real links (profiles/r01_tune_dslash.log); output stores are
   // non-temporal (the result is read by the NEXT kernel, after 0.6 GB of links went through the caches)
   const int nsw = fused ? A.nb1 : nb;          // (the fused launch remaps its interior workgroups only)
-  A.nbA = fused ? (int)(sweep_push_fraction(c, c1 - c0) * A.nb1) : 0;
   A.swz = (c->recon != 0 && nsw >= 64 && (nsw & 7) == 0) ? nsw : 0;
   A.ntstore = 1;
   double *psave = A.partials;
   A.partials = psave ? psave + part_off : nullptr;
-  dim3 grid(nb + (fused ? A.push.nblocks + A.fz.ncl : 0)), block(256);
+  dim3 grid(fused ? fused_grid : nb), block(256);
 #define QX_LAUNCH(R) \
   do { \
     if (HALO && fused) { \
@@ -449,7 +344,7 @@ double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs) {
 }
 
 // FusedCtl of the next fused launch: five words on lines of their own + the parked-block list
-int sweep_fused_ctl(qexhip_ctx *c, int nbnd, FusedCtl *F, int nrhs) {
+static int sweep_fused_ctl(qexhip_ctx *c, int nbnd, FusedCtl *F, int nrhs) {
   if (c->fz_cap < nbnd) {
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->fz_buf) HIPCHK(hipFree(c->fz_buf));
@@ -473,6 +368,19 @@ int sweep_fused_ctl(qexhip_ctx *c, int nbnd, FusedCtl *F, int nrhs) {
     const double us = c->opt_fused_spin_us >= 0 ? (double)c->opt_fused_spin_us : std::max(25.0, nrhs * exchange_estimate_us(c));
     F->spin_ticks = (long long)(us * tick_per_us);
   }
+  return 0;
+}
+
+int fused_sweep_setup(qexhip_ctx *c, int nrhs, DevField *const *f, int parity, int lo_end, int hi_beg, FusedSweep *F,
+                      const double2 **gh_hi, const double2 **gh_lo, int *grid, int *nparts) {
+  const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (c->g.Vh - hi_beg + 255) / 256;
+  CHK(comm_halo_push_only_multi(c, nrhs, f, parity, gh_hi, gh_lo, &F->push));
+  CHK(peer_ghost_args(c, &F->pg));
+  CHK(sweep_fused_ctl(c, nb_lo + nb_hi, &F->fz, nrhs));
+  F->e0 = hi_beg; F->e1 = c->g.Vh; F->nb2 = nb_int + nb_lo;
+  F->nbA = (int)(sweep_push_fraction(c, hi_beg - lo_end, nrhs) * nb_int);
+  *grid = F->push.nblocks + nb_int + nb_lo + nb_hi + F->fz.ncl;
+  *nparts = nb_int + nb_lo + nb_hi;
   return 0;
 }
 
@@ -607,12 +515,11 @@ int dslash_sweep(qexhip_ctx *c, DevField &out, DevField &in, int parity, const D
     if (sweep_form(c, overlap) == 2) {
       // The fused sweep: the exchange is INSIDE the launch -- its first workgroups push the faces, its boundary workgroups poll the inbound
       // data words, park when those are late, its last workgroups clean up -- and neither the comm stream nor an event is involved.
-      CHK(comm_halo_push_only(c, in, 1 - parity, &A.gh_hi, &A.gh_lo, &A.push));
-      CHK(peer_ghost_args(c, &A.pg));
-      CHK(sweep_fused_ctl(c, nb_lo + nb_hi, &A.fz));
-      if (c->ndir == 8) CHK((launch<8, true>(c, A, lo_end, hi_beg, init, o.dot, 0, 0, lo_end, "dslash", nullptr, true, hi_beg, g.Vh)));
-      else CHK((launch<16, true>(c, A, lo_end, hi_beg, init, o.dot, 0, 0, lo_end, "dslash", nullptr, true, hi_beg, g.Vh)));
-      nparts = nb_int + nb_lo + nb_hi;
+      DevField *inp = &in;
+      int grid;
+      CHK(fused_sweep_setup(c, 1, &inp, 1 - parity, lo_end, hi_beg, &A.fs, &A.gh_hi, &A.gh_lo, &grid, &nparts));
+      if (c->ndir == 8) CHK((launch<8, true>(c, A, lo_end, hi_beg, init, o.dot, 0, 0, lo_end, "dslash", nullptr, grid)));
+      else CHK((launch<16, true>(c, A, lo_end, hi_beg, init, o.dot, 0, 0, lo_end, "dslash", nullptr, grid)));
     } else if (!overlap) {
       // the exchange is ordered before us on the compute stream: one launch over all sites
       // (small local volumes are launch-latency-bound; this drops two launches per CG iteration)

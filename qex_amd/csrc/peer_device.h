@@ -1,5 +1,5 @@
 // peer_device.h -- the device side of the peer transport that OTHER kernels carry (peer.hip has the transport's own kernels): bounded
-// polls, the tagged granules of the small all-reduce, and the push / wait / park pieces of the fused sweep (dslash.hip).
+// polls, the tagged granules of the small all-reduce, and the push / wait / park pieces of the fused sweeps (fused_sweep.h).
 //
 // Small all-reduces (the CG's scalars): the payload travels INSIDE the flags.  A double is cut into two 8-byte granules
 // {32 data bits, 32-bit tag = low half of the sequence number}; an aligned 8-byte store is one transaction, so a granule is
@@ -82,7 +82,7 @@ __device__ inline void peer_copy_chunk(uint4 *__restrict__ d4, const uint4 *__re
   }
 }
 
-// The push half of a face exchange as workgroups of SOMEBODY ELSE's launch (the fused sweeps: dslash.hip, batch.hip): npiece pieces per
+// The push half of a face exchange as workgroups of SOMEBODY ELSE's launch (the fused sweeps: fused_sweep.h): npiece pieces per
 // direction (one per system of a lock-step batch), piece k at k * n16 of the neighbour's arena half; workgroup blk of nblocks copies
 // its chunks, the last one through raises the data words.
 enum { PEER_PUSH_MAXPIECE = 4 };
@@ -135,7 +135,7 @@ __device__ inline void peer_push_block(const PeerPush &P, const unsigned blk) {
   }
 }
 
-// What the boundary workgroups of the fused sweep (dslash.hip: k_dslash_fused) need from the transport: the two inbound data words they
+// What the boundary workgroups of the fused sweeps (fused_sweep.h) need from the transport: the two inbound data words they
 // poll themselves (nothing is posted behind the push, nobody stays for it), under emulation the transport time counted from the
 // push's start, and the two credit words that go back to the senders once every reader of the arena is through.
 struct PeerGhost {
@@ -189,7 +189,7 @@ __device__ inline bool peer_ghost_wait(const PeerGhost &G) {
   return true;
 }
 
-// Bookkeeping of ONE fused launch in device memory of the context (dslash.hip): every boundary workgroup counts itself in `dec` once
+// Bookkeeping of ONE fused launch in device memory of the context (fused_sweep.h: fused_finish): every boundary workgroup counts itself in `dec` once
 // it has finished or parked; a parked one appends its block to `list` first.  All words are zero between launches (the last cleanup
 // workgroup resets them; launches of one stream do not overlap).
 struct FusedCtl {
