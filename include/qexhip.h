@@ -214,6 +214,24 @@ int qexhip_stag_solve(qexhip_handle h, double *x, const double *b, double mass, 
 int qexhip_stag_solve_prev(qexhip_handle h, double *x, const double *b, double mass, double r2req,
                            int maxits, int use_prev, int *iters, double *r2_final);
 
+/* Mixed-precision solves: SolverParams.sloppySolve (src/solvers/solverBase.nim:8-15), what QEX's GPU backend turns into a
+ * QUDA solve with reliable updates (src/quda/qudaWrapperImpl.nim:194-197, reliable_delta = 0.1).
+ *   sloppy = 0 (SloppyNone)   the fp64 CG: exactly qexhip_stag_solve_xx / qexhip_stag_solve_prev / qexhip_dev_solve_xx
+ *   sloppy = 1 (SloppySingle) CG iterations in fp32 (fp32 links and fields, fp32 Dslash sweeps, reductions in double), with
+ *                             reliable updates: x, b and the true residual b - A x in fp64 whenever |r_s|^2 has fallen by
+ *                             delta^2 = 0.01 since the last one, when the fp32 residual says converged, and at maxits
+ *   sloppy = 2 (SloppyHalf)   runs single: there is no half-precision format
+ * The solve stops on the TRUE (fp64) residual: r2_over_b2 is |b - A x|^2/|b|^2 of the returned x (solveXX); iters counts fp32
+ * iterations; nupdates (may be NULL) receives the number of reliable updates, the last one that confirmed convergence included
+ * (0 for sloppy = 0).  iters == maxits is not an error.  One rank only: QEXHIP_ERR_ARG for sloppy > 0 on a communicator of
+ * more than one rank, and for sloppy outside 0..2.  The fp32 copy of the links is built on first use and rebuilt whenever the
+ * operator's links have changed since (any set_links variant, t-sharding by qexhip_comm_force_halo); qexhip_release_workspace
+ * frees it. */
+int qexhip_stag_solve_xx_sloppy(qexhip_handle h, double *x, const double *b, double mass, double r2req, int maxits,
+                                int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates);
+int qexhip_stag_solve_sloppy(qexhip_handle h, double *x, const double *b, double mass, double r2req, int maxits,
+                             int use_prev, int sloppy, int *iters, double *r2_final, int *nupdates);
+
 /* multi-shift solveXX (src/physics/stagSolve.nim:296-345 + src/solvers/cgm.nim:84-315).
  * shifts[0] = base mass, shifts[k>0] = sigma_k added to m0^2; xs[k] full-volume vectors. */
 int qexhip_stag_solve_xx_multi(qexhip_handle h, double *const *xs, const double *b,
@@ -252,6 +270,15 @@ int qexhip_dev_op_xx(qexhip_handle h, int r_id, int x_id, double m2, int par_eve
 int qexhip_dev_solve_xx(qexhip_handle h, int x_id, int b_id, double mass, double r2req,
                         int maxits, int par_even, int *iters, double *r2_over_b2,
                         double *hist, int histcap);
+/* qexhip_stag_solve_xx_sloppy on resident fields */
+int qexhip_dev_solve_xx_sloppy(qexhip_handle h, int x_id, int b_id, double mass, double r2req, int maxits, int par_even,
+                               int sloppy, int *iters, double *r2_over_b2, int *nupdates);
+/* the fp32 operator of the sloppy solve on resident fp64 fields: r[par] = f64(4 m2 x32 - (2D)(2D) x32), x32 = f32(x[par]), with
+ * the fp32 links and the fp32 sweep the sloppy CG iterates with (one rank only) */
+int qexhip_dev_op_xx_sloppy(qexhip_handle h, int r_id, int x_id, double m2, int par_even);
+/* format of the fp32 link copy (building it if stale): 0 = 18 reals, 1 = rows 0,1 + sign (every link +-SU(3) to 1e-6); max_dev =
+ * the largest deviation of a stored row 2 from the sign-format rebuild (0 when the sign format is capped off by "recon" = 0) */
+int qexhip_stag_links_info_f32(qexhip_handle h, int *format, double *max_dev);
 /* Re-entry of the CG on the state the last qexhip_dev_solve_xx (or re-entry) on x_id left behind -- CgState.solve called
  * again with b2 >= 0 (src/solvers/cg.nim:21-27,85,133,155-161,256-261): no set-up, r / p / rzold kept, the stopping
  * criterion comes from the new r2req / maxits, `iters` goes on counting from where the last call stopped (maxits is the
@@ -403,7 +430,10 @@ int qexhip_stag_solve_batch(qexhip_handle h, int n, double *const *x, const doub
 int qexhip_stag_links_info(qexhip_handle h, int *nlinks, int *compressed, double *max_dev);
 /* Options of a context.  Unknown names are an error (QEXHIP_ERR_ARG).
  *   "recon"        cap on the link compression (0 keep all 18 reals, 1 sign format only, 2 also the U(3) format; default 2),
- *                  effective at the next set_links
+ *                  effective at the next set_links (the fp32 copy of the sloppy solves: 0 keeps 18 reals, else the sign format
+ *                  where it applies)
+ *   "sloppy_check" the sloppy solves post their (device-gated) reliable-update launches every this many fp32 iterations, and
+ *                  at maxits (default 4; 1: in the iteration that calls for an update)
  *   "overlap"      face exchange on the second stream beside the interior sweep: 0 never, 1 always, -1 (default) measured at
  *                  set_links when the communicator has more than one rank (qexhip_stag_sweep_info), else by interior / face
  *                  size; -2: measure on one rank too (test hook)

@@ -84,11 +84,13 @@ struct SolverParams {
   double r2req = 1e-6;
   int maxits = 50000;
   int verbosity = 1;
+  int sloppySolve = 0;         // SloppyNone / SloppySingle / SloppyHalf (solverBase.nim:8-15): > 0 = mixed-precision single-mass solves
   // outputs
   int calls = 0, iterations = 0, iterationsMax = 0;
   double seconds = 0, flops = 0, r2 = 0;
-  std::vector<double> r2hist;  // "CG iteration: k  r2/b2:" values when histcap > 0
-  void resetStats() { calls = iterations = iterationsMax = 0; seconds = flops = r2 = 0; r2hist.clear(); }
+  int reliableUpdates = 0;     // sloppySolve > 0: fp64 true-residual updates
+  std::vector<double> r2hist;  // "CG iteration: k  r2/b2:" values when histcap > 0 (fp64 solves only)
+  void resetStats() { calls = iterations = iterationsMax = reliableUpdates = 0; seconds = flops = r2 = 0; r2hist.clear(); }
   int finalIterations() const { return iterations; }
 };
 
@@ -158,6 +160,14 @@ class Staggered {
   // solveXX(s, r, x, m, sp, parEven): r <- solution, x = rhs (stagSolve.nim:57-132)
   void solveXX(Field &r, const Field &x, double m, SolverParams &sp, bool parEven = true, int histcap = 0) {
     int its = 0; double fin = 0;
+    if (sp.sloppySolve) {
+      int nup = 0;
+      timed(sp, its, [&] {
+        check(qexhip_stag_solve_xx_sloppy(c_.h, r.data(), x.data(), m, sp.r2req, sp.maxits, parEven ? 1 : 0, sp.sloppySolve, &its, &fin, &nup));
+      });
+      sp.r2 = fin; sp.reliableUpdates += nup; sp.r2hist.clear();
+      return;
+    }
     std::vector<double> hist(histcap > 0 ? histcap : 1);
     timed(sp, its, [&] {
       check(qexhip_stag_solve_xx(c_.h, r.data(), x.data(), m, sp.r2req, sp.maxits, parEven ? 1 : 0, &its, &fin, hist.data(), histcap));
@@ -170,6 +180,12 @@ class Staggered {
   // Staggered.solve(x, b, m, sp): full lattice, even-odd preconditioned, true-residual restarts
   void solve(Field &x, const Field &b, double m, SolverParams &sp) {
     int its = 0; double fin = 0;
+    if (sp.sloppySolve) {
+      int nup = 0;
+      timed(sp, its, [&] { check(qexhip_stag_solve_sloppy(c_.h, x.data(), b.data(), m, sp.r2req, sp.maxits, 0, sp.sloppySolve, &its, &fin, &nup)); });
+      sp.r2 = fin; sp.reliableUpdates += nup;
+      return;
+    }
     timed(sp, its, [&] { check(qexhip_stag_solve(c_.h, x.data(), b.data(), m, sp.r2req, sp.maxits, &its, &fin)); });
     sp.r2 = fin;
   }
@@ -182,6 +198,7 @@ class Staggered {
   // per system the result of solve(x[j], b[j], m[j], sps[j])
   void solveBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms, std::vector<SolverParams> &sps) {
     const int n = (int)xs.size();
+    for (auto &sp : sps) if (sp.sloppySolve) throw std::invalid_argument("sloppySolve: single-system solves only");
     std::vector<double *> xp; std::vector<const double *> bp; std::vector<double> rq, fin(n); std::vector<int> its(n);
     int maxits = sps.at(0).maxits;
     for (int j = 0; j < n; j++) { xp.push_back(xs[j].data()); bp.push_back(bs.at(j).data()); rq.push_back(sps.at(j).r2req); maxits = std::min(maxits, sps[j].maxits); }
@@ -196,6 +213,7 @@ class Staggered {
   }
   // multi-mass Staggered.solve(xs, b, ms, sp) (stagSolve.nim:347-446)
   void solve(std::vector<Field> &xs, const Field &b, const std::vector<double> &ms, SolverParams &sp) {
+    if (sp.sloppySolve) throw std::invalid_argument("sloppySolve: single-mass solves only");
     std::vector<double *> p;
     for (auto &x : xs) p.push_back(x.data());
     int its = 0; double fin = 0;

@@ -48,6 +48,11 @@ SYMBOLS = [
     ("qexhip_stag_outer", _ci, [_vp, _vp, _vp, _cd, _cd, _ci]),
     ("qexhip_stag_solve_xx", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd, _vp, _ci]),
     ("qexhip_stag_solve", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _pi, _pd]),
+    ("qexhip_stag_solve_xx_sloppy", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _ci, _ci, _pi, _pd, _pi]),
+    ("qexhip_stag_solve_sloppy", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _ci, _ci, _pi, _pd, _pi]),
+    ("qexhip_dev_solve_xx_sloppy", _ci, [_vp, _ci, _ci, _cd, _cd, _ci, _ci, _ci, _pi, _pd, _pi]),
+    ("qexhip_dev_op_xx_sloppy", _ci, [_vp, _ci, _ci, _cd, _ci]),
+    ("qexhip_stag_links_info_f32", _ci, [_vp, _pi, _pd]),
     ("qexhip_stag_solve_prev", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),
     ("qexhip_stag_solve_xx_multi", _ci, [_vp, _vp, _vp, _vp, _ci, _cd, _ci, _ci, _pi, _vp, _ci]),
     ("qexhip_stag_solve_multi", _ci, [_vp, _vp, _vp, _vp, _ci, _cd, _ci, _pi, _pd]),

@@ -186,6 +186,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   gauge_free(c);
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
+  f32_state_free(c);
   if (c->outer_F) (void)hipFree(c->outer_F);
   if (c->obs_table) (void)hipFree(c->obs_table);
   if (c->tile_order) (void)hipFree(c->tile_order);
@@ -256,7 +257,7 @@ extern "C" int qexhip_comm_force_halo(qexhip_handle c, int on) {
   c->force_halo = on;
   int depth = c->g.depth ? c->g.depth : 1;
   if (geom_init(c->g, c->g.X, depth, on ? 1 : 0)) return QEXHIP_ERR_ARG;
-  if (c->W) { HIPCHK(hipFree(c->W)); c->W = nullptr; c->ndir = 0; }
+  if (c->W) { HIPCHK(hipFree(c->W)); c->W = nullptr; c->ndir = 0; c->links_gen++; }
   return drop_fields_for_regeom(c);
 }
 
@@ -429,6 +430,47 @@ extern "C" int qexhip_stag_solve_prev(qexhip_handle c, double *x, const double *
   return field_download(c, *fx, x);
 }
 
+static int sloppy_check(qexhip_ctx *c, int sloppy) {
+  if (sloppy < 0 || sloppy > 2) {
+    qexhip_set_error("sloppy = %d: 0 (SloppyNone, fp64), 1 (SloppySingle) or 2 (SloppyHalf, runs single)", sloppy);
+    return QEXHIP_ERR_ARG;
+  }
+  if (sloppy > 0 && c->nranks > 1) {
+    qexhip_set_error("sloppy solves run on one rank only (communicator of %d ranks)", c->nranks);
+    return QEXHIP_ERR_ARG;
+  }
+  return 0;
+}
+
+extern "C" int qexhip_stag_solve_xx_sloppy(qexhip_handle c, double *x, const double *b, double mass, double r2req, int maxits,
+                                           int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates) {
+  if (!c || !x || !b) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, sloppy));
+  if (nupdates) *nupdates = 0;
+  if (!sloppy) return qexhip_stag_solve_xx(c, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nullptr, 0);
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb, *fx;
+  CHK(host_in(c, WK_IN, b, &fb));
+  CHK(get_work(c, WK_OUT, &fx));
+  CHK(solve_xx_sloppy_dev(c, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates));
+  return field_download(c, *fx, x);
+}
+
+extern "C" int qexhip_stag_solve_sloppy(qexhip_handle c, double *x, const double *b, double mass, double r2req, int maxits,
+                                        int use_prev, int sloppy, int *iters, double *r2_final, int *nupdates) {
+  if (!c || !x || !b) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, sloppy));
+  if (nupdates) *nupdates = 0;
+  if (!sloppy) return qexhip_stag_solve_prev(c, x, b, mass, r2req, maxits, use_prev, iters, r2_final);
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb, *fx;
+  CHK(host_in(c, WK_IN, b, &fb));
+  if (use_prev) CHK(host_in(c, WK_OUT, x, &fx));
+  else CHK(get_work(c, WK_OUT, &fx));
+  CHK(solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, use_prev, sloppy, nupdates));
+  return field_download(c, *fx, x);
+}
+
 static int multi_common(qexhip_ctx *c, double *const *xs, const double *b, const double *vals, int nmass,
                         double r2req, int maxits, int par_even, int full, int *iters, double *out, double *hist,
                         int histcap) {
@@ -575,6 +617,40 @@ extern "C" int qexhip_dev_solve_xx(qexhip_handle c, int x_id, int b_id, double m
   return solve_xx_dev(c, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, hist, histcap);
 }
 
+extern "C" int qexhip_dev_solve_xx_sloppy(qexhip_handle c, int x_id, int b_id, double mass, double r2req, int maxits, int par_even,
+                                          int sloppy, int *iters, double *r2_over_b2, int *nupdates) {
+  if (!c) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, sloppy));
+  if (nupdates) *nupdates = 0;
+  if (!sloppy) return qexhip_dev_solve_xx(c, x_id, b_id, mass, r2req, maxits, par_even, iters, r2_over_b2, nullptr, 0);
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fx, *fb;
+  CHK(find_field(c, x_id, &fx));
+  CHK(find_field(c, b_id, &fb));
+  if (x_id == b_id) { qexhip_set_error("dev_solve_xx_sloppy: the solution field is the source field"); return QEXHIP_ERR_ARG; }
+  return solve_xx_sloppy_dev(c, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
+}
+extern "C" int qexhip_dev_op_xx_sloppy(qexhip_handle c, int r_id, int x_id, double m2, int par_even) {
+  if (!c) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, 1));
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fr, *fx;
+  CHK(find_field(c, r_id, &fr));
+  CHK(find_field(c, x_id, &fx));
+  DevFieldF *xi, *ro;
+  CHK(f32_field(c, F32_IN, &xi));
+  CHK(f32_field(c, F32_AP, &ro));
+  const int px = par_even ? 0 : 1;
+  CHK(f32_from_f64(c, *xi, *fx, px, 1.0));
+  CHK(f32_op_xx(c, *ro, *xi, m2, par_even, 0, nullptr, nullptr));
+  return f32_to_f64(c, *fr, *ro, px, 1.0, 0);
+}
+extern "C" int qexhip_stag_links_info_f32(qexhip_handle c, int *format, double *max_dev) {
+  if (!c) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  return f32_links(c, format, max_dev);
+}
+
 extern "C" int qexhip_dev_solve_xx_continue(qexhip_handle c, int x_id, double r2req, int maxits, int *iters, double *r2_over_b2,
                                             double *hist, int histcap) {
   if (!c) return QEXHIP_ERR_ARG;
@@ -617,6 +693,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
     }
   }
   gauge_release_scratch(c);
+  f32_state_free(c);                 // the mixed-precision CG's fp32 links and fields: rebuilt by the next sloppy solve
   return 0;
 }
 
@@ -734,6 +811,10 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
   else if (n == "emu_link_gbs") c->emu_link_gbs = value;
   else if (n == "obs_clover") c->opt_obs_clover = value;
   else if (n == "force_pair") c->opt_force_pair = value;
+  else if (n == "sloppy_check") {
+    if (value < 1) { qexhip_set_error("option sloppy_check: >= 1 fp32 iterations"); return QEXHIP_ERR_ARG; }
+    c->opt_sloppy_check = value;
+  }
   else { qexhip_set_error("unknown option"); return QEXHIP_ERR_ARG; }
   return 0;
 }

@@ -228,6 +228,7 @@ __global__ void __launch_bounds__(256) k_links_compress(size_t nrows, const doub
 }
 int links_compress(qexhip_ctx *c) {
   const Geom &g = c->g;
+  c->links_gen++;                                        // every writer of W ends here: the fp32 copy (dslash_f32.hip) is stale now
   c->recon = 0;
   if (!c->opt_recon || !c->W) return 0;
   const size_t nrows = (size_t)2 * g.ntile * c->ndir;

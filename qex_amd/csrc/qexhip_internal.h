@@ -46,6 +46,23 @@ struct DevField {  // full-volume colour vector: parity halves, each with its gh
   double2 *par(int p) const { return d + (size_t)p * half; }
 };
 
+struct DevFieldF {  // fp32 colour vector of the mixed-precision CG: float2 v[tile][3][64] per parity (vec_off), no ghost tiles
+  float2 *d = nullptr;
+  size_t half = 0;  // float2 elements per parity half (= ntile*192)
+  float2 *par(int p) const { return d + (size_t)p * half; }
+};
+
+// state of the reliable-update CG (dslash_f32.hip, solver.cpp: solve_xx_sloppy_dev), resident on the device
+struct SlpScal {
+  double b2, r2stop;
+  double r2t;                 // |b - A x|^2 of the last reliable update (fp64)
+  double sigma, sigma_p;      // r_s = r / sigma; p_s is in units of sigma_p
+  double r2s, r2s_old, maxr2s;   // |r_s|^2 now, one iteration back, max since the last update (units of sigma)
+  int k, maxits, nupd;
+  int done, upd, noupd;       // noupd = !upd: the `done` word the gated fp64 sweeps read
+  int conv, first;            // the next k_slp_xpay rebuilds r_s from the fp64 residual / restarts p_s = r_s
+};
+
 // CG scalars resident on the device (no host round trip per iteration)
 struct CgScal {
   double b2, r2, rzo, pAp, r2stop, tmp;
@@ -176,6 +193,10 @@ struct qexhip_ctx {
   int lds_attr_done = 0;                             // per context (= per device): which kernels had MaxDynamicSharedMemorySize raised (bit 0 k_force_lds, 1 k_flow_obs_clover, 2 k_flow_obs_clover2, 3 k_force_lds2, 4 k_projUderiv_batch)
   void *cgm_scal = nullptr;                          // CgmScal of the multi-shift solver (multishift.hip)
   double *meson_buf = nullptr; size_t meson_cap = 0; // workgroup partials + global table of the meson / slice-norm reductions (meson.hip)
+  unsigned long links_gen = 0;                       // bumped by every writer of W / Wc (links_compress ends each of them): the fp32 copy's staleness test
+  void *f32 = nullptr;                               // F32State (dslash_f32.hip): fp32 links + fields + SlpScal of the mixed-precision CG
+  int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
+                                                     // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
 
 // work-field slots (get_work)
@@ -295,6 +316,22 @@ void sweep_plan(const qexhip_ctx *c, int *lo_end, int *hi_beg, int *overlap);   
 int sweep_form(const qexhip_ctx *c, int overlap);                              // 2 fused / 0 by sites: what an overlapped sweep runs as
 double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs = 1);   // where in the dispatch order the fused sweep's boundary workgroups go
 
+// ---- dslash_f32.hip (mixed-precision CG, one rank) ----
+enum { F32_T = 0, F32_R, F32_P, F32_AP, F32_X, F32_IN, F32_NF };   // fp32 work fields
+#define SLP_DELTA 0.1                                    // reliable-update delta (QEX's reliable_delta, qudaSet.nim:63)
+int f32_links(qexhip_ctx *c, int *fmt, double *dev);     // the fp32 copy of the links, rebuilt when links_gen moved
+int f32_field(qexhip_ctx *c, int slot, DevFieldF **f);
+int f32_op_xx(qexhip_ctx *c, DevFieldF &r, DevFieldF &x, double m2, int par_even, int dot, const int *done, int *nparts);
+int f32_from_f64(qexhip_ctx *c, DevFieldF &y, const DevField &x, int parity, double a);              // y = f32(a x)
+int f32_to_f64(qexhip_ctx *c, DevField &y, const DevFieldF &x, int parity, double a, int accumulate);  // y (+)= a x
+void f32_state_free(qexhip_ctx *c);
+int slp_alloc(qexhip_ctx *c, SlpScal **s);
+int slp_init(qexhip_ctx *c, SlpScal *s, double r2req, int maxits);
+int slp_xpay(qexhip_ctx *c, SlpScal *s, DevFieldF &p, DevFieldF &rs, const DevField &r, int parity);
+int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const DevFieldF &p, const DevFieldF &Ap, int parity, int ndot);
+int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity);
+int slp_resid(qexhip_ctx *c, SlpScal *s, DevField &r, const DevField &b, const DevField &Ax, int parity);
+
 // ---- blas.hip ----
 int blas_zero(qexhip_ctx *c, DevField &f, int parity);
 int blas_copy(qexhip_ctx *c, DevField &dst, const DevField &src, int parity);
@@ -326,7 +363,9 @@ int solve_xx_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2
                  int par_even, int *iters, double *r2_over_b2, double *hist, int histcap);
 int solve_xx_continue_dev(qexhip_ctx *c, DevField &x, double r2req, int maxits, int *iters, double *r2_over_b2, double *hist, int histcap);
 int solve_full_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits,
-                   int *iters, double *r2_final, int use_prev = 0);
+                   int *iters, double *r2_final, int use_prev = 0, int sloppy = 0, int *nupdates = nullptr);
+int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                        int *iters, double *r2_over_b2, int *nupdates);
 int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts,
                        int nmass, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);
 int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *masses,

@@ -22,6 +22,8 @@ from . import _lib
 from ._lib import check, lib
 
 EVEN, ODD, ALL = 0, 1, 2
+# SolverParams.sloppySolve (solverBase.nim:8-15): SloppyHalf runs single precision -- there is no half-precision format
+SloppyNone, SloppySingle, SloppyHalf = 0, 1, 2
 _SUBSET = {"even": EVEN, "odd": ODD, "all": ALL}
 
 
@@ -36,11 +38,12 @@ def _p(a):
 class SolverParams:
     """solverBase.nim:10-58 (fields the staggered path uses)."""
 
-    def __init__(self, r2req=1e-6, maxits=50000, verbosity=1, usePrevSoln=False):
+    def __init__(self, r2req=1e-6, maxits=50000, verbosity=1, usePrevSoln=False, sloppySolve=SloppyNone):
         self.r2req = r2req
         self.maxits = maxits
         self.verbosity = verbosity
         self.usePrevSoln = usePrevSoln
+        self.sloppySolve = sloppySolve
         self.subsetName = "all"
         self.resetStats()
 
@@ -52,6 +55,7 @@ class SolverParams:
         self.flops = 0.0
         self.r2 = 0.0
         self.r2hist = None
+        self.reliableUpdates = 0   # mixed-precision solves (sloppySolve != 0): fp64 true-residual updates
 
     @property
     def finalIterations(self):
@@ -221,6 +225,24 @@ class Context:
                                               (C.c_double * n)(*[float(v) for v in shifts]), n, float(r2req), int(maxits),
                                               1 if par_even else 0, C.byref(its), _p(hist), histcap))
         return its.value, hist[: min(histcap, its.value + 1)]
+
+    def dev_solve_xx_sloppy(self, x_id, b_id, mass, r2req, maxits, par_even=True, sloppy=SloppySingle):
+        """mixed-precision solveXX on resident fields (qexhip_dev_solve_xx_sloppy); returns (fp32 iterations, true r2/b2,
+        reliable updates)"""
+        its, fin, nup = C.c_int(0), C.c_double(0), C.c_int(0)
+        check(lib().qexhip_dev_solve_xx_sloppy(self._h, int(x_id), int(b_id), float(mass), float(r2req), int(maxits),
+                                               1 if par_even else 0, int(sloppy), C.byref(its), C.byref(fin), C.byref(nup)))
+        return its.value, fin.value, nup.value
+
+    def dev_op_xx_sloppy(self, r_id, x_id, m2, par_even=True):
+        """r[par] = 4 m2 x - (2D)(2D) x with the sloppy solve's fp32 links and sweep (x rounded to fp32, the result back to fp64)"""
+        check(lib().qexhip_dev_op_xx_sloppy(self._h, int(r_id), int(x_id), float(m2), 1 if par_even else 0))
+
+    def links_info_f32(self):
+        """(format, max deviation) of the fp32 link copy of the sloppy solves: 0 = 18 reals, 1 = rows 0,1 + sign"""
+        f, dev = C.c_int(0), C.c_double(0)
+        check(lib().qexhip_stag_links_info_f32(self._h, C.byref(f), C.byref(dev)))
+        return f.value, dev.value
 
     def release_workspace(self):
         check(lib().qexhip_release_workspace(self._h))
@@ -397,8 +419,17 @@ class Staggered:
         t0 = time.time()
         its, fin = C.c_int(0), C.c_double(0)
         hist = np.zeros(max(histcap, 1))
-        check(lib().qexhip_stag_solve_xx(self.ctx._h, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
-                                         1 if parEven else 0, C.byref(its), C.byref(fin), _p(hist), histcap))
+        sloppy = int(getattr(sp, "sloppySolve", SloppyNone))
+        if sloppy != SloppyNone:
+            # mixed precision (no residual history: the fp32 iterations' residuals are not the true ones)
+            nup = C.c_int(0)
+            check(lib().qexhip_stag_solve_xx_sloppy(self.ctx._h, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
+                                                    1 if parEven else 0, sloppy, C.byref(its), C.byref(fin), C.byref(nup)))
+            sp.reliableUpdates += nup.value
+            histcap = 0
+        else:
+            check(lib().qexhip_stag_solve_xx(self.ctx._h, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
+                                             1 if parEven else 0, C.byref(its), C.byref(fin), _p(hist), histcap))
         sp.calls += 1
         sp.iterations += its.value
         sp.iterationsMax = max(sp.iterationsMax, its.value)
@@ -419,7 +450,15 @@ class Staggered:
         """Staggered.solve: x (array or list of arrays) <- D(m)^-1 b  (stagSolve.nim:224-294,347-446)"""
         t0 = time.time()
         its, fin = C.c_int(0), C.c_double(0)
-        if isinstance(x, (list, tuple)):
+        sloppy = int(getattr(sp, "sloppySolve", SloppyNone))
+        if isinstance(x, (list, tuple)) and sloppy != SloppyNone:
+            raise ValueError("sloppySolve applies to single-mass solves only (multi-shift solves run in fp64)")
+        if sloppy != SloppyNone:
+            nup = C.c_int(0)
+            check(lib().qexhip_stag_solve_sloppy(self.ctx._h, _p(x), _p(b), float(m), float(sp.r2req), int(sp.maxits),
+                                                 1 if sp.usePrevSoln else 0, sloppy, C.byref(its), C.byref(fin), C.byref(nup)))
+            sp.reliableUpdates += nup.value
+        elif isinstance(x, (list, tuple)):
             ms = np.array([float(v) for v in m], dtype=np.float64)
             ptrs = (C.c_void_p * len(x))(*[_p(a).value for a in x])
             check(lib().qexhip_stag_solve_multi(self.ctx._h, ptrs, _p(b), _p(ms), len(x), float(sp.r2req),
@@ -456,6 +495,8 @@ class Staggered:
         all systems.  sps: one SolverParams (shared r2req / maxits) or one per system; each gets the
         statistics of its own system, exactly as n calls of solve would record them."""
         sl = [sps] * len(xs) if isinstance(sps, SolverParams) else list(sps)
+        if any(int(getattr(sp, "sloppySolve", SloppyNone)) != SloppyNone for sp in sl):
+            raise ValueError("sloppySolve applies to single-system solves only (lock-step batched solves run in fp64)")
         t0 = time.time()
         its, fin = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl))
         dt = (time.time() - t0) / len(xs)
@@ -474,6 +515,8 @@ class Staggered:
 
     def solveXX_multi(self, xs, b, shifts, sp, parEven=True, histcap=0):
         """Staggered.solveXX(xs, b, ms, sp, subset) (stagSolve.nim:296-345): shifts[0] = base mass."""
+        if int(getattr(sp, "sloppySolve", SloppyNone)) != SloppyNone:
+            raise ValueError("sloppySolve applies to single-mass solves only (multi-shift solves run in fp64)")
         its = C.c_int(0)
         sh = np.array([float(v) for v in shifts], dtype=np.float64)
         hist = np.zeros(max(histcap, 1))
