@@ -428,10 +428,23 @@ int qexhip_stag_solve_batch(qexhip_handle h, int n, double *const *x, const doub
  * chosen format.  Row 2 is rebuilt in registers.  QEXHIP_RECON=0|1|2 caps the format.  No counterpart in QEX (its
  * CPU Dslash always reads full links, stagD.nim:349-395); QUDA's reconstruct-12/13 is the precedent. */
 int qexhip_stag_links_info(qexhip_handle h, int *nlinks, int *compressed, double *max_dev);
+/* Bytes the 8- or 16-link sweep streams per link at the last set_links: 96 / 112 for formats 1 / 2, 144 for 18 reals, and 108 for
+ * the lossless residual format.  That one is taken by 8-link operators that fit neither format 1 nor 2 (QEX's `random` start):
+ * rows 0,1 are stored exactly, row 2 as int16 multiples of one ulp of its rebuild +-conj(row0 x row1), and a link whose row 2 this
+ * does not reproduce bit for bit is "escaped" (its row 2 is read from the 18 reals).  The operator is the 18-real one bit for bit,
+ * so qexhip_stag_links_info reports format 0.  Taken when at most 1 % of the links escape; option "lossless" = 0 (or "recon"
+ * = 0) keeps it off.  escaped = the links the last encoding escaped (0 if it did not run). */
+int qexhip_stag_links_storage(qexhip_handle h, int *bytes_per_link, long long *escaped);
+/* The residual format's encoder and decoder on the host, for n links of 18 doubles (3x3 complex, row-major, re/im): escaped[i] =
+ * link i is escaped; row2[6 i ..] = its row 2 as decoded (the rebuild for an escaped link).  Either output may be null.  Needs no
+ * device. */
+int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped, double *row2);
 /* Options of a context.  Unknown names are an error (QEXHIP_ERR_ARG).
  *   "recon"        cap on the link compression (0 keep all 18 reals, 1 sign format only, 2 also the U(3) format; default 2),
  *                  effective at the next set_links (the fp32 copy of the sloppy solves: 0 keeps 18 reals, else the sign format
- *                  where it applies)
+ *                  where it applies); 0 also keeps the lossless format off
+ *   "lossless"     1 (default): 8-link operators that fit neither compressed format take the lossless 108-byte residual format
+ *                  (qexhip_stag_links_storage) if at most 1 % of their links escape it; 0: 18 reals.  Effective at the next set_links
  *   "sloppy_check" the sloppy solves post their (device-gated) reliable-update launches every this many fp32 iterations, and
  *                  at maxits (default 4; 1: in the iteration that calls for an update)
  *   "overlap"      face exchange on the second stream beside the interior sweep: 0 never, 1 always, -1 (default) measured at

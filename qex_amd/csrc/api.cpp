@@ -195,6 +195,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   if (c->meson_buf) (void)hipFree(c->meson_buf);
   if (c->Wc) (void)hipFree(c->Wc);
   if (c->Ws) (void)hipFree(c->Ws);
+  if (c->Wm) (void)hipFree(c->Wm);
   if (c->stage) (void)hipFree(c->stage);
   if (c->partials) (void)hipFree(c->partials);
   if (c->dscal) (void)hipFree(c->dscal);
@@ -790,6 +791,7 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
   if (!c || !name) return QEXHIP_ERR_ARG;
   const std::string n(name);
   if (n == "recon") c->opt_recon = value;            // takes effect at the next set_links
+  else if (n == "lossless") c->opt_lossless = value;   // takes effect at the next set_links
   else if (n == "overlap") c->opt_overlap = value;
   else if (n == "transport") {
     if (comm_ready(c)) { qexhip_set_error("option transport must be set before qexhip_comm_init"); return QEXHIP_ERR_STATE; }
@@ -836,6 +838,16 @@ extern "C" int qexhip_stag_links_info(qexhip_handle c, int *nlinks, int *compres
   if (compressed) *compressed = c->recon;
   if (max_dev) *max_dev = c->recon_dev;
   return 0;
+}
+extern "C" int qexhip_stag_links_storage(qexhip_handle c, int *bytes_per_link, long long *escaped) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (bytes_per_link) *bytes_per_link = !c->W ? 0 : (c->lres ? 108 : (c->recon == 1 ? 96 : (c->recon == 2 ? 112 : 144)));
+  if (escaped) *escaped = c->lres_esc;
+  return 0;
+}
+extern "C" int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped, double *row2) {
+  if (!links || n < 0) return QEXHIP_ERR_ARG;
+  return link_residual_host((const double2 *)links, n, escaped, (double2 *)row2);
 }
 extern "C" int qexhip_hisq_prepare(qexhip_handle c, const double *g, double *fl, double *ll) {
   if (!c || !g) return QEXHIP_ERR_ARG;

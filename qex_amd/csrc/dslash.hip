@@ -6,7 +6,7 @@
 // wavefront per 64-site tile: the wavefront streams its contiguous block of links (72 KiB /
 // 144 KiB) with 16-byte loads, neighbour vectors come from the opposite-parity field with
 // unit-stride (x), row-stride (y), plane-stride (z) or slice-stride (t) access, all coalesced.
-// HBM-bound: 1248 B and 570 flop per site (1-hop), no MFMA on purpose.
+// HBM-bound: 1248 B and 570 flop per site (1-hop; 960 B on the lossless 108-byte links, link_residual.h), no MFMA on purpose.
 //
 // Two kernels with disjoint roles (round 6; rounds 4-5 had one kernel with seven template parameters):
 //   k_dslash<NDIR, HALO, INIT, DOT, RECON>     every sweep that reads its t-neighbours from the FIELD: the whole lattice on one GPU, and on a
@@ -28,8 +28,8 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 
 struct DslashArgs {
   Geom g;
-  const double2 *W;      // links of the output parity (RECON: rows 0,1 only, [tile][dir][6][64])
-  const unsigned long long *S;   // RECON: sign masks [tile][dir], bit = lane
+  const double2 *W;      // links of the output parity (RECON 1, 2: rows 0,1 (+ det) only, [tile][dir][6|7][64]; 3: link_residual.h rows)
+  const unsigned long long *S;   // RECON 1: sign masks [tile][dir], bit = lane; 3: [tile][dir][sign, escape] (S[-2]: this parity's W)
   const double2 *in;     // hop source (opposite parity half)
   double2 *out;          // output parity half
   const double2 *rin;    // a-term
@@ -82,10 +82,10 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
     const int tu = FUSED ? __builtin_amdgcn_readfirstlane(s.t) : 0;
     double2 acc[3];
     double2 xsv[3];
-    constexpr int NLOAD = RECON == 1 ? 6 : (RECON == 2 ? 7 : 9);
-    constexpr int LROW = NLOAD * 64;             // double2 per (tile, direction)
+    constexpr int NLOAD = (RECON == 1 || RECON == 3) ? 6 : (RECON == 2 ? 7 : 9);
+    constexpr int LROW = RECON == 3 ? LR_ROW : NLOAD * 64;      // double2 per (tile, direction)
     const double2 *w = A.W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63);
-    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : nullptr;
+    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : (RECON == 3 ? A.S + (size_t)(c >> 6) * NDIR * 2 : nullptr);
     // fused: hops that leave the slab read the neighbours' faces where the neighbours WROTE them -- the transport's receive arena --
     // instead of the field's ghost tiles: which base a t-hop reads from is wavefront-uniform, four scalar selects, nothing per lane
     const double2 *in_f1 = A.in, *in_b1 = A.in, *in_f3 = A.in, *in_b3 = A.in;
@@ -125,6 +125,12 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
         const int lane = c & 63;
         if (do_f) recon_row2<1>(U, (sm[2 * pr] >> lane) & 1ull);
         if (do_b) recon_row2<1>(W, (sm[2 * pr + 1] >> lane) & 1ull);
+      } else if (RECON == 3) {
+        // row 2 = rebuild + int16 residuals (link_residual.h), bit for bit the 18-real link; an escaped lane reads it from W
+        const int lane = c & 63;
+        const size_t fr = ((size_t)(c >> 6) * NDIR + 2 * pr) * 576 + lane;
+        if (do_f) recon_row2_res(U, wp - lane, sm + 4 * pr, A.S - 2, fr, lane);
+        if (do_b) recon_row2_res(W, wp - lane + LROW, sm + 4 * pr + 2, A.S - 2, fr + 576, lane);
       } else if (RECON == 2) {
         if (do_f) recon_row2<2>(U, false);
         if (do_b) recon_row2<2>(W, false);
@@ -195,7 +201,8 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       //          spills to scratch (290-330 us) -- never unroll the 16-link loop completely.
       // mu/hop are wave-uniform, so the neighbour arithmetic of the rolled loop branches on scalars.
       // compressed 8-link kernel (rows 0,1 + sign, 864 B/site): rolled 80.2 us, x2 81.9, x4 83.5 (32^4, in CG)
-      constexpr int UNR = (NDIR == 8) ? (RECON ? 1 : 4) : 2;
+      // lossless 8-link kernel (108 B/link, 960 B/site): x2 83.8 us, rolled 88.5 (32^4, bench.py); the fused sweep stays rolled
+      constexpr int UNR = (NDIR == 8) ? (RECON == 3 ? (FUSED ? 1 : 2) : (RECON ? 1 : 4)) : 2;
       if (!edge) {
         // every hop of the site: the loop of the one-launch kernel
 #pragma unroll UNR
@@ -232,7 +239,9 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       }
     }
     if (DOT && !skip && !parked) {
-      const int pidx = !FUSED ? (int)blockIdx.x : fused_partial_slot(A.fs, R, lb);
+      // (RECON 3: the slot of the logical block, which the XCD swizzle leaves where the unswizzled launch puts it -- the partials are
+      // summed in slot order, and this format computes the 18-real operator's bits, the residual history included)
+      const int pidx = !FUSED ? (RECON == 3 ? lb : (int)blockIdx.x) : fused_partial_slot(A.fs, R, lb);
       double r = block_sum_256(dotv);
       if (threadIdx.x == 0) A.partials[pidx] = r;
     }
@@ -268,9 +277,10 @@ static int launch(qexhip_ctx *c, DslashArgs &A, int c0, int c1, bool init, bool 
   A.nb1 = (c1 - c0 + 255) / 256;
   const int nb = A.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0);
   // XCD swizzle: measured on for compressed links, off for 18-real links (profiles/r01_tune_dslash.log); output stores are
-  // non-temporal (the result is read by the NEXT kernel, after 0.6 GB of links went through the caches)
+  // non-temporal (the result is read by the NEXT kernel, after 0.6 GB of links went through the caches).  The lossless format
+  // takes it in the one-launch kernel only: the fused kernel's dot partials go by dispatch slot, which the remap would reorder
   const int nsw = fused ? A.nb1 : nb;          // (the fused launch remaps its interior workgroups only)
-  A.swz = (c->recon != 0 && nsw >= 64 && (nsw & 7) == 0) ? nsw : 0;
+  A.swz = ((c->recon != 0 || (c->lres && !fused)) && nsw >= 64 && (nsw & 7) == 0) ? nsw : 0;
   A.ntstore = 1;
   double *psave = A.partials;
   A.partials = psave ? psave + part_off : nullptr;
@@ -289,7 +299,10 @@ static int launch(qexhip_ctx *c, DslashArgs &A, int c0, int c1, bool init, bool 
   } while (0)
   if (c->recon == 1) QX_LAUNCH(1);
   else if (c->recon == 2) QX_LAUNCH(2);
-  else QX_LAUNCH(0);
+  else if constexpr (NDIR == 8) {
+    if (c->lres) QX_LAUNCH(3);
+    else QX_LAUNCH(0);
+  } else QX_LAUNCH(0);
 #undef QX_LAUNCH
   A.partials = psave;
   HIPCHK(hipGetLastError());
@@ -338,7 +351,7 @@ static double exchange_estimate_us(const qexhip_ctx *c) {
 // about one exchange time, then parks), but the waiting ones do hold slots meanwhile.
 // nrhs > 1 (the lock-step batch): the links once, the vectors and the faces nrhs times.
 double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs) {
-  const double bsite = c->ndir * (c->recon == 1 ? 96.0 : (c->recon == 2 ? 112.0 : 144.0)) + 120.0 * nrhs;
+  const double bsite = c->ndir * (c->recon == 1 ? 96.0 : (c->recon == 2 ? 112.0 : (c->lres ? 108.0 : 144.0))) + 120.0 * nrhs;
   const double t_int = (double)interior_sites * bsite / 5.5e6;       // us
   return t_int > 0 ? std::min(1.0, std::max(0.65, nrhs * exchange_estimate_us(c) / t_int)) : 1.0;
 }
@@ -484,6 +497,9 @@ int dslash_sweep(qexhip_ctx *c, DevField &out, DevField &in, int parity, const D
   if (c->recon) {
     A.W = c->Wc + (size_t)parity * g.ntile * c->ndir * (c->recon == 1 ? 384 : 448);
     A.S = c->Ws + (size_t)parity * g.ntile * c->ndir;
+  } else if (c->lres) {
+    A.W = c->Wc + (size_t)parity * g.ntile * c->ndir * LR_ROW;
+    A.S = c->Wm + (size_t)parity * (2 + g.ntile * c->ndir * 2) + 2;
   } else {
     A.W = c->W + (size_t)parity * g.ntile * c->ndir * 576;
     A.S = nullptr;

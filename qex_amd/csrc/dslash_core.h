@@ -1,6 +1,7 @@
 // dslash_core.h -- device pieces shared by the Dslash kernels (dslash.hip, batch.hip)
 #pragma once
 #include <hip/hip_runtime.h>
+#include "link_residual.h"
 
 typedef double d2v __attribute__((ext_vector_type(2)));
 
@@ -51,6 +52,23 @@ __device__ __forceinline__ void recon_row2(double2 U[9], bool neg) {
   for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
 }
 
+// lossless format (RECON 3, link_residual.h): row 2 of a link whose rows 0,1 are in U[0..5].  `row` = the link's (tile, dir) row,
+// `m` its [sign, escape] masks; an escaped lane reads row 2 from the 18 reals: element `fr` of W's parity half, whose address the
+// header `hdr` of the parity's mask block holds (the kernels' argument block stays as it is)
+__device__ __forceinline__ void recon_row2_res(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
+                                               size_t fr, int lane) {
+  const uint64_t lo = __builtin_nontemporal_load((const uint64_t *)(row + LR_RES) + lane);
+  const uint32_t hi = __builtin_nontemporal_load((const uint32_t *)(row + LR_RES + 32) + lane);
+  double2 r2[3];
+  lr_decode(U, (m[0] >> lane) & 1ull, lo, hi, r2);
+  if ((m[1] >> lane) & 1ull) {
+    const double2 *wf = (const double2 *)(uintptr_t)hdr[0] + fr;
+#pragma unroll
+    for (int k = 0; k < 3; k++) r2[k] = wf[(6 + k) * 64];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
+}
 
 // one link of the operator's storage as the sweep reads it: `w` points at this lane's element of the (tile, dir) row of W
 // (RECON 0: 9 double2) or Wc (RECON 1: rows 0,1; RECON 2: rows 0,1 + det), `sm` at the row's sign mask (RECON 1 only)

@@ -5,6 +5,7 @@
 #include <vector>
 #include "qexhip_internal.h"
 #include "site_index.h"
+#include "link_residual.h"
 #include <cstring>
 
 int geom_init(Geom &g, const int X[4], int depth, int halo) {
@@ -226,10 +227,56 @@ __global__ void __launch_bounds__(256) k_links_compress(size_t nrows, const doub
   }
   if (l == 0 && bits > __hip_atomic_load(maxdev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxdev, bits);
 }
+// The lossless residual format (link_residual.h) of an 8-link operator whose links fit neither format 1 nor 2 (QEX's g.random is
+// unitary only to ~1e-11, but to a few ulp for almost every link): rows 0,1 into Wc (row stride LR_ROW), the int16 residuals of
+// row 2 behind them, sign and escape masks into Wm[parity][2 + prows][2] (each parity's block behind a header: the host writes it);
+// `nesc` counts the escaped links (one atomic per wavefront).
+__global__ void __launch_bounds__(256) k_links_residual(size_t nrows, size_t prows, const double2 *__restrict__ W, double2 *Wc,
+                                                        unsigned long long *Wm, unsigned int *nesc) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // (row = (parity, tile, dir), lane)
+  const size_t row = j >> 6;
+  if (row >= nrows) return;
+  const int l = j & 63;
+  const double2 *w = W + row * 576 + l;
+  double2 *o = Wc + row * LR_ROW + l;
+  double2 u[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) u[k] = w[k * 64];
+#pragma unroll
+  for (int k = 0; k < 6; k++) o[k * 64] = u[k];
+  bool neg;
+  uint64_t lo;
+  uint32_t hi;
+  const bool ok = lr_encode(u, &neg, &lo, &hi);
+  ((uint64_t *)(Wc + row * LR_ROW + LR_RES))[l] = lo;
+  ((uint32_t *)(Wc + row * LR_ROW + LR_RES + 32))[l] = hi;
+  const unsigned long long sgn = __ballot(neg), esc = __ballot(!ok);
+  if (l == 0) {
+    unsigned long long *m = Wm + 2 * (row + row / prows + 1);
+    m[0] = sgn;
+    m[1] = esc;
+    if (esc) atomicAdd(nesc, (unsigned int)__popcll(esc));
+  }
+}
+
+// The same encoder and decoder on the host (qexhip_link_residual_host): n links of 9 double2 each
+int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2 *row2) {
+  for (long i = 0; i < n; i++) {
+    bool neg;
+    uint64_t lo;
+    uint32_t hi;
+    const bool ok = lr_encode(u + 9 * i, &neg, &lo, &hi);
+    if (escaped) escaped[i] = !ok;
+    if (row2) lr_decode(u + 9 * i, neg, lo, hi, row2 + 3 * i);
+  }
+  return 0;
+}
+
 int links_compress(qexhip_ctx *c) {
   const Geom &g = c->g;
   c->links_gen++;                                        // every writer of W ends here: the fp32 copy (dslash_f32.hip) is stale now
   c->recon = 0;
+  c->lres = 0; c->lres_esc = 0;
   if (!c->opt_recon || !c->W) return 0;
   const size_t nrows = (size_t)2 * g.ntile * c->ndir;
   if (c->Wc_rows < nrows) {
@@ -254,6 +301,27 @@ int links_compress(qexhip_ctx *c) {
     memcpy(&dev, &bits, sizeof(dev));
     if (fmt == 1 || dev <= 5e-14f) c->recon_dev = dev;
     if (dev <= 5e-14f) { c->recon = fmt; break; }
+  }
+  // neither format holds: the residual format when at most 1 % of the links escape it (8-link operators; it stores the same
+  // operator bit for bit, so qexhip_stag_links_info keeps reporting format 0)
+  if (!c->recon && c->opt_lossless && c->ndir == 8) {
+    if (!c->Wm || c->Wm_rows < nrows) {
+      if (c->Wm) HIPCHK(hipFree(c->Wm));
+      c->Wm = nullptr; c->Wm_rows = 0;
+      HIPCHK(hipMalloc((void **)&c->Wm, (nrows + 2) * 2 * sizeof(unsigned long long)));
+      c->Wm_rows = nrows;
+    }
+    const size_t prows = nrows / 2;
+    HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
+    k_links_residual<<<nblk, 256, 0, c->stream>>>(nrows, prows, c->W, c->Wc, c->Wm, flag);
+    HIPCHK(hipGetLastError());
+    unsigned int nesc = 0;
+    HIPCHK(hipMemcpyAsync(&nesc, flag, sizeof(nesc), hipMemcpyDeviceToHost, c->stream));
+    const unsigned long long hdr[2][2] = {{(unsigned long long)(uintptr_t)c->W, 0}, {(unsigned long long)(uintptr_t)(c->W + prows * 576), 0}};
+    for (int p = 0; p < 2; p++) HIPCHK(hipMemcpyAsync(c->Wm + p * 2 * (prows + 1), hdr[p], sizeof hdr[p], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->lres_esc = nesc;
+    if ((double)nesc <= 0.01 * (double)(nrows * 64)) c->lres = 1;
   }
   return 0;
 }

@@ -356,6 +356,13 @@ class Staggered:
         check(lib().qexhip_stag_links_info(self.ctx._h, C.byref(n), C.byref(cflag), C.byref(dev)))
         return n.value, cflag.value, dev.value
 
+    def links_storage(self):
+        """(bytes per link the sweep streams, links escaped by the last lossless encoding): 144 / 96 / 112 for formats 0 / 1 / 2,
+        108 for the lossless residual format (the 18-real operator bit for bit: links_info reports format 0)"""
+        nb, ne = C.c_int(0), C.c_longlong(0)
+        check(lib().qexhip_stag_links_storage(self.ctx._h, C.byref(nb), C.byref(ne)))
+        return nb.value, ne.value
+
     def D(self, r, x, m):
         check(lib().qexhip_stag_D(self.ctx._h, _p(r), _p(x), float(m), 1.0))
 
@@ -533,6 +540,20 @@ def newStag(ctx, g):
 
 def newStag3(ctx, g, g3):
     return Staggered(ctx, g, g3)
+
+
+def link_residual_host(links):
+    """The lossless link format's encoder + decoder on the host (no device needed).  links: complex or (..., 3, 3, 2) real array
+    of 3x3 matrices.  Returns (escaped: bool per link, row2: the decoded row 2 of every link, shape (n, 3, 2))."""
+    a = np.asarray(links)
+    if np.iscomplexobj(a):
+        a = np.stack([a.real, a.imag], axis=-1)
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 18)
+    n = a.shape[0]
+    esc = np.zeros(n, dtype=np.uint8)
+    row2 = np.zeros((n, 3, 2), dtype=np.float64)
+    check(lib().qexhip_link_residual_host(a.ctypes.data, n, esc.ctypes.data, row2.ctypes.data))
+    return esc.astype(bool), row2
 
 
 # ---- gauge observables / Wilson flow (src/gauge/gaugeUtils.nim:213-282, src/gauge/wflow.nim:21-67) ----
