@@ -34,6 +34,7 @@ DEFAULTS = dict(
     Nf=1, mass=0.1, num_pv=2, mass_pv=0.75, bc="aaaa",                       # :44,69-76
     alpha=(0.4, 0.5, 0.5), a_tol=1e-20, f_tol=1e-12, maxits=10000,           # :80-92
     seed=987654321, start="cold",
+    sloppy=0,                                                                 # SolverParams.sloppySolve of every solve (-sloppy)
 )
 
 
@@ -90,7 +91,7 @@ class Spv:
         self.s = q.Staggered(self.ctx, None, smear=self.hc, bc=self.prm["bc"])
 
     def _sp(self, tol):
-        return q.SolverParams(r2req=tol, maxits=self.prm["maxits"], verbosity=0)
+        return q.SolverParams(r2req=tol, maxits=self.prm["maxits"], verbosity=0, sloppySolve=self.prm["sloppy"])
 
     def _gsum(self, v):
         """rank sum of a host-side scalar (QEX: the threadRankSum at the end of norm2, commsUtils.nim:195-204)"""
@@ -241,6 +242,7 @@ def main():
     ap.add_argument("-halo", action="store_true", help="every kernel in its t-sharded form on one GPU")
     ap.add_argument("-time", action="store_true")
     ap.add_argument("-start", default="cold", help="cold, or the spread of a warm start (e.g. 0.3)")
+    ap.add_argument("-sloppy", type=int, default=0, help="SolverParams.sloppySolve of every solve: 0 fp64, 1 mixed precision")
     a = ap.parse_args()
     ranks = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -249,7 +251,7 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("gloo")
         ranks = (dist.get_world_size(), dist.get_rank(), dist)
-    hmc = Spv(a.lat, resident=not a.host_fields, halo=a.halo, start=a.start, ranks=ranks)
+    hmc = Spv(a.lat, resident=not a.host_fields, halo=a.halo, start=a.start, ranks=ranks, sloppy=a.sloppy)
     if hmc.rank != 0:
         sys.stdout = open(os.devnull, "w")            # one log, rank 0's (QEX: echo prints on rank 0)
     print(hmc.ctx.info(), "transport", hmc.ctx.comm_transport()[0])

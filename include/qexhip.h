@@ -223,10 +223,13 @@ int qexhip_stag_solve_prev(qexhip_handle h, double *x, const double *b, double m
  *   sloppy = 2 (SloppyHalf)   runs single: there is no half-precision format
  * The solve stops on the TRUE (fp64) residual: r2_over_b2 is |b - A x|^2/|b|^2 of the returned x (solveXX); iters counts fp32
  * iterations; nupdates (may be NULL) receives the number of reliable updates, the last one that confirmed convergence included
- * (0 for sloppy = 0).  iters == maxits is not an error.  One rank only: QEXHIP_ERR_ARG for sloppy > 0 on a communicator of
- * more than one rank, and for sloppy outside 0..2.  The fp32 copy of the links is built on first use and rebuilt whenever the
- * operator's links have changed since (any set_links variant, t-sharding by qexhip_comm_force_halo); qexhip_release_workspace
- * frees it. */
+ * (0 for sloppy = 0).  iters == maxits is not an error.  QEXHIP_ERR_ARG for sloppy outside 0..2.
+ * t-sharded contexts: each rank passes its slab, as with the fp64 entries, and the call is collective.  The fp32 faces travel on the
+ * context's transport (half the bytes of the fp64 ones), every reduction is rank-global, and every rank returns the same iters,
+ * r2 and nupdates; the sharded fp32 operator gives the one-rank operator's bits site for site.  The fp32 copy of the links is
+ * built on first use and rebuilt whenever the operator's links have changed since (any set_links variant, t-sharding by
+ * qexhip_comm_force_halo); its storage format is the one the whole lattice would get (largest deviation over the ranks);
+ * qexhip_release_workspace frees it. */
 int qexhip_stag_solve_xx_sloppy(qexhip_handle h, double *x, const double *b, double mass, double r2req, int maxits,
                                 int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates);
 int qexhip_stag_solve_sloppy(qexhip_handle h, double *x, const double *b, double mass, double r2req, int maxits,
@@ -274,10 +277,11 @@ int qexhip_dev_solve_xx(qexhip_handle h, int x_id, int b_id, double mass, double
 int qexhip_dev_solve_xx_sloppy(qexhip_handle h, int x_id, int b_id, double mass, double r2req, int maxits, int par_even,
                                int sloppy, int *iters, double *r2_over_b2, int *nupdates);
 /* the fp32 operator of the sloppy solve on resident fp64 fields: r[par] = f64(4 m2 x32 - (2D)(2D) x32), x32 = f32(x[par]), with
- * the fp32 links and the fp32 sweep the sloppy CG iterates with (one rank only) */
+ * the fp32 links and the fp32 sweep the sloppy CG iterates with; t-sharded: collective, on each rank's slab */
 int qexhip_dev_op_xx_sloppy(qexhip_handle h, int r_id, int x_id, double m2, int par_even);
 /* format of the fp32 link copy (building it if stale): 0 = 18 reals, 1 = rows 0,1 + sign (every link +-SU(3) to 1e-6); max_dev =
- * the largest deviation of a stored row 2 from the sign-format rebuild (0 when the sign format is capped off by "recon" = 0) */
+ * the largest deviation of a stored row 2 from the sign-format rebuild (0 when the sign format is capped off by "recon" = 0); t-sharded:
+ * the maximum over the ranks, and collective when the copy is rebuilt */
 int qexhip_stag_links_info_f32(qexhip_handle h, int *format, double *max_dev);
 /* Re-entry of the CG on the state the last qexhip_dev_solve_xx (or re-entry) on x_id left behind -- CgState.solve called
  * again with b2 >= 0 (src/solvers/cg.nim:21-27,85,133,155-161,256-261): no set-up, r / p / rzold kept, the stopping

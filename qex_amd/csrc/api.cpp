@@ -436,10 +436,6 @@ static int sloppy_check(qexhip_ctx *c, int sloppy) {
     qexhip_set_error("sloppy = %d: 0 (SloppyNone, fp64), 1 (SloppySingle) or 2 (SloppyHalf, runs single)", sloppy);
     return QEXHIP_ERR_ARG;
   }
-  if (sloppy > 0 && c->nranks > 1) {
-    qexhip_set_error("sloppy solves run on one rank only (communicator of %d ranks)", c->nranks);
-    return QEXHIP_ERR_ARG;
-  }
   return 0;
 }
 

@@ -244,47 +244,54 @@ static int emu_exchange(qexhip_ctx *c, hipStream_t st, size_t bytes) {
 static inline int upper(const qexhip_ctx *c) { return (c->rank + 1) % c->nranks; }
 static inline int lower(const qexhip_ctx *c) { return (c->rank - 1 + c->nranks) % c->nranks; }
 
-// Exchange the t-faces of one parity half of f.  Runs on the comm stream after ev_ready (the
-// producer of f on the compute stream); the caller joins (devjoin_signal / devjoin_wait) behind whatever it posts after the exchange.  Message order is the same on every
-// rank -- sends {bottom->lower, top->upper}, receives {ghost_hi<-upper, ghost_lo<-lower} -- so
-// that with two ranks (upper == lower) or one rank (self) the k-th send pairs with the k-th recv.
-int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready) {
+// Exchange the t-faces of one parity half of a field whose complex entries are `esz` bytes (16: DevField, 8: DevFieldF).  Runs on the
+// comm stream after ev_ready (the producer of the field on the compute stream); the caller joins (devjoin_signal / devjoin_wait) behind
+// whatever it posts after the exchange.  Message order is the same on every rank -- sends {bottom->lower, top->upper}, receives
+// {ghost_hi<-upper, ghost_lo<-lower} -- so that with two ranks (upper == lower) or one rank (self) the k-th send pairs with the k-th recv.
+static int halo_exchange(qexhip_ctx *c, char *base, size_t esz, int overlap, bool wait_ready) {
   // overlap == 0: post the exchange on the compute stream itself (no cross-stream events).  Used
   // when the interior sweep is too short to hide the exchange: two cross-stream dependencies
   // cost more than they buy there.
   CHK(need_comm(c));
   hipStream_t cs = overlap ? c->cstream : c->stream;
   const Geom &g = c->g;
-  const size_t face2 = (size_t)g.depth * g.F * 3;  // double2 per face
-  const size_t nd = face2 * 2;                     // doubles
-  double2 *base = f.par(parity);
-  double2 *bottom = base;                                       // t = 0 .. depth-1
-  double2 *top = base + (size_t)(g.ntile) * 192 - face2;        // t = Xt-depth .. Xt-1
-  double2 *ghost_hi = base + (size_t)g.ntile * 192;
-  double2 *ghost_lo = ghost_hi + face2;
+  const size_t bytes = (size_t)g.depth * g.F * 3 * esz;         // per face
+  const size_t nd = bytes / (esz / 2);                           // reals per face
+  const ncclDataType_t type = esz == 16 ? ncclDouble : ncclFloat;
+  char *bottom = base;                                           // t = 0 .. depth-1
+  char *top = base + (size_t)g.ntile * 192 * esz - bytes;        // t = Xt-depth .. Xt-1
+  char *ghost_hi = base + (size_t)g.ntile * 192 * esz;
+  char *ghost_lo = ghost_hi + bytes;
   if (overlap && wait_ready) HIPCHK(hipStreamWaitEvent(c->cstream, c->ev_ready, 0));     // (not when the comm stream produced the faces itself)
   ScopedTimer tm(c, "exchange", cs);            // on the stream the group is posted on: transport + waiting for the neighbours
-  CHK(emu_exchange(c, cs, nd * sizeof(double)));
+  CHK(emu_exchange(c, cs, bytes));
   if (peer_faces(c)) {
     const void *dn = bottom, *up = top;
     void *from_up = ghost_hi, *from_dn = ghost_lo;
-    CHK(peer_exchange(c, cs, 1, &dn, 1, &up, &from_up, &from_dn, nd * sizeof(double), emu_exchange_time(c, nd * sizeof(double))));
+    CHK(peer_exchange(c, cs, 1, &dn, 1, &up, &from_up, &from_dn, bytes, emu_exchange_time(c, bytes)));
   } else if (c->comm) {
     // the overlapped exchange has the second communicator to itself (comm_init)
     ncclComm_t comm = (ncclComm_t)((overlap && c->comm2) ? c->comm2 : c->comm);
     NCCLCHK(ncclGroupStart());
-    NCCLCHK(ncclSend(bottom, nd, ncclDouble, lower(c), comm, cs));
-    NCCLCHK(ncclSend(top, nd, ncclDouble, upper(c), comm, cs));
-    NCCLCHK(ncclRecv(ghost_hi, nd, ncclDouble, upper(c), comm, cs));
-    NCCLCHK(ncclRecv(ghost_lo, nd, ncclDouble, lower(c), comm, cs));
+    NCCLCHK(ncclSend(bottom, nd, type, lower(c), comm, cs));
+    NCCLCHK(ncclSend(top, nd, type, upper(c), comm, cs));
+    NCCLCHK(ncclRecv(ghost_hi, nd, type, upper(c), comm, cs));
+    NCCLCHK(ncclRecv(ghost_lo, nd, type, lower(c), comm, cs));
     NCCLCHK(ncclGroupEnd());
   } else {
     // single rank, no communicator: periodic wrap by device-to-device copies
-    HIPCHK(hipMemcpyAsync(ghost_hi, bottom, nd * sizeof(double), hipMemcpyDeviceToDevice, cs));
-    HIPCHK(hipMemcpyAsync(ghost_lo, top, nd * sizeof(double), hipMemcpyDeviceToDevice, cs));
+    HIPCHK(hipMemcpyAsync(ghost_hi, bottom, bytes, hipMemcpyDeviceToDevice, cs));
+    HIPCHK(hipMemcpyAsync(ghost_lo, top, bytes, hipMemcpyDeviceToDevice, cs));
   }
   // overlap: the caller (dslash_sweep) posts its boundary launch behind the group on cstream and the join signal after it
   return 0;
+}
+int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready) {
+  return halo_exchange(c, (char *)f.par(parity), sizeof(double2), overlap, wait_ready);
+}
+// the fp32 fields of the mixed-precision CG (dslash_f32.hip): the same messages in the same order, half the bytes
+int comm_halo_exchange_f32(qexhip_ctx *c, DevFieldF &f, int parity, int overlap) {
+  return halo_exchange(c, (char *)f.par(parity), sizeof(float2), overlap, true);
 }
 
 // Peer transport, the fused sweeps: the faces of one parity half of n fields (fused_sweep_setup: n = 1 for dslash_sweep, up to 4 for the lock-step batch) will be

@@ -1,6 +1,7 @@
 // dslash_f32.hip -- the single-precision side of the mixed-precision CG (SolverParams.sloppySolve, solverBase.nim:8-15):
 // an fp32 copy of the operator's links, the fp32 Dslash sweep, and the fp32 BLAS / bookkeeping kernels of the reliable-update
-// CG whose host control is solve_xx_sloppy_dev (solver.cpp).  One rank only (no ghost zones, no fused form).
+// CG whose host control is solve_xx_sloppy_dev (solver.cpp).  Whole lattice on one GPU, or a t-sharded slab with ghost zones (the
+// fp64 DevField's layout) filled by the fp32 face exchange (comm_halo_exchange_f32); no fused (self-pushing) form.
 //
 // Links: built on the device from the resident fp64 links (c->W: BCs, staggered phases and Naik links already applied), lazily,
 // whenever c->links_gen has moved since the last build (every writer of W ends in links_compress, which bumps it).  Per parity
@@ -10,7 +11,8 @@
 //   format 1 (NL = 6, 48 B/link + 1 bit): rows 0,1 and a sign mask [tile][dir] (bit = lane); row 2 = +-conj(row0 x row1) is
 //             rebuilt in registers.  Chosen when every link satisfies that to F32_UNIT_TOL (a few fp32 ulps), and unless
 //             QEXHIP_RECON / option "recon" is 0.
-// Fields: float2 v[tile][3][64] per parity, the fp64 field's site and tile order (vec_off), no ghost tiles.
+// Fields: float2 v[tile][3][64] per parity, the fp64 field's site and tile order (vec_off); with g.halo the ghost tiles follow the
+// body as in DevField (ghost_hi, then ghost_lo, room for depth 3 each), without it the body alone.
 // Every reduction (<p,Ap>, |r|^2) accumulates in double, as QEX does for fp32 fields (fieldET.nim:609,708).
 #include "qexhip_internal.h"
 #include "site_index.h"
@@ -139,7 +141,17 @@ int f32_links(qexhip_ctx *c, int *fmt_out, double *dev_out) {
       float d;
       memcpy(&d, &bits, sizeof(d));
       dev = d;
-      if (dev <= F32_UNIT_TOL) fmt = 1;
+    }
+    if (c->nranks > 1 && comm_ready(c)) {
+      // t-sharded: the largest deviation over the ranks decides, so that every slab is stored in the format the whole lattice would
+      // be (and the sharded operator gives the one-rank operator's bits); a rank with the sign format switched off rules it out
+      // everywhere.  Collective: every rank rebuilds its copy at the same point, behind the same (collective) writer of the links.
+      double v[1] = {c->opt_recon ? dev : 1e300};
+      CHK(comm_allreduce_max(c, v, 1));
+      if (c->opt_recon) dev = v[0];
+      if (v[0] <= F32_UNIT_TOL) fmt = 1;
+    } else if (c->opt_recon && dev <= F32_UNIT_TOL) {
+      fmt = 1;
     }
     if (fmt == 0) {
       k_links_f32<0><<<nblk, 256, 0, c->stream>>>(nrows, c->W, S->W, nullptr, nullptr);
@@ -152,11 +164,19 @@ int f32_links(qexhip_ctx *c, int *fmt_out, double *dev_out) {
   return 0;
 }
 
+// etile = ntile without a halo: the ghost zones cost nothing on a one-rank context that has none.  A field allocated before the
+// geometry changed (qexhip_comm_force_halo) is allocated again.
 int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {
   F32State *S = st_of(c);
   DevFieldF &F = S->f[slot];
+  const size_t half = (size_t)c->g.etile * 192;
+  if (F.d && F.half != half) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipFree(F.d));
+    F.d = nullptr;
+  }
   if (!F.d) {
-    F.half = body2(c);
+    F.half = half;
     HIPCHK(hipMalloc((void **)&F.d, 2 * F.half * sizeof(float2)));
     HIPCHK(hipMemsetAsync(F.d, 0, 2 * F.half * sizeof(float2), c->stream));   // padding lanes stay zero
   }
@@ -165,8 +185,13 @@ int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {
 }
 
 // ---- fp32 Dslash sweep --------------------------------------------------------------------------------------------
-// out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)])  (k_dslash's arithmetic with ca = 0, post = 1), whole lattice on one
-// GPU: one lane per site, 64-site tiles, links streamed non-temporally with 16-byte loads, fp32 FMAs, <xs,out> partials in double.
+// out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)])  (k_dslash's arithmetic with ca = 0, post = 1): one lane per site, 64-site
+// tiles, links streamed non-temporally with 16-byte loads, fp32 FMAs, <xs,out> partials in double.
+//   HALO = false  the whole lattice on one GPU (t-hops wrap)
+//   HALO = true   a t-sharded slab (or a one-rank context with a halo): t-hops that leave the slab read the ghost zones (nbr_pos<true>),
+//                 over the site range [c0,c1) plus [d0,d1) for workgroups >= nb1 (both faces in one launch), as k_dslash<.., HALO, ..>.
+//                 Every site runs the operations of the HALO = false kernel in the same order -- only the positions its t-hops read
+//                 differ --, so a sharded fp32 operator gives the one-rank operator's bits site for site.
 struct DslashF32Args {
   Geom g;
   const f4v *W;                    // links of the output parity
@@ -179,13 +204,28 @@ struct DslashF32Args {
   double *partials;
   const int *done;
 };
+struct DslashF32HaloArgs {         // (a type of its own: the HALO = false kernels keep their kernel arguments and code)
+  DslashF32Args a;
+  int c0, c1, d0, d1, nb1;
+};
+template <bool HALO> struct F32SweepArgs { using T = DslashF32Args; };
+template <> struct F32SweepArgs<true> { using T = DslashF32HaloArgs; };
+__device__ __forceinline__ const DslashF32Args &f32_args(const DslashF32Args &P) { return P; }
+__device__ __forceinline__ const DslashF32Args &f32_args(const DslashF32HaloArgs &P) { return P.a; }
 
-template <int NDIR, bool INIT, bool DOT, int RECON>
-__global__ void __launch_bounds__(256) k_dslash_f32(DslashF32Args A) {
+template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON>
+__global__ void __launch_bounds__(256) k_dslash_f32(typename F32SweepArgs<HALO>::T P) {
+  const DslashF32Args &A = f32_args(P);
   if (A.done && *A.done) return;
   const Geom &g = A.g;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  const bool active = c < g.Vh;
+  int c = blockIdx.x * 256 + threadIdx.x;
+  bool active = c < g.Vh;
+  if constexpr (HALO) {
+    int clim = P.c1;
+    if ((int)blockIdx.x < P.nb1) c = P.c0 + blockIdx.x * 256 + threadIdx.x;
+    else { c = P.d0 + (blockIdx.x - P.nb1) * 256 + threadIdx.x; clim = P.d1; }
+    active = c < clim;
+  }
   double dotv = 0;
   if (active) {
     const SiteXYZT s = site_coord(g, c, A.parity);
@@ -204,8 +244,8 @@ __global__ void __launch_bounds__(256) k_dslash_f32(DslashF32Args A) {
     for (int pr = 0; pr < NDIR / 2; pr++) {
       const int mu = pr & 3;
       const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<false>(g, c, s, mu, hop);
-      const int pb = nbr_pos<false>(g, c, s, mu, -hop);
+      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
+      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
       f4v t[NL];
 #pragma unroll
       for (int q = 0; q < NL; q++) t[q] = __builtin_nontemporal_load(&w[(size_t)(pr * NL + q) * 64]);
@@ -238,8 +278,40 @@ __global__ void __launch_bounds__(256) k_dslash_f32(DslashF32Args A) {
   }
 }
 
-static int sweep_f32(qexhip_ctx *c, DevFieldF &out, const DevFieldF &in, int parity, const DevFieldF *xs, double cb, bool neg,
-                     bool dot, const int *done) {
+// one launch of the halo kernel over [c0,c1) (+ [d0,d1) behind it) on stream st, dot partials from A.partials + part_off
+static int launch_f32_halo(qexhip_ctx *c, int fmt, const DslashF32Args &A, int c0, int c1, int d0, int d1, bool init, bool dot,
+                           int part_off, const char *tname, hipStream_t st) {
+  if (c1 <= c0 && d1 <= d0) return 0;
+  if (c1 <= c0) { c0 = d0; c1 = d1; d0 = d1 = 0; }
+  DslashF32HaloArgs P;
+  memset(&P, 0, sizeof P);
+  P.a = A;
+  P.a.partials = A.partials + part_off;
+  P.c0 = c0; P.c1 = c1; P.d0 = d0; P.d1 = d1;
+  P.nb1 = (c1 - c0 + 255) / 256;
+  const dim3 grid(P.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0)), block(256);
+  ScopedTimer tm(c, tname, st);
+#define QX_F32H(ND, R)                                                                                       \
+  do {                                                                                                       \
+    if (init && dot) hipLaunchKernelGGL((k_dslash_f32<ND, true, true, true, R>), grid, block, 0, st, P);    \
+    else if (init) hipLaunchKernelGGL((k_dslash_f32<ND, true, true, false, R>), grid, block, 0, st, P);     \
+    else if (dot) hipLaunchKernelGGL((k_dslash_f32<ND, true, false, true, R>), grid, block, 0, st, P);      \
+    else hipLaunchKernelGGL((k_dslash_f32<ND, true, false, false, R>), grid, block, 0, st, P);              \
+  } while (0)
+  if (c->ndir == 8) { if (fmt == 1) QX_F32H(8, 1); else QX_F32H(8, 0); }
+  else { if (fmt == 1) QX_F32H(16, 1); else QX_F32H(16, 0); }
+#undef QX_F32H
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// One fp32 sweep; *nparts <- how many <xs,out> partials it left in c->partials.  With g.halo, in the forms the fp64 sweep chooses
+// between (sweep_plan / sweep_form): exchange-first (the fp32 faces on the compute stream, one launch over all sites) or split by
+// sites (exchange + both faces' launch on the comm stream, interior launch on the compute stream, device-side join).  The fused form
+// has no fp32 kernel: where sweep_form picks it, the fp32 sweep is split by sites.  dot: the caller's next operation on the compute
+// stream is comm_allreduce_parts (slp_update), which takes the join of a split sweep with it where the mailboxes carry the sum.
+static int sweep_f32(qexhip_ctx *c, DevFieldF &out, DevFieldF &in, int parity, const DevFieldF *xs, double cb, bool neg,
+                     bool dot, const int *done, int *nparts) {
   F32State *S = st_of(c);
   const Geom &g = c->g;
   const int NL = S->fmt == 1 ? 6 : 9;
@@ -257,19 +329,43 @@ static int sweep_f32(qexhip_ctx *c, DevFieldF &out, const DevFieldF &in, int par
   A.partials = c->partials;
   A.done = done;
   const bool init = cb != 0.0;
+  c->bnd_out_on_cstream = nullptr;        // (the fp64 sweep's early-exchange shortcut is for a pair of fp64 sweeps only)
+  if (g.halo) {
+    int lo_end, hi_beg, overlap;
+    sweep_plan(c, &lo_end, &hi_beg, &overlap);
+    CHK(devjoin_flush(c));
+    if (!overlap) {
+      CHK(comm_halo_exchange_f32(c, in, 1 - parity, 0));
+      CHK(launch_f32_halo(c, S->fmt, A, 0, g.Vh, 0, 0, init, dot, 0, "dslash_f32", c->stream));
+      *nparts = (g.Vh + 255) / 256;
+    } else {
+      // split by sites (also where sweep_form(c, overlap) == 2: no fused fp32 sweep yet)
+      const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
+      HIPCHK(hipEventRecord(c->ev_ready, c->stream));
+      CHK(comm_halo_exchange_f32(c, in, 1 - parity, 1));
+      CHK(launch_f32_halo(c, S->fmt, A, lo_end, hi_beg, 0, 0, init, dot, 0, "dslash_f32", c->stream));
+      CHK(launch_f32_halo(c, S->fmt, A, 0, lo_end, hi_beg, g.Vh, init, dot, nb_int, "dslash_f32_bnd", c->cstream));
+      CHK(devjoin_signal(c, c->cstream));
+      if (dot && c->peer) CHK(devjoin_defer(c));
+      else CHK(devjoin_wait(c, c->stream, c->cstream));
+      *nparts = nb_int + nb_lo + nb_hi;
+    }
+    return 0;
+  }
   const dim3 grid((g.Vh + 255) / 256), block(256);
   ScopedTimer tm(c, "dslash_f32", c->stream);
-#define QX_F32(ND, R)                                                                          \
-  do {                                                                                         \
-    if (init && dot) hipLaunchKernelGGL((k_dslash_f32<ND, true, true, R>), grid, block, 0, c->stream, A);   \
-    else if (init) hipLaunchKernelGGL((k_dslash_f32<ND, true, false, R>), grid, block, 0, c->stream, A);    \
-    else if (dot) hipLaunchKernelGGL((k_dslash_f32<ND, false, true, R>), grid, block, 0, c->stream, A);     \
-    else hipLaunchKernelGGL((k_dslash_f32<ND, false, false, R>), grid, block, 0, c->stream, A);             \
+#define QX_F32(ND, R)                                                                                  \
+  do {                                                                                                 \
+    if (init && dot) hipLaunchKernelGGL((k_dslash_f32<ND, false, true, true, R>), grid, block, 0, c->stream, A);   \
+    else if (init) hipLaunchKernelGGL((k_dslash_f32<ND, false, true, false, R>), grid, block, 0, c->stream, A);    \
+    else if (dot) hipLaunchKernelGGL((k_dslash_f32<ND, false, false, true, R>), grid, block, 0, c->stream, A);     \
+    else hipLaunchKernelGGL((k_dslash_f32<ND, false, false, false, R>), grid, block, 0, c->stream, A);             \
   } while (0)
   if (c->ndir == 8) { if (S->fmt == 1) QX_F32(8, 1); else QX_F32(8, 0); }
   else { if (S->fmt == 1) QX_F32(16, 1); else QX_F32(16, 0); }
 #undef QX_F32
   HIPCHK(hipGetLastError());
+  *nparts = (g.Vh + 255) / 256;
   return 0;
 }
 
@@ -279,9 +375,10 @@ int f32_op_xx(qexhip_ctx *c, DevFieldF &r, DevFieldF &x, double m2, int par_even
   DevFieldF *t;
   CHK(f32_field(c, F32_T, &t));
   const int px = par_even ? 0 : 1, py = 1 - px;
-  CHK(sweep_f32(c, *t, x, py, nullptr, 0.0, false, false, done));
-  CHK(sweep_f32(c, r, *t, px, &x, 4.0 * m2, true, dot != 0, done));
-  if (nparts) *nparts = (c->g.Vh + 255) / 256;
+  int np = 0;
+  CHK(sweep_f32(c, *t, x, py, nullptr, 0.0, false, false, done, &np));
+  CHK(sweep_f32(c, r, *t, px, &x, 4.0 * m2, true, dot != 0, done, &np));
+  if (nparts) *nparts = np;
   return 0;
 }
 
@@ -457,12 +554,23 @@ int slp_xpay(qexhip_ctx *c, SlpScal *s, DevFieldF &p, DevFieldF &rs, const DevFi
   HIPCHK(hipGetLastError());
   return 0;
 }
+// Sharded, every set of partials these kernels sum -- <p,Ap> and |r_s|^2 here, |b - A x|^2 in slp_resid (|b|^2: blas_norm2) -- is first
+// summed over the ranks (comm_allreduce_parts, as the fp64 CG does in cg_update), so that k_slp_close / k_slp_rclose see the same
+// rank-global values on every rank.  INVARIANT: every rank then sets the same `upd` / `done` flags at the same iteration and takes the
+// same reliable updates and the same stop; the host posts the same exchanges and all-reduces everywhere, and solve_xx_sloppy_dev checks
+// the agreement at the end of every chunk -- a rank that left the loop or skipped an update its neighbour took would leave the
+// neighbour's next exchange without a partner.  (One rank: comm_allreduce_parts changes nothing, the bits are the one-rank solve's.)
 int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const DevFieldF &p, const DevFieldF &Ap, int parity, int ndot) {
   const size_t n = body2(c);
   const int nb = grid_for(n);
-  k_slp_update<<<nb, 256, 0, c->stream>>>(xs.par(parity), rs.par(parity), p.par(parity), Ap.par(parity), n, s, c->partials, ndot,
-                                          c->partials + c->part2_off);
-  k_slp_close<<<1, 256, 0, c->stream>>>(s, c->partials + c->part2_off, nb, SLP_DELTA * SLP_DELTA);
+  double *r2p = c->partials + c->part2_off;
+  if (ndot > 0) CHK(comm_allreduce_parts(c, c->partials, ndot, &ndot));
+  CHK(devjoin_flush(c));              // (no-op when the all-reduce has taken the second sweep's join with it)
+  k_slp_update<<<nb, 256, 0, c->stream>>>(xs.par(parity), rs.par(parity), p.par(parity), Ap.par(parity), n, s, c->partials, ndot, r2p);
+  HIPCHK(hipGetLastError());
+  int nr2 = nb;
+  CHK(comm_allreduce_parts(c, r2p, nb, &nr2));
+  k_slp_close<<<1, 256, 0, c->stream>>>(s, r2p, nr2, SLP_DELTA * SLP_DELTA);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -475,8 +583,12 @@ int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity)
 int slp_resid(qexhip_ctx *c, SlpScal *s, DevField &r, const DevField &b, const DevField &Ax, int parity) {
   const size_t n = body2(c);
   const int nb = grid_for(n);
-  k_slp_resid<<<nb, 256, 0, c->stream>>>(r.par(parity), b.par(parity), Ax.par(parity), n, s, c->partials + c->part2_off);
-  k_slp_rclose<<<1, 256, 0, c->stream>>>(s, c->partials + c->part2_off, nb);
+  double *r2p = c->partials + c->part2_off;
+  k_slp_resid<<<nb, 256, 0, c->stream>>>(r.par(parity), b.par(parity), Ax.par(parity), n, s, r2p);
+  HIPCHK(hipGetLastError());
+  int nr2 = nb;
+  CHK(comm_allreduce_parts(c, r2p, nb, &nr2));      // (posted whether or not an update is due: the ranks post the same collectives)
+  k_slp_rclose<<<1, 256, 0, c->stream>>>(s, r2p, nr2);
   HIPCHK(hipGetLastError());
   return 0;
 }

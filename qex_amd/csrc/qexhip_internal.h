@@ -46,9 +46,9 @@ struct DevField {  // full-volume colour vector: parity halves, each with its gh
   double2 *par(int p) const { return d + (size_t)p * half; }
 };
 
-struct DevFieldF {  // fp32 colour vector of the mixed-precision CG: float2 v[tile][3][64] per parity (vec_off), no ghost tiles
+struct DevFieldF {  // fp32 colour vector of the mixed-precision CG: float2 v[tile][3][64] per parity (vec_off), ghost tiles as DevField's
   float2 *d = nullptr;
-  size_t half = 0;  // float2 elements per parity half (= ntile*192)
+  size_t half = 0;  // float2 elements per parity half (= etile*192: ntile*192 without a halo)
   float2 *par(int p) const { return d + (size_t)p * half; }
 };
 
@@ -260,6 +260,7 @@ int comm_halo_push_only_multi(qexhip_ctx *c, int n, DevField *const *f, int pari
                                                                               // and reads what arrives in the receive arena
 int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready = true);  // overlap: on cstream after ev_ready (wait_ready);
                                                                               // the caller joins behind what it posts next
+int comm_halo_exchange_f32(qexhip_ctx *c, DevFieldF &f, int parity, int overlap);  // the same for an fp32 field (half the bytes)
 int comm_halo_exchange_multi(qexhip_ctx *c, int n, DevField *const *f, int parity, int overlap);   // n fields, one RCCL group
 int comm_allreduce(qexhip_ctx *c, double *dptr, int n);          // on stream
 int comm_allreduce_parts(qexhip_ctx *c, double *parts, int n, int *n_out);   // workgroup partials -> *n_out values whose sum is the rank-global dot product
@@ -322,7 +323,7 @@ void sweep_plan(const qexhip_ctx *c, int *lo_end, int *hi_beg, int *overlap);   
 int sweep_form(const qexhip_ctx *c, int overlap);                              // 2 fused / 0 by sites: what an overlapped sweep runs as
 double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs = 1);   // where in the dispatch order the fused sweep's boundary workgroups go
 
-// ---- dslash_f32.hip (mixed-precision CG, one rank) ----
+// ---- dslash_f32.hip (mixed-precision CG; whole lattice or t-sharded slab) ----
 enum { F32_T = 0, F32_R, F32_P, F32_AP, F32_X, F32_IN, F32_NF };   // fp32 work fields
 #define SLP_DELTA 0.1                                    // reliable-update delta (QEX's reliable_delta, qudaSet.nim:63)
 int f32_links(qexhip_ctx *c, int *fmt, double *dev);     // the fp32 copy of the links, rebuilt when links_gen moved

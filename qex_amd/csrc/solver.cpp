@@ -9,6 +9,7 @@
 // All vectors stay in HBM; the CG scalars stay on the device (CgScal) and the host only reads
 // the state back once per chunk of iterations.
 #include "qexhip_internal.h"
+#include "../../include/qexhip.h"
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -189,6 +190,24 @@ int solve_xx_continue_dev(qexhip_ctx *c, DevField &x, double r2req, int maxits, 
 // opt_sloppy_check-th iteration (default 4; always at maxits), so an update waits up to 3 iterations: posted every iteration, the
 // gated no-ops (each sweep still dispatches its whole grid, ~4.6 us) cost 7 % of an fp32 iteration at 32^4 -- measured on MI355X,
 // 137.9 vs 130.9 us per iteration for every 1st / 4th iteration, 222 vs 224 iterations.
+// Sharded: the state every rank just read back decides whether its host posts another chunk, so the ranks must hold the same bits
+// (slp_update: the reductions are rank-global, and so are the flags computed from them).  Checked here, with host operands, before
+// any rank acts on its copy: {r2t, -r2t, key, -key} max-reduced, max and min must coincide.
+static int slp_agree(qexhip_ctx *c, const SlpScal &h) {
+  if (c->nranks < 2 || !comm_ready(c)) return 0;
+  CHK(peer_check(c));
+  const double key = ((double)h.k * 2.0 + h.done) * 65536.0 + (h.nupd & 0xffff);      // (exact in a double)
+  double v[4] = {h.r2t, -h.r2t, key, -key};
+  CHK(comm_allreduce_max(c, v, 4));
+  const bool both_nan = std::isnan(v[0]) && std::isnan(v[1]);
+  if ((!both_nan && v[0] != -v[1]) || v[2] != -v[3]) {
+    qexhip_set_error("sharded sloppy solve: the ranks disagree on the true residual (%.17g .. %.17g) or on iterations / updates / stop "
+                     "(key %g .. %g)", -v[1], v[0], -v[3], v[2]);
+    return QEXHIP_ERR_COMM;
+  }
+  return 0;
+}
+
 int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                         int *iters, double *r2_over_b2, int *nupdates) {
   const int par = par_even ? 0 : 1;
@@ -233,6 +252,7 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
     HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(&h, c->pinned, sizeof(SlpScal));
+    CHK(slp_agree(c, h));
   }
   if (iters) *iters = h.k;
   if (r2_over_b2) *r2_over_b2 = (h.b2 != 0.0) ? h.r2t / h.b2 : 0.0;
