@@ -2,14 +2,15 @@
 """src/observables/fpvaMeas.nim through libqexhip: local and one-link (symmetric spatial shift) staggered meson correlators
 from point-source propagators.
 
-    python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5]
+    python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5] [-sloppy 0]
     python -m torch.distributed.run --nproc-per-node N examples/stag_mesons.py ...     # t-sharded over N ranks
 
 For each colour the point source at (0,0,0,t0) and its three symmetric one-link shifts are solved in one lock-step batch of four
 (qexhip_dev_solve_batch), the shifted propagators are shifted back at the sink, and the four tables are contracted on the device;
 no propagator leaves the GPU.  The tables are printed as printLocalMesons prints them: Walsh-Hadamard transform over the corner
 bits, normalisation nt / physVol.  The configuration is the library's RngMilc6 warm start (as examples/stag_prop.py), seeded by
-global site, so every partition sees the same gauge field."""
+global site, so every partition sees the same gauge field.  -sloppy 1 runs the batches in mixed precision (fp32 iterations with
+fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only."""
 import argparse
 import os
 import sys
@@ -27,7 +28,11 @@ ap.add_argument("-t0", type=int, default=2)
 ap.add_argument("-seed", type=int, default=987654321)
 ap.add_argument("-warm", type=float, default=0.5)
 ap.add_argument("-r2req", type=float, default=1e-16)
+ap.add_argument("-sloppy", type=int, default=0, choices=[0, 1, 2])
 a = ap.parse_args()
+if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    sys.exit("stag_mesons.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
+             "lattices (run without -sloppy, or on one rank)" % a.sloppy)
 
 world, rank, dist = 1, 0, None
 if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -57,10 +62,17 @@ g = rng.warm(a.warm)                                              # g.warm
 q.rephase(lo, g, t_offset=rank * lt, t_global=glat[3])            # g.setBC; g.stagPhase
 s = q.newStag(ctx, g)
 print("links per site, storage format, max deviation:", s.links_info())
+if a.sloppy:
+    print("mixed-precision batches: fp32 link format, max deviation:", ctx.links_info_f32())
 t = time.perf_counter()
-cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt)
+if a.sloppy:
+    cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt, sloppy=a.sloppy)
+else:
+    cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt)
 total = time.perf_counter() - t
 print("solves: %.4f s (iterations per colour [local, x, y, z]: %s)" % (st["solve_s"], st["iterations"]))
+if a.sloppy:
+    print("reliable updates per colour [local, x, y, z]: %s" % (st["updates"],))
 print("contractions: %.6f s (%.3f %% of the measurement, %.4f s)" % (st["contract_s"], 100.0 * st["contract_s"] / total, total))
 f = glat[3] / float(np.prod(glat))                                # nt / physVol
 q.printLocalMesons(cl, f)

@@ -312,6 +312,9 @@ int qexhip_dev_zero(qexhip_handle h, int id, int parity);
  * operator's current links: faction / pbp of the HMC drivers without moving a vector (staghmc_sh.nim:260-272,339-364) */
 int qexhip_dev_solve_batch(qexhip_handle h, int n, const int *x_ids, const int *b_ids, const double *mass,
                            const double *r2req, int maxits, int *iters, double *r2);
+/* qexhip_stag_solve_batch_sloppy (below) on resident fields: ONE lock-step batch, n in 1..4 */
+int qexhip_dev_solve_batch_sloppy(qexhip_handle h, int n, const int *x_ids, const int *b_ids, const double *mass,
+                                  const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);
 
 /* ---------------- meson correlators on resident fields ----------------
  * Local staggered mesons from point-source propagators (src/observables/fpvaMeas.nim, tests/examples/testStagProp.nim).
@@ -421,6 +424,20 @@ int qexhip_stag_solve_xx_batch(qexhip_handle h, int n, double *const *x, const d
                                const double *r2req, int maxits, int par_even, int *iters, double *r2_over_b2);
 int qexhip_stag_solve_batch(qexhip_handle h, int n, double *const *x, const double *const *b, const double *mass,
                             const double *r2req, int maxits, int *iters, double *r2_over_b2);
+
+/* The lock-step batch in mixed precision (sloppy as in qexhip_stag_solve_xx_sloppy): the fp32 iterations of all n (1..4) systems
+ * share ONE sweep over the fp32 link copy; every system keeps its own reliable-update state, takes its fp64 true-residual updates
+ * on its own, and stops on its own TRUE residual.  Per system the arithmetic is that of the single-system sloppy call on that
+ * system, so x, iters (fp32 iterations), the residual and nupdates are bit for bit what qexhip_stag_solve_xx_sloppy /
+ * qexhip_stag_solve_sloppy return for it alone; maxits is shared, as in the fp64 batch.  iters, r2_* and nupdates (may be NULL) are
+ * arrays of n.  sloppy = 0 is qexhip_stag_solve_xx_batch / qexhip_stag_solve_batch itself (nupdates 0).
+ * QEXHIP_ERR_ARG for sloppy outside 0..2, n outside 1..4, mass 0 (with sloppy > 0), and -- with sloppy > 0 -- for t-sharded
+ * contexts (more than one rank, or qexhip_comm_force_halo): the batched fp32 face exchange is not built; nothing is launched. */
+int qexhip_stag_solve_xx_batch_sloppy(qexhip_handle h, int n, double *const *x, const double *const *b, const double *mass,
+                                      const double *r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2,
+                                      int *nupdates);
+int qexhip_stag_solve_batch_sloppy(qexhip_handle h, int n, double *const *x, const double *const *b, const double *mass,
+                                   const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);
 
 /* Storage format the library chose for the operator's links at the last set_links call.  A unitary link is fixed
  * by rows 0,1 and its determinant (row2 = det * conj(row0 x row1)), and the sweep is HBM-bound, so:

@@ -195,20 +195,27 @@ class Staggered {
     solve(x, b, m, sp);
   }
   // n <= 4 independent solves on these links in lock-step (one stream of the links per sweep for all of them);
-  // per system the result of solve(x[j], b[j], m[j], sps[j])
-  void solveBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms, std::vector<SolverParams> &sps) {
+  // per system the result of solve(x[j], b[j], m[j], sps[j]).  sloppy = -1: fp64, and a sloppy SolverParams is refused (as before);
+  // 0, 1, 2: the precision of the batch, chosen explicitly (qexhip_stag_solve_batch_sloppy; one rank only when > 0), overriding
+  // sps[j].sloppySolve; sps[j].reliableUpdates gets system j's updates
+  void solveBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms, std::vector<SolverParams> &sps,
+                  int sloppy = -1) {
     const int n = (int)xs.size();
-    for (auto &sp : sps) if (sp.sloppySolve) throw std::invalid_argument("sloppySolve: single-system solves only");
-    std::vector<double *> xp; std::vector<const double *> bp; std::vector<double> rq, fin(n); std::vector<int> its(n);
+    if (sloppy < -1 || sloppy > 2) throw std::invalid_argument("solveBatch: sloppy = -1 (unset), 0, 1 or 2");
+    if (sloppy < 0)
+      for (auto &sp : sps)
+        if (sp.sloppySolve) throw std::invalid_argument("sloppySolve: single-system solves only (pass sloppy = 1 to solveBatch for the mixed-precision batch)");
+    std::vector<double *> xp; std::vector<const double *> bp; std::vector<double> rq, fin(n); std::vector<int> its(n), nup(n);
     int maxits = sps.at(0).maxits;
     for (int j = 0; j < n; j++) { xp.push_back(xs[j].data()); bp.push_back(bs.at(j).data()); rq.push_back(sps.at(j).r2req); maxits = std::min(maxits, sps[j].maxits); }
     auto t0 = std::chrono::steady_clock::now();
-    check(qexhip_stag_solve_batch(c_.h, n, xp.data(), bp.data(), ms.data(), rq.data(), maxits, its.data(), fin.data()));
+    if (sloppy < 0) check(qexhip_stag_solve_batch(c_.h, n, xp.data(), bp.data(), ms.data(), rq.data(), maxits, its.data(), fin.data()));
+    else check(qexhip_stag_solve_batch_sloppy(c_.h, n, xp.data(), bp.data(), ms.data(), rq.data(), maxits, sloppy, its.data(), fin.data(), nup.data()));
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / n;
     for (int j = 0; j < n; j++) {
       SolverParams &sp = sps[j];
       sp.seconds += dt; sp.calls += 1; sp.iterations += its[j]; sp.iterationsMax = std::max(sp.iterationsMax, its[j]);
-      sp.flops += flops(its[j]); sp.r2 = fin[j];
+      sp.flops += flops(its[j]); sp.r2 = fin[j]; sp.reliableUpdates += nup[j];
     }
   }
   // multi-mass Staggered.solve(xs, b, ms, sp) (stagSolve.nim:347-446)

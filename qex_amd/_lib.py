@@ -88,6 +88,8 @@ SYMBOLS = [
     ("qexhip_nhyp_smear", _ci, [_vp, _vp, _vp, _cd, _cd, _cd]),
     ("qexhip_stag_solve_xx_batch", _ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _pi, _vp]),
     ("qexhip_stag_solve_batch", _ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _pi, _vp]),
+    ("qexhip_stag_solve_xx_batch_sloppy", _ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _pi, _vp, _pi]),
+    ("qexhip_stag_solve_batch_sloppy", _ci, [_vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _pi, _vp, _pi]),
     ("qexhip_stag_links_info", _ci, [_vp, _pi, _pi, _vp]),
     ("qexhip_stag_links_storage", _ci, [_vp, _pi, C.POINTER(C.c_longlong)]),
     ("qexhip_link_residual_host", _ci, [_vp, _ci, _vp, _vp]),
@@ -125,6 +127,7 @@ SYMBOLS = [
     ("qexhip_md_refresh_momenta", _ci, [_vp, _vp]),
     ("qexhip_dev_zero", _ci, [_vp, _ci, _ci]),
     ("qexhip_dev_solve_batch", _ci, [_vp, _ci, _pi, _pi, _pd, _pd, _ci, _pi, _pd]),
+    ("qexhip_dev_solve_batch_sloppy", _ci, [_vp, _ci, _pi, _pi, _pd, _pd, _ci, _ci, _pi, _pd, _pi]),
     ("qexhip_dev_meson_corners", _ci, [_vp, _ci, _pi, _pi, _ci, _vp]),
     ("qexhip_dev_sym_shift", _ci, [_vp, _ci, _ci, _ci]),
     ("qexhip_dev_norm2slice", _ci, [_vp, _ci, _ci, _vp]),

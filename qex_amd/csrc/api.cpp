@@ -183,6 +183,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   nhyp_state_free(c);
   hisq_state_free(c);
   batch_state_free(c);
+  batch_f32_state_free(c);
   gauge_free(c);
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
@@ -691,6 +692,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   }
   gauge_release_scratch(c);
   f32_state_free(c);                 // the mixed-precision CG's fp32 links and fields: rebuilt by the next sloppy solve
+  batch_f32_state_free(c);           // and the batched form's fp32 fields
   return 0;
 }
 
@@ -827,6 +829,28 @@ extern "C" int qexhip_stag_solve_batch(qexhip_handle c, int n, double *const *x,
   if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
   return solve_batch_host(c, n, x, b, mass, r2req, maxits, -1, iters, r2_over_b2);
+}
+// Mixed-precision lock-step batches.  sloppy = 0 IS the fp64 entry; the batched fp32 form is one-rank only (batch_sloppy_check).
+extern "C" int qexhip_stag_solve_xx_batch_sloppy(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
+                                                 const double *r2req, int maxits, int par_even, int sloppy, int *iters,
+                                                 double *r2_over_b2, int *nupdates) {
+  if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, sloppy));
+  if (n < 1 || n > 4) { qexhip_set_error("batch solve: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
+  if (nupdates) for (int j = 0; j < n; j++) nupdates[j] = 0;
+  if (!sloppy) return qexhip_stag_solve_xx_batch(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2);
+  HIPCHK(hipSetDevice(c->device));
+  return solve_batch_sloppy_host(c, n, x, b, mass, r2req, maxits, par_even ? 1 : 0, sloppy, iters, r2_over_b2, nupdates);
+}
+extern "C" int qexhip_stag_solve_batch_sloppy(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
+                                              const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates) {
+  if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, sloppy));
+  if (n < 1 || n > 4) { qexhip_set_error("batch solve: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
+  if (nupdates) for (int j = 0; j < n; j++) nupdates[j] = 0;
+  if (!sloppy) return qexhip_stag_solve_batch(c, n, x, b, mass, r2req, maxits, iters, r2_final);
+  HIPCHK(hipSetDevice(c->device));
+  return solve_batch_sloppy_host(c, n, x, b, mass, r2req, maxits, -1, sloppy, iters, r2_final, nupdates);
 }
 extern "C" int qexhip_stag_links_info(qexhip_handle c, int *nlinks, int *compressed, double *max_dev) {
   if (!c) return QEXHIP_ERR_ARG;
@@ -967,12 +991,9 @@ extern "C" int qexhip_dev_zero(qexhip_handle c, int id, int parity) {
   CHK(find_field(c, id, &f));
   return blas_zero(c, *f, parity);
 }
-extern "C" int qexhip_dev_solve_batch(qexhip_handle c, int n, const int *x_ids, const int *b_ids, const double *mass,
-                                      const double *r2req, int maxits, int *iters, double *r2) {
-  if (!c || !x_ids || !b_ids || !mass || !r2req || n < 1 || n > 64) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  // every solution is zeroed while its system is set up, in order: a solution field that is also a source (of ANY system of
-  // the call) or another system's solution would be destroyed silently -- refuse such aliases for the whole call
+// every solution is zeroed while its system is set up, in order: a solution field that is also a source (of ANY system of
+// the call) or another system's solution would be destroyed silently -- refuse such aliases for the whole call
+static int batch_alias_check(int n, const int *x_ids, const int *b_ids) {
   for (int i = 0; i < n; i++)
     for (int j = 0; j < n; j++)
       if (x_ids[i] == b_ids[j] || (i != j && x_ids[i] == x_ids[j])) {
@@ -980,6 +1001,13 @@ extern "C" int qexhip_dev_solve_batch(qexhip_handle c, int n, const int *x_ids, 
                          x_ids[i] == b_ids[j] ? "the source" : "the solution", j);
         return QEXHIP_ERR_ARG;
       }
+  return 0;
+}
+extern "C" int qexhip_dev_solve_batch(qexhip_handle c, int n, const int *x_ids, const int *b_ids, const double *mass,
+                                      const double *r2req, int maxits, int *iters, double *r2) {
+  if (!c || !x_ids || !b_ids || !mass || !r2req || n < 1 || n > 64) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  CHK(batch_alias_check(n, x_ids, b_ids));
   for (int k0 = 0; k0 < n; k0 += 4) {          // lock-step batches of four, as qexhip_stag_solve_batch
     const int k = std::min(4, n - k0);
     DevField *xs[4], *bs[4];
@@ -990,6 +1018,24 @@ extern "C" int qexhip_dev_solve_batch(qexhip_handle c, int n, const int *x_ids, 
     CHK(solve_full_batch_dev(c, k, xs, bs, mass + k0, r2req + k0, maxits, iters ? iters + k0 : nullptr, r2 ? r2 + k0 : nullptr));
   }
   return 0;
+}
+// qexhip_stag_solve_batch_sloppy on resident fields: ONE lock-step batch (n <= 4)
+extern "C" int qexhip_dev_solve_batch_sloppy(qexhip_handle c, int n, const int *x_ids, const int *b_ids, const double *mass,
+                                             const double *r2req, int maxits, int sloppy, int *iters, double *r2, int *nupdates) {
+  if (!c || !x_ids || !b_ids || !mass || !r2req) return QEXHIP_ERR_ARG;
+  CHK(sloppy_check(c, sloppy));
+  if (n < 1 || n > 4) { qexhip_set_error("batch solve: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
+  if (nupdates) for (int j = 0; j < n; j++) nupdates[j] = 0;
+  if (!sloppy) return qexhip_dev_solve_batch(c, n, x_ids, b_ids, mass, r2req, maxits, iters, r2);
+  HIPCHK(hipSetDevice(c->device));
+  CHK(batch_sloppy_check(c, n, mass));
+  CHK(batch_alias_check(n, x_ids, b_ids));
+  DevField *xs[4], *bs[4];
+  for (int j = 0; j < n; j++) {
+    CHK(find_field(c, x_ids[j], &xs[j]));
+    CHK(find_field(c, b_ids[j], &bs[j]));
+  }
+  return solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates);
 }
 extern "C" int qexhip_nhyp_release(qexhip_handle c) {
   if (!c) return QEXHIP_ERR_ARG;

@@ -632,8 +632,9 @@ int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
 }
 }  // namespace
 
-int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
-                         int maxits, int *iters, double *r2_final) {
+// sloppy > 0: the inner solveXX's are the mixed-precision lock-step batch (batch_f32.hip), nupdates[j] <- system j's reliable updates
+static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                                 int maxits, int *iters, double *r2_final, int sloppy, int *nupdates) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
   BatchState *B = (BatchState *)c->batch;
   if (!B) { B = new BatchState(); c->batch = B; }
@@ -649,6 +650,7 @@ int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const
     s.x = x[j]; s.b = b[j];
     s.r = &B->f[4 * QX_MAXRHS + 3 * j]; s.y = &B->f[4 * QX_MAXRHS + 3 * j + 1]; s.d = &B->f[4 * QX_MAXRHS + 3 * j + 2];
     s.m = mass[j]; s.r2req = r2req[j]; s.its = 0;
+    if (nupdates) nupdates[j] = 0;
     CHK(blas_norm2(c, *s.b, 2, &c->dscal[2]));
     CHK(read_scalars(c, &c->dscal[2], 1, &s.b2));
     s.r2stop = s.r2req * s.b2;
@@ -683,7 +685,7 @@ int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const
     for (int par = 1; par >= 0; par--) {
       DevField *xs[QX_MAXRHS], *bs[QX_MAXRHS];
       double ms[QX_MAXRHS], rrs[QX_MAXRHS];
-      int idx[QX_MAXRHS], its[QX_MAXRHS], k = 0, mx = 0;
+      int idx[QX_MAXRHS], its[QX_MAXRHS], nup[QX_MAXRHS] = {0, 0, 0, 0}, k = 0, mx = 0;
       for (int j : active)
         if (S[j].par == par) {
           xs[k] = S[j].y; bs[k] = S[j].src; ms[k] = S[j].m; rrs[k] = S[j].rr; idx[k] = j;
@@ -692,8 +694,12 @@ int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const
         }
       if (!k) continue;
       // systems of one group share maxits: the remaining budget of the one that has used least
-      CHK(solve_xx_batch_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr));
-      for (int i = 0; i < k; i++) S[idx[i]].n = its[i];
+      if (sloppy) CHK(solve_xx_batch_sloppy_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr, nup));
+      else CHK(solve_xx_batch_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr));
+      for (int i = 0; i < k; i++) {
+        S[idx[i]].n = its[i];
+        if (nupdates) nupdates[idx[i]] += nup[i];
+      }
     }
     std::vector<int> next;
     for (int j : active) {
@@ -723,6 +729,35 @@ int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const
     if (iters) iters[j] = S[j].its;
     if (r2_final) r2_final[j] = (S[j].b2 != 0.0) ? (S[j].r2e + S[j].r2o) / S[j].b2 : 0.0;
   }
+  return 0;
+}
+
+int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                         int maxits, int *iters, double *r2_final) {
+  return solve_full_batch_impl(c, n, x, b, mass, r2req, maxits, iters, r2_final, 0, nullptr);
+}
+// n x Staggered.solve with the mixed-precision inner batch: the same ReconR / ReconL decisions and true-residual outer loop per system
+int solve_full_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                                int maxits, int sloppy, int *iters, double *r2_final, int *nupdates) {
+  if (!sloppy) {
+    if (nupdates) for (int j = 0; j < n && j < QX_MAXRHS; j++) nupdates[j] = 0;
+    return solve_full_batch_dev(c, n, x, b, mass, r2req, maxits, iters, r2_final);
+  }
+  CHK(batch_sloppy_check(c, n, mass));
+  return solve_full_batch_impl(c, n, x, b, mass, r2req, maxits, iters, r2_final, sloppy, nupdates);
+}
+
+// the first `count` (<= 4 per system) CG work fields of the batch state, for the mixed-precision batch (which leaves the fp64 CG's idle)
+int batch_work_fields(qexhip_ctx *c, int count, DevField **out) {
+  if (count < 0 || count > 4 * QX_MAXRHS) { qexhip_set_error("batch_work_fields: count"); return -1; }
+  BatchState *B = (BatchState *)c->batch;
+  if (!B) { B = new BatchState(); c->batch = B; }
+  while ((int)B->f.size() < 4 * QX_MAXRHS) {     // (callers that hold pointers into B->f have grown it past this already)
+    DevField nf;
+    CHK(field_alloc(c, nf));
+    B->f.push_back(nf);
+  }
+  for (int i = 0; i < count; i++) out[i] = &B->f[i];
   return 0;
 }
 

@@ -1,0 +1,437 @@
+// batch_f32.hip -- the mixed-precision form of the lock-step batched CG (batch.hip): up to four reliable-update solveXX's on the
+// SAME links, their fp32 iterations advanced together so that the fp32 link copy (dslash_f32.hip) is streamed ONCE per sweep for
+// all of them.  Where QEX's measurement code asks for it: src/observables/conn4d.nim:52 and scalarTrace.nim:42 default to a sloppy
+// solve, which src/quda/qudaWrapperImpl.nim:194-197 hands on as mixed precision.
+//
+// The rule is batch.hip's: every system keeps its own state (SlpScal: sigma, alpha, beta, max|r_s|^2, upd / noupd / done, k, nupd) and
+// its arithmetic is, operation for operation, that of the single-system solve_xx_sloppy_dev (solver.cpp) -- the sweep is
+// k_dslash_f32<NDIR, false, INIT, DOT, RECON> per system (same hop order, same (sgn*cb)*xs start, same final *= sgn, same fma nesting
+// in the dot, same workgroup partition, same fixed-order final sums), the BLAS kernels are k_slp_* with the system in blockIdx.y and
+// the single-system grid per system, and the reliable update runs the fp64 op_xx per system behind that system's `noupd` word.  A
+// system solved in a batch returns the bits -- solution, iterations, true residual, updates -- it returns alone.
+//
+// One rank, no ghost zones: t-sharded contexts are refused (the fp32 faces of all systems in one exchange are not built).
+#include "qexhip_internal.h"
+#include "site_index.h"
+#include "reduce.h"
+#include "cg_device.h"
+#include "dslash_f32_core.h"
+#include <algorithm>
+#include <cstring>
+
+#define QX_MAXRHS 4
+
+struct MrhsF32Args {
+  Geom g;
+  const f4v *W;                    // fp32 links of the output parity: [tile][pair][NL][64] float4
+  const unsigned long long *S;     // RECON: sign masks [tile][dir]
+  const float2 *in[QX_MAXRHS];
+  float2 *out[QX_MAXRHS];
+  const float2 *xs[QX_MAXRHS];
+  float cb[QX_MAXRHS];
+  double *partials[QX_MAXRHS];
+  const SlpScal *st;               // st[j].done switches system j off
+  int parity, nrhs;
+};
+
+// SECOND = false: out_j = +sum_mu (U in_j(+mu) - U^+ in_j(-mu))              (k_dslash_f32<.., INIT = false, DOT = false, ..>, sgn = +1)
+// SECOND = true : out_j = cb_j xs_j - sum_mu (...), partial <xs_j, out_j>   (k_dslash_f32<.., INIT = true,  DOT = true,  ..>, sgn = -1)
+// one lane per site; each pair of links is loaded once and applied to every live system
+template <int NDIR, int RECON, bool SECOND>
+__global__ void __launch_bounds__(256) k_dslash_mrhs_f32(MrhsF32Args A) {
+  bool act[QX_MAXRHS];
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
+  if (!any) return;
+  const Geom &g = A.g;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  double dotv[QX_MAXRHS] = {0, 0, 0, 0};
+  if (c < g.Vh) {
+    const SiteXYZT s = site_coord(g, c, A.parity);
+    constexpr int NL = RECON == 1 ? 6 : 9;
+    const f4v *w = A.W + (size_t)(c >> 6) * (NDIR / 2 * NL * 64) + (c & 63);
+    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : nullptr;
+    const float sgn = SECOND ? -1.f : 1.f;
+    float2 acc[QX_MAXRHS][3], xsv[QX_MAXRHS][3];
+#pragma unroll
+    for (int j = 0; j < QX_MAXRHS; j++) {
+      if (!act[j]) continue;
+      if (SECOND) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) xsv[j][k] = A.xs[j][vec_off(c, k)];
+      }
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+        acc[j][k] = SECOND ? make_float2((sgn * A.cb[j]) * xsv[j][k].x, (sgn * A.cb[j]) * xsv[j][k].y) : make_float2(0.f, 0.f);
+    }
+#pragma unroll 1
+    for (int pr = 0; pr < NDIR / 2; pr++) {
+      const int mu = pr & 3;
+      const int hop = pr >= 4 ? 3 : 1;
+      const int pf = nbr_pos<false>(g, c, s, mu, hop);
+      const int pb = nbr_pos<false>(g, c, s, mu, -hop);
+      f4v t[NL];
+#pragma unroll
+      for (int q = 0; q < NL; q++) t[q] = __builtin_nontemporal_load(&w[(size_t)(pr * NL + q) * 64]);
+      float2 U[9], W[9];
+      unpack_pair<NL>(t, U, W);
+      if (RECON == 1) {
+        const int lane = c & 63;
+        recon_row2f(U, (sm[2 * pr] >> lane) & 1ull);
+        recon_row2f(W, (sm[2 * pr + 1] >> lane) & 1ull);
+      }
+#pragma unroll
+      for (int j = 0; j < QX_MAXRHS; j++) {
+        if (!act[j]) continue;
+        float2 vf[3], vb[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { vf[k] = A.in[j][vec_off(pf, k)]; vb[k] = A.in[j][vec_off(pb, k)]; }
+        mv3f<false>(acc[j], U, vf);
+        mv3f<true>(acc[j], W, vb);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < QX_MAXRHS; j++) {
+      if (!act[j]) continue;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        acc[j][k].x *= sgn; acc[j][k].y *= sgn;
+        A.out[j][vec_off(c, k)] = acc[j][k];
+      }
+      if (SECOND) {
+        // xs_j is read AGAIN here rather than kept: 4 x 3 float2 held across the hop loop put the kernel at 178-184 VGPRs (2 waves/SIMD);
+        // read twice it is at 130-136 (3 waves/SIMD), still without scratch.  The same values, so the same dot.
+#pragma unroll
+        for (int k = 0; k < 3; k++) xsv[j][k] = A.xs[j][vec_off(c, k)];
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+          dotv[j] = fma((double)xsv[j][k].x, (double)acc[j][k].x, fma((double)xsv[j][k].y, (double)acc[j][k].y, dotv[j]));
+      }
+    }
+  }
+  if (SECOND) {
+#pragma unroll
+    for (int j = 0; j < QX_MAXRHS; j++) {
+      if (!act[j]) continue;             // uniform over the grid
+      const double r = block_sum_256(dotv[j]);
+      if (threadIdx.x == 0) A.partials[j][blockIdx.x] = r;
+    }
+  }
+}
+
+// ---- the reliable-update CG's BLAS and bookkeeping kernels (dslash_f32.hip: k_slp_*) for n systems: system = blockIdx.y, each with
+// the single-system kernel's grid in x, so the workgroup partials group as they do there ----
+struct SlpBatch {
+  double2 *x[QX_MAXRHS], *r[QX_MAXRHS];          // fp64: solution, true residual
+  const double2 *b[QX_MAXRHS], *Ax[QX_MAXRHS];   // fp64: source, A x of the reliable update
+  float2 *rs[QX_MAXRHS], *ps[QX_MAXRHS], *xs[QX_MAXRHS];
+  const float2 *aps[QX_MAXRHS];
+  double *dotp[QX_MAXRHS], *r2p[QX_MAXRHS];      // <p,Ap> partials of the second sweep; |r_s|^2 / |b - A x|^2 partials
+  SlpScal *s;
+};
+
+__global__ void __launch_bounds__(256) k_slpb_xpay(SlpBatch B, size_t n) {
+  const int j = blockIdx.y;
+  const SlpScal *s = &B.s[j];
+  if (s->done) return;
+  const bool conv = s->conv, first = s->first;
+  const double inv = 1.0 / s->sigma;
+  const float beta = (float)((s->r2s * s->sigma) / (s->r2s_old * s->sigma_p));
+  float2 *p = B.ps[j], *rs = B.rs[j];
+  const double2 *r = B.r[j];
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    float2 rv;
+    if (conv) {
+      const double2 v = r[i];
+      rv = make_float2((float)(inv * v.x), (float)(inv * v.y));
+      rs[i] = rv;
+    } else {
+      rv = rs[i];
+    }
+    if (first) p[i] = rv;
+    else {
+      const float2 pv = p[i];
+      p[i] = make_float2(fmaf(beta, pv.x, rv.x), fmaf(beta, pv.y, rv.y));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_slpb_update(SlpBatch B, size_t n, int ndot) {
+  const int j = blockIdx.y;
+  const SlpScal *s = &B.s[j];
+  if (s->done) return;
+  const double pAp = cg_sum_parts(B.dotp[j], ndot);
+  const float alpha = (float)(s->r2s / pAp);
+  float2 *xs = B.xs[j], *rs = B.rs[j];
+  const float2 *p = B.ps[j], *Ap = B.aps[j];
+  double acc = 0;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float2 pv = p[i], av = Ap[i];
+    float2 xv = xs[i], rv = rs[i];
+    xv.x = fmaf(alpha, pv.x, xv.x); xv.y = fmaf(alpha, pv.y, xv.y);
+    rv.x = fmaf(-alpha, av.x, rv.x); rv.y = fmaf(-alpha, av.y, rv.y);
+    xs[i] = xv; rs[i] = rv;
+    acc = fma((double)rv.x, (double)rv.x, fma((double)rv.y, (double)rv.y, acc));
+  }
+  const double t = block_sum_256(acc);
+  if (threadIdx.x == 0) B.r2p[j][blockIdx.x] = t;
+}
+
+// one workgroup per system
+__global__ void __launch_bounds__(256) k_slpb_close(SlpBatch B, int nparts, double delta2) {
+  SlpScal *s = &B.s[blockIdx.x];
+  if (s->done) return;
+  const double r2 = cg_sum_parts(B.r2p[blockIdx.x], nparts);
+  if (threadIdx.x == 0) {
+    s->k += 1;
+    s->r2s_old = s->r2s; s->sigma_p = s->sigma;
+    s->r2s = r2;
+    s->maxr2s = fmax(s->maxr2s, r2);
+    const int due = r2 < delta2 * s->maxr2s || r2 * s->sigma * s->sigma <= s->r2stop || s->k >= s->maxits;
+    s->upd = s->upd || due;
+    s->noupd = !s->upd;
+    s->conv = 0; s->first = 0;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_slpb_flush(SlpBatch B, size_t n) {
+  const int j = blockIdx.y;
+  const SlpScal *s = &B.s[j];
+  if (!s->upd || s->done) return;
+  const double sg = s->sigma;
+  double2 *x = B.x[j];
+  float2 *xs = B.xs[j];
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float2 v = xs[i];
+    double2 o = x[i];
+    o.x = fma(sg, (double)v.x, o.x); o.y = fma(sg, (double)v.y, o.y);
+    x[i] = o;
+    xs[i] = make_float2(0.f, 0.f);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_slpb_resid(SlpBatch B, size_t n) {
+  const int j = blockIdx.y;
+  const SlpScal *s = &B.s[j];
+  if (!s->upd || s->done) return;
+  double2 *r = B.r[j];
+  const double2 *b = B.b[j], *Ax = B.Ax[j];
+  double acc = 0;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const double2 bv = b[i], av = Ax[i];
+    const double2 rv = make_double2(bv.x - av.x, bv.y - av.y);
+    r[i] = rv;
+    acc = fma(rv.x, rv.x, fma(rv.y, rv.y, acc));
+  }
+  const double t = block_sum_256(acc);
+  if (threadIdx.x == 0) B.r2p[j][blockIdx.x] = t;
+}
+
+// one workgroup per system
+__global__ void __launch_bounds__(256) k_slpb_rclose(SlpBatch B, int nparts) {
+  SlpScal *s = &B.s[blockIdx.x];
+  if (!s->upd || s->done) return;
+  const double r2t = cg_sum_parts(B.r2p[blockIdx.x], nparts);
+  if (threadIdx.x == 0) {
+    s->r2t = r2t;
+    s->nupd += 1;
+    s->upd = 0; s->noupd = 1;
+    if (!(r2t > s->r2stop) || s->k >= s->maxits) {
+      s->done = 1;
+    } else {
+      const double sg = sqrt(r2t);
+      s->r2s = 1.0;
+      s->sigma = sg;
+      s->maxr2s = 1.0;
+      s->conv = 1;
+      if (!(s->r2s_old > 0)) s->first = 1;
+    }
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------
+enum { BF_R = 0, BF_P, BF_AP, BF_X, BF_T, BF_N };   // fp32 work fields per system
+
+struct BatchF32State {
+  DevFieldF f[BF_N * QX_MAXRHS];
+  SlpScal *s = nullptr;
+  double *partials = nullptr;
+  size_t npart = 0;
+};
+
+void batch_f32_state_free(qexhip_ctx *c) {
+  BatchF32State *S = (BatchF32State *)c->batch_f32;
+  if (!S) return;
+  for (auto &f : S->f) if (f.d) (void)hipFree(f.d);
+  if (S->s) (void)hipFree(S->s);
+  if (S->partials) (void)hipFree(S->partials);
+  delete S;
+  c->batch_f32 = nullptr;
+}
+
+static int bf_field(qexhip_ctx *c, BatchF32State *S, int idx, DevFieldF **f) {
+  DevFieldF &F = S->f[idx];
+  const size_t half = (size_t)c->g.etile * 192;
+  if (F.d && F.half != half) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipFree(F.d));
+    F.d = nullptr;
+  }
+  if (!F.d) {
+    F.half = half;
+    HIPCHK(hipMalloc((void **)&F.d, 2 * F.half * sizeof(float2)));
+    HIPCHK(hipMemsetAsync(F.d, 0, 2 * F.half * sizeof(float2), c->stream));   // padding lanes stay zero
+  }
+  *f = &F;
+  return 0;
+}
+
+// what every batched sloppy entry checks before anything is launched
+int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass) {
+  if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
+  if (c->nranks > 1 || c->g.halo) {
+    qexhip_set_error("batched sloppy solve: t-sharded contexts (more than one rank, or ghost zones in t) are not supported -- the "
+                     "sharded form is not built; use the fp64 batch or single-system sloppy solves there");
+    return -1;
+  }
+  for (int j = 0; j < n; j++)
+    if (mass[j] == 0.0) { qexhip_set_error("batched sloppy solve: mass 0 unsupported (op_xx's <p,Ap> needs 4 m^2 > 0)"); return -1; }
+  return 0;
+}
+
+template <int NDIR, int RECON>
+static void launch_mrhs_f32(const MrhsF32Args &A, bool second, int nb, hipStream_t st) {
+  if (second) hipLaunchKernelGGL((k_dslash_mrhs_f32<NDIR, RECON, true>), dim3(nb), dim3(256), 0, st, A);
+  else hipLaunchKernelGGL((k_dslash_mrhs_f32<NDIR, RECON, false>), dim3(nb), dim3(256), 0, st, A);
+}
+static int sweep_mrhs_f32(qexhip_ctx *c, const MrhsF32Args &A, int fmt, bool second) {
+  const int nb = (c->g.Vh + 255) / 256;
+  ScopedTimer tm(c, "dslash_batch_f32", c->stream);
+  if (c->ndir == 8) { if (fmt == 1) launch_mrhs_f32<8, 1>(A, second, nb, c->stream); else launch_mrhs_f32<8, 0>(A, second, nb, c->stream); }
+  else { if (fmt == 1) launch_mrhs_f32<16, 1>(A, second, nb, c->stream); else launch_mrhs_f32<16, 0>(A, second, nb, c->stream); }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// n (1..4) mixed-precision solveXX's in lock-step: solve_xx_batch_dev's semantics (own mass, r2req, iteration count; shared maxits),
+// solve_xx_sloppy_dev's iteration per system.  iters: fp32 iterations; r2_over_b2: the TRUE residual; nupdates: reliable updates.
+int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                              int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates) {
+  const Geom &g = c->g;
+  CHK(batch_sloppy_check(c, n, mass));
+  int fmt = 0;
+  const void *Wv = nullptr;
+  const unsigned long long *Sv = nullptr;
+  CHK(f32_links_dev(c, &Wv, &Sv, &fmt));
+  BatchF32State *S = (BatchF32State *)c->batch_f32;
+  if (!S) { S = new BatchF32State(); c->batch_f32 = S; }
+  if (!S->s) HIPCHK(hipMalloc((void **)&S->s, sizeof(SlpScal) * QX_MAXRHS));
+  const size_t nvec = (size_t)g.ntile * 192;
+  const int nbd = (g.Vh + 255) / 256;                                          // <p,Ap> partials of a sweep (f32_op_xx's count)
+  const int nbb = (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048));   // the k_slp_* grid (grid_for)
+  const size_t per = (size_t)nbd + nbb;
+  if (S->npart < per * QX_MAXRHS) {
+    if (S->partials) HIPCHK(hipFree(S->partials));
+    S->partials = nullptr; S->npart = 0;
+    HIPCHK(hipMalloc((void **)&S->partials, per * QX_MAXRHS * sizeof(double)));
+    S->npart = per * QX_MAXRHS;
+  }
+  DevField *w64[2 * QX_MAXRHS];
+  CHK(batch_work_fields(c, 2 * QX_MAXRHS, w64));                             // r, A x per system
+  const int par = par_even ? 0 : 1;
+  const int NL = fmt == 1 ? 6 : 9;
+  MrhsF32Args A1, A2;
+  SlpBatch L;
+  memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2); memset(&L, 0, sizeof L);
+  double m2[QX_MAXRHS];
+  DevField *rj[QX_MAXRHS], *axj[QX_MAXRHS];
+  for (int j = 0; j < n; j++) {
+    DevFieldF *rs, *ps, *aps, *xs, *t;
+    CHK(bf_field(c, S, BF_N * j + BF_R, &rs));
+    CHK(bf_field(c, S, BF_N * j + BF_P, &ps));
+    CHK(bf_field(c, S, BF_N * j + BF_AP, &aps));
+    CHK(bf_field(c, S, BF_N * j + BF_X, &xs));
+    CHK(bf_field(c, S, BF_N * j + BF_T, &t));
+    rj[j] = w64[2 * j]; axj[j] = w64[2 * j + 1];
+    m2[j] = mass[j] * mass[j];
+    // exactly the start of solve_xx_sloppy_dev: x = 0, b2, r = b, x_s = 0, k_slp_init
+    CHK(blas_zero(c, *x[j], 2));
+    CHK(blas_norm2(c, *b[j], par, &c->dscal[0]));
+    CHK(blas_copy(c, *rj[j], *b[j], par));
+    HIPCHK(hipMemsetAsync(xs->par(par), 0, xs->half * sizeof(float2), c->stream));
+    CHK(slp_init(c, &S->s[j], r2req[j], maxits));
+    A1.in[j] = ps->par(par); A1.out[j] = t->par(1 - par);
+    A2.in[j] = t->par(1 - par); A2.out[j] = aps->par(par); A2.xs[j] = ps->par(par);
+    A2.cb[j] = (float)(4.0 * m2[j]);
+    A2.partials[j] = S->partials + per * j;
+    L.x[j] = x[j]->par(par); L.r[j] = rj[j]->par(par); L.b[j] = b[j]->par(par); L.Ax[j] = axj[j]->par(par);
+    L.rs[j] = rs->par(par); L.ps[j] = ps->par(par); L.xs[j] = xs->par(par); L.aps[j] = aps->par(par);
+    L.dotp[j] = S->partials + per * j; L.r2p[j] = S->partials + per * j + nbd;
+  }
+  L.s = S->s;
+  for (MrhsF32Args *A : {&A1, &A2}) {
+    const int parity = (A == &A1) ? 1 - par : par;
+    A->g = g; A->st = S->s; A->nrhs = n; A->parity = parity;
+    A->W = (const f4v *)Wv + (size_t)parity * g.ntile * (c->ndir / 2) * NL * 64;
+    A->S = fmt == 1 ? Sv + (size_t)parity * g.ntile * c->ndir : nullptr;
+  }
+  SlpScal h[QX_MAXRHS];
+  auto read_states = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(c->pinned, S->s, sizeof(SlpScal) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(h, c->pinned, sizeof(SlpScal) * n);
+    return 0;
+  };
+  auto all_done = [&]() { for (int j = 0; j < n; j++) if (!h[j].done) return false; return true; };
+  CHK(read_states());
+  const int every = std::max(1, c->opt_sloppy_check);
+  int k = 0;
+  while (!all_done() && k < maxits) {
+    const int chunk = std::min(32, maxits - k);
+    for (int i = 0; i < chunk; i++, k++) {
+      {
+        ScopedTimer tm(c, "blas", c->stream);
+        k_slpb_xpay<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
+      }
+      CHK(sweep_mrhs_f32(c, A1, fmt, false));
+      CHK(sweep_mrhs_f32(c, A2, fmt, true));
+      {
+        ScopedTimer tm(c, "blas", c->stream);
+        k_slpb_update<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec, nbd);
+      }
+      k_slpb_close<<<n, 256, 0, c->stream>>>(L, nbb, SLP_DELTA * SLP_DELTA);
+      HIPCHK(hipGetLastError());
+      // the (device-gated) reliable update of every system whose `upd` is up, posted as solve_xx_sloppy_dev posts its own; a system
+      // that is done counts no further, so the host's k is each live system's own k
+      if ((k + 1) % every == 0 || k + 1 >= maxits) {
+        k_slpb_flush<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
+        HIPCHK(hipGetLastError());
+        for (int j = 0; j < n; j++) CHK(op_xx(c, *axj[j], *x[j], m2[j], par_even, 0, &S->s[j].noupd));
+        k_slpb_resid<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
+        k_slpb_rclose<<<n, 256, 0, c->stream>>>(L, nbb);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    CHK(read_states());
+  }
+  for (int j = 0; j < n; j++) {
+    if (iters) iters[j] = h[j].k;
+    if (r2_over_b2) r2_over_b2[j] = (h[j].b2 != 0.0) ? h[j].r2t / h[j].b2 : 0.0;
+    if (nupdates) nupdates[j] = h[j].nupd;
+  }
+  return 0;
+}
+
+// host-field entry points (solve_batch_host with the precision of the inner CG): xx_parity >= 0 solveXX on that parity, else the full solve
+int solve_batch_sloppy_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass, const double *r2req,
+                            int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates) {
+  CHK(batch_sloppy_check(c, n, mass));
+  DevField *xs[QX_MAXRHS], *bs[QX_MAXRHS];
+  CHK(batch_io_fields(c, n, xs, bs));
+  for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
+  if (xx_parity >= 0) CHK(solve_xx_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2, nupdates));
+  else CHK(solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
+  for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
+  return 0;
+}

@@ -164,6 +164,13 @@ int f32_links(qexhip_ctx *c, int *fmt_out, double *dev_out) {
   return 0;
 }
 
+int f32_links_dev(qexhip_ctx *c, const void **W, const unsigned long long **Sm, int *fmt) {
+  CHK(f32_links(c, fmt, nullptr));
+  F32State *S = st_of(c);
+  *W = S->W; *Sm = S->S;
+  return 0;
+}
+
 // etile = ntile without a halo: the ghost zones cost nothing on a one-rank context that has none.  A field allocated before the
 // geometry changed (qexhip_comm_force_halo) is allocated again.
 int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {

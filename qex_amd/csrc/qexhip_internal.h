@@ -200,6 +200,7 @@ struct qexhip_ctx {
   double *meson_buf = nullptr; size_t meson_cap = 0; // workgroup partials + global table of the meson / slice-norm reductions (meson.hip)
   unsigned long links_gen = 0;                       // bumped by every writer of W / Wc (links_compress ends each of them): the fp32 copy's staleness test
   void *f32 = nullptr;                               // F32State (dslash_f32.hip): fp32 links + fields + SlpScal of the mixed-precision CG
+  void *batch_f32 = nullptr;                         // BatchF32State (batch_f32.hip): fp32 fields + SlpScal[4] of the mixed-precision batched CG
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -246,6 +247,16 @@ void batch_state_free(qexhip_ctx *c);
 int batch_io_fields(qexhip_ctx *c, int n, DevField **xs, DevField **bs);
 int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                          int maxits, int *iters, double *r2_final);
+int batch_work_fields(qexhip_ctx *c, int count, DevField **out);
+// ---- batch_f32.hip: the mixed-precision lock-step batch (one rank, no ghost zones) ----
+void batch_f32_state_free(qexhip_ctx *c);
+int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass);     // n in 1..4, not t-sharded, no mass 0 -- before anything is launched
+int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                              int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
+int solve_full_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                                int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);     // (batch.hip)
+int solve_batch_sloppy_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass, const double *r2req,
+                            int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates);
 int nhyp_fforce(qexhip_ctx *c, double *f_host, int n, const double *const *phi, const double *mass, const double *scale,
                 const double *r2req, int maxits, int bcmask, const int ph[4], int *iters, DevField *const *phi_dev = nullptr);
 int solve_batch_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass,
@@ -327,6 +338,7 @@ double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs = 1
 enum { F32_T = 0, F32_R, F32_P, F32_AP, F32_X, F32_IN, F32_NF };   // fp32 work fields
 #define SLP_DELTA 0.1                                    // reliable-update delta (QEX's reliable_delta, qudaSet.nim:63)
 int f32_links(qexhip_ctx *c, int *fmt, double *dev);     // the fp32 copy of the links, rebuilt when links_gen moved
+int f32_links_dev(qexhip_ctx *c, const void **W, const unsigned long long **S, int *fmt);   // f32_links + the copy's device pointers (W: float4)
 int f32_field(qexhip_ctx *c, int slot, DevFieldF **f);
 int f32_op_xx(qexhip_ctx *c, DevFieldF &r, DevFieldF &x, double m2, int par_even, int dot, const int *done, int *nparts);
 int f32_from_f64(qexhip_ctx *c, DevFieldF &y, const DevField &x, int parity, double a);              // y = f32(a x)

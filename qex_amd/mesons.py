@@ -115,14 +115,16 @@ def wallSource(lo, t0, v, t_offset=0):
     return r
 
 
-def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0):
+def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0, sloppy=0):
     """The measurement of fpvaMeas.nim's main block (:80-138) on resident fields: for each colour ic, the point source src at
     (0,0,0,t0) and its three symmetric shifts are solved in ONE lock-step batch of four, the shifted propagators are shifted back at
     the sink, and the contractions of all three colours run on the device in one launch per table:
         cl     = stagLocalMesons(dest, dest, t0)
         cs[mu] = stagLocalMesons(dest, symShift(solve(symShift(src, mu)), mu), t0)        mu = 0, 1, 2
     lo is the rank-local Layout, t_offset its first global t.  Returns (cl, [cx, cy, cz], stats) with the raw (nt, 8) tables
-    (printLocalMesons transforms and scales them) and stats = {"solve_s", "contract_s", "iterations"}."""
+    (printLocalMesons transforms and scales them) and stats = {"solve_s", "contract_s", "iterations", "updates"}.
+    sloppy = 1 (or 2) runs the batches in mixed precision (Context.dev_solve_batch(..., sloppy=...): one rank only); "updates" then
+    holds the reliable updates per colour and system, and zeros for the fp64 batch."""
     import time
 
     ctx = stag.ctx
@@ -137,16 +139,21 @@ def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0):
         dest = [new() for _ in range(3)]
         rs = [[new() for _ in range(3)] for _ in range(3)]      # rs[mu][ic]
         src, srcs, dests = new(), [new() for _ in range(3)], [new() for _ in range(3)]
-        stats = {"solve_s": 0.0, "contract_s": 0.0, "iterations": []}
+        stats = {"solve_s": 0.0, "contract_s": 0.0, "iterations": [], "updates": []}
         for ic in range(3):
             ctx.field_upload(src, pointSource(lo, [0, 0, 0, t0], ic, t_offset))
             for mu in range(3):
                 ctx.dev_sym_shift(srcs[mu], src, mu)
             ctx.sync()
             t = time.perf_counter()
-            its, _ = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits)
+            if sloppy:
+                its, _, nup = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits, sloppy=sloppy)
+            else:
+                its, _ = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits)
+                nup = [0] * 4
             stats["solve_s"] += time.perf_counter() - t
             stats["iterations"].append(its)
+            stats["updates"].append(nup)
             for mu in range(3):
                 ctx.dev_sym_shift(rs[mu][ic], dests[mu], mu)
         ctx.sync()

@@ -250,11 +250,27 @@ class Context:
     def dev_zero(self, fid, subset="all"):
         check(lib().qexhip_dev_zero(self._h, int(fid), _SUBSET[subset]))
 
-    def dev_solve_batch(self, x_ids, b_ids, masses, r2req, maxits=1000000):
-        """n x Staggered.solve on resident fields (lock-step batches of four); returns (iterations, r2) per system"""
+    def dev_solve_batch(self, x_ids, b_ids, masses, r2req, maxits=1000000, sloppy=None):
+        """n x Staggered.solve on resident fields (lock-step batches of four); returns (iterations, r2) per system.
+        sloppy = 0, 1 or 2 (SloppyNone / SloppySingle / SloppyHalf) chooses the precision of the batched CG explicitly
+        (qexhip_dev_solve_batch_sloppy; mixed precision on one rank only) and returns (iterations, r2, reliable updates)."""
         n = len(x_ids)
         rq = [float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]
         its, fin = (C.c_int * n)(), (C.c_double * n)()
+        if sloppy is not None:
+            sloppy = _batch_sloppy(sloppy)
+            ms = [float(v) for v in masses]
+            xi, bi = [int(v) for v in x_ids], [int(v) for v in b_ids]
+            nup = []
+            for k0 in range(0, n, 4):           # the entry takes one lock-step batch of at most four
+                k = min(4, n - k0)
+                i4, f4, u4 = (C.c_int * k)(), (C.c_double * k)(), (C.c_int * k)()
+                check(lib().qexhip_dev_solve_batch_sloppy(self._h, k, (C.c_int * k)(*xi[k0:k0 + k]), (C.c_int * k)(*bi[k0:k0 + k]),
+                                                          (C.c_double * k)(*ms[k0:k0 + k]), (C.c_double * k)(*rq[k0:k0 + k]),
+                                                          int(maxits), sloppy, i4, f4, u4))
+                its[k0:k0 + k], fin[k0:k0 + k] = list(i4), list(f4)
+                nup += list(u4)
+            return list(its), list(fin), nup
         check(lib().qexhip_dev_solve_batch(self._h, n, (C.c_int * n)(*[int(v) for v in x_ids]), (C.c_int * n)(*[int(v) for v in b_ids]),
                                            (C.c_double * n)(*[float(v) for v in masses]), (C.c_double * n)(*rq), int(maxits), its, fin))
         return list(its), list(fin)
@@ -482,7 +498,9 @@ class Staggered:
         if sp.verbosity > 1:
             print("stagSolve(HIP): " + sp.getStats())
 
-    def _batch(self, fn_name, xs, bs, ms, r2req, maxits, parEven=None):
+    def _batch(self, fn_name, xs, bs, ms, r2req, maxits, parEven=None, sloppy=None):
+        if sloppy is not None:
+            sloppy = _batch_sloppy(sloppy)
         n = len(xs)
         if not (1 <= n <= 4 and len(bs) == n and len(ms) == n):
             raise ValueError("batch solve: 1..4 systems, one source and one mass each")
@@ -491,22 +509,43 @@ class Staggered:
         bp = (C.c_void_p * n)(*[_p(a).value for a in bs])
         mv, rv = (C.c_double * n)(*[float(v) for v in ms]), (C.c_double * n)(*rq)
         its, fin = (C.c_int * n)(), (C.c_double * n)()
+        if sloppy is not None:
+            nup = (C.c_int * n)()
+            if parEven is None:
+                check(lib().qexhip_stag_solve_batch_sloppy(self.ctx._h, n, xp, bp, mv, rv, int(maxits), sloppy, its, fin, nup))
+            else:
+                check(lib().qexhip_stag_solve_xx_batch_sloppy(self.ctx._h, n, xp, bp, mv, rv, int(maxits), 1 if parEven else 0,
+                                                              sloppy, its, fin, nup))
+            return list(its), list(fin), list(nup)
         if parEven is None:
             check(lib().qexhip_stag_solve_batch(self.ctx._h, n, xp, bp, mv, rv, int(maxits), its, fin))
         else:
             check(lib().qexhip_stag_solve_xx_batch(self.ctx._h, n, xp, bp, mv, rv, int(maxits), 1 if parEven else 0, its, fin))
         return list(its), list(fin)
 
-    def solve_batch(self, xs, bs, ms, sps):
+    def solve_batch(self, xs, bs, ms, sps, sloppy=None):
         """n (<= 4) x Staggered.solve on these links in lock-step: the links are streamed once per sweep for
         all systems.  sps: one SolverParams (shared r2req / maxits) or one per system; each gets the
-        statistics of its own system, exactly as n calls of solve would record them."""
+        statistics of its own system, exactly as n calls of solve would record them.
+        sloppy: None = fp64, and a SolverParams that asks for a sloppy solve is refused; 0, 1 or 2 (SloppyNone / SloppySingle /
+        SloppyHalf) = the precision of the batched CG, chosen explicitly whatever sps say (mixed precision: one rank only; every
+        system comes out bit for bit as its own sloppy solve does; sp.reliableUpdates gets each system's updates)."""
         sl = [sps] * len(xs) if isinstance(sps, SolverParams) else list(sps)
-        if any(int(getattr(sp, "sloppySolve", SloppyNone)) != SloppyNone for sp in sl):
-            raise ValueError("sloppySolve applies to single-system solves only (lock-step batched solves run in fp64)")
+        if sloppy is not None:
+            sloppy = _batch_sloppy(sloppy)
+        elif any(int(getattr(sp, "sloppySolve", SloppyNone)) != SloppyNone for sp in sl):
+            raise ValueError("sloppySolve applies to single-system solves only: a lock-step batch runs in fp64 unless the "
+                             "mixed-precision batch is asked for with the keyword sloppy=1 (solve_batch / solveXX_batch / "
+                             "dev_solve_batch)")
         t0 = time.time()
-        its, fin = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl))
+        nup = [0] * len(xs)
+        if sloppy is None:
+            its, fin = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl))
+        else:
+            its, fin, nup = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl), sloppy=sloppy)
         dt = (time.time() - t0) / len(xs)
+        for sp, u in zip(sl, nup):
+            sp.reliableUpdates += u
         for sp, i, f in zip(sl, its, fin):
             sp.calls += 1
             sp.iterations += i
@@ -516,9 +555,10 @@ class Staggered:
             sp.r2 = f
         return its
 
-    def solveXX_batch(self, xs, bs, ms, r2req, maxits, parEven=True):
-        """n (<= 4) x solveEE / solveOO in lock-step; returns (iterations, r2/b2) per system"""
-        return self._batch("xx", xs, bs, ms, r2req, maxits, parEven)
+    def solveXX_batch(self, xs, bs, ms, r2req, maxits, parEven=True, sloppy=None):
+        """n (<= 4) x solveEE / solveOO in lock-step; returns (iterations, r2/b2) per system.  sloppy = 0, 1 or 2 chooses the
+        precision explicitly (as in solve_batch) and returns (fp32 iterations, true r2/b2, reliable updates) per system."""
+        return self._batch("xx", xs, bs, ms, r2req, maxits, parEven, sloppy)
 
     def solveXX_multi(self, xs, b, shifts, sp, parEven=True, histcap=0):
         """Staggered.solveXX(xs, b, ms, sp, subset) (stagSolve.nim:296-345): shifts[0] = base mass."""
@@ -532,6 +572,13 @@ class Staggered:
                                                int(sp.maxits), 1 if parEven else 0, C.byref(its), _p(hist), histcap))
         sp.iterations += its.value
         sp.r2hist = hist[: min(histcap, its.value + 1)] if histcap else None
+
+
+def _batch_sloppy(sloppy):
+    """the explicit precision of a lock-step batch: 0, 1 or 2, checked before any library call"""
+    if isinstance(sloppy, bool) or not isinstance(sloppy, (int, np.integer)) or not 0 <= int(sloppy) <= 2:
+        raise ValueError("sloppy = %r: None (fp64, the default), 0 (SloppyNone), 1 (SloppySingle) or 2 (SloppyHalf, runs single)" % (sloppy,))
+    return int(sloppy)
 
 
 def newStag(ctx, g):
