@@ -5,7 +5,8 @@
 // repetitions (:260-272), the fork's fforce loop (src/stagg_pv_hmc/staghmc_spv.nim:758-830).  Each is
 // `stag.solve` -> solveXX -> CG (src/physics/stagSolve.nim:57-138, src/solvers/cg.nim:55-272).  The Dslash
 // is HBM-bound and 89 % of its bytes are links, so streaming the links ONCE for up to four right-hand
-// sides cuts the bytes per system from 864 to (768 + 96 n)/n (352 at n = 3, compressed links).  Every
+// sides cuts the bytes per system from 864 to (768 + 96 n)/n (352 at n = 3, compressed links).  One sweep
+// body, mrhs_body, behind the kernels k_dslash_mrhs (sites from the field) and k_dslash_mrhs_fused (fused_sweep.h).  Every
 // system keeps its own CG state (alpha, beta, residual, iteration count, done flag) and its arithmetic
 // is, operation for operation, that of the single-system path (same per-site accumulation order, same
 // workgroup partials, same fixed-order final sums), so each solution and iteration count equals what
@@ -18,6 +19,7 @@
 #include "fused_sweep.h"
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #define QX_MAXRHS 4
@@ -33,199 +35,96 @@ struct MrhsArgs {
   double *partials[QX_MAXRHS];
   const CgScal *st;            // st[j].done switches system j off
   int parity, nrhs, swz, ntstore;
-  int c0, c1, d0, d1, nb1;     // site range [c0, c1) for workgroups < nb1, [d0, d1) for the rest (both t-faces in one launch)
+  SweepRanges r;               // [c0, c1) for workgroups < nb1, [d0, d1) for the rest (both t-faces in one launch; fused: interior, low face)
   int part_off;                // first <xs, out> partial this launch writes
 };
-
-// SECOND = false: out_j = +sum_mu (U in_j(+mu) - U^+ in_j(-mu))              (stagDP, first half of stagD2ee)
-// SECOND = true : out_j = cb_j xs_j - sum_mu (...), partial <xs_j, out_j>   (stagDM + 4m^2 x + <p,Ap>)
-template <int NDIR, int RECON, bool SECOND, bool HALO>
-__global__ void __launch_bounds__(256) k_dslash_mrhs(MrhsArgs A) {
-  bool act[QX_MAXRHS];
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
-  if (!any) return;
-  int bid = blockIdx.x;
-  if (A.swz) bid = (bid & 7) * (A.swz >> 3) + (bid >> 3);
-  int c = A.c0 + bid * 256 + threadIdx.x, clim = A.c1;
-  if (bid >= A.nb1) { c = A.d0 + (bid - A.nb1) * 256 + threadIdx.x; clim = A.d1; }
-  double dotv[QX_MAXRHS] = {0, 0, 0, 0};
-  if (c < clim) {
-    const Geom &g = A.g;
-    SiteXYZT s = site_coord(g, c, A.parity);
-    double2 acc[QX_MAXRHS][3], xsv[QX_MAXRHS][3];
-    const double sgn = SECOND ? -1.0 : 1.0;
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;
-      if (SECOND) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          xsv[j][k] = A.xs[j][vec_off(c, k)];
-          acc[j][k].x = (sgn * A.cb[j]) * xsv[j][k].x;
-          acc[j][k].y = (sgn * A.cb[j]) * xsv[j][k].y;
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[j][k] = make_double2(0.0, 0.0);
-      }
-    }
-    constexpr int NLOAD = RECON == 1 ? 6 : (RECON == 2 ? 7 : 9);
-    constexpr int LROW = NLOAD * 64;
-    const double2 *w = A.W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63);
-    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : nullptr;
-#pragma unroll 1
-    for (int pr = 0; pr < NDIR / 2; pr++) {
-      const int mu = pr & 3;
-      const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
-      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
-      const double2 *wp = w + (size_t)pr * (2 * LROW);
-      double2 U[9], Wm[9];
-#pragma unroll
-      for (int k = 0; k < NLOAD; k++) {
-        d2v t = __builtin_nontemporal_load((const d2v *)&wp[k * 64]);
-        U[k] = make_double2(t.x, t.y);
-      }
-#pragma unroll
-      for (int k = 0; k < NLOAD; k++) {
-        d2v t = __builtin_nontemporal_load((const d2v *)&wp[LROW + k * 64]);
-        Wm[k] = make_double2(t.x, t.y);
-      }
-      if (RECON == 1) {
-        const int lane = c & 63;
-        recon_row2<1>(U, (sm[2 * pr] >> lane) & 1ull);
-        recon_row2<1>(Wm, (sm[2 * pr + 1] >> lane) & 1ull);
-      } else if (RECON == 2) {
-        recon_row2<2>(U, false);
-        recon_row2<2>(Wm, false);
-      }
-#pragma unroll
-      for (int j = 0; j < QX_MAXRHS; j++) {
-        if (!act[j]) continue;
-        double2 vf[3], vb[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) vf[k] = A.in[j][vec_off(pf, k)];
-#pragma unroll
-        for (int k = 0; k < 3; k++) vb[k] = A.in[j][vec_off(pb, k)];
-        mv3<false>(acc[j], U, vf);
-        mv3<true>(acc[j], Wm, vb);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        acc[j][k].x *= sgn; acc[j][k].y *= sgn;
-        if (A.ntstore) {
-          d2v t; t.x = acc[j][k].x; t.y = acc[j][k].y;
-          __builtin_nontemporal_store(t, (d2v *)&A.out[j][vec_off(c, k)]);
-        } else {
-          A.out[j][vec_off(c, k)] = acc[j][k];
-        }
-      }
-      if (SECOND) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) dotv[j] = fma(xsv[j][k].x, acc[j][k].x, fma(xsv[j][k].y, acc[j][k].y, dotv[j]));
-      }
-    }
-  }
-  if (SECOND) {
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;             // uniform over the grid
-      double r = block_sum_256(dotv[j]);
-      if (threadIdx.x == 0) A.partials[j][A.part_off + blockIdx.x] = r;
-    }
-  }
-}
-
-// The lock-step sweep of a t-sharded slab on the peer transport as ONE launch on ONE stream -- k_dslash_fused (dslash.hip) for up to four
-// systems, with the workgroup roles of fused_sweep.h (the push workgroups send the faces of all systems, one piece each).  A system's
-// arithmetic is k_dslash_fused's: same hop order (local first), same partial slots; parked or not a block gives the same bits.
+// what the fused launch carries beside them
 struct MrhsFusedArgs {
-  MrhsArgs a;                       // c0..c1 interior, d0..d1 low face (workgroups >= nb1)
+  MrhsArgs a;
   FusedSweep fs;                    // e0..e1 high face, push, ghost words, bookkeeping
   const double2 *gh_hi[QX_MAXRHS], *gh_lo[QX_MAXRHS];
 };
-template <int NDIR, int RECON, bool SECOND>
-__global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
-  const MrhsArgs &A = F.a;
+__device__ __forceinline__ const MrhsArgs &mrhs_args(const MrhsArgs &P) { return P; }
+__device__ __forceinline__ const MrhsArgs &mrhs_args(const MrhsFusedArgs &P) { return P.a; }
+
+// The lock-step sweep's one body, dslash_body (dslash.hip) for up to four systems: each pair of links is fetched once (LinkCursor) and
+// applied to every live system.
+//   SECOND = false: out_j = +sum_mu (U in_j(+mu) - U^+ in_j(-mu))              (stagDP, first half of stagD2ee)
+//   SECOND = true : out_j = cb_j xs_j - sum_mu (...), partial <xs_j, out_j>   (stagDM + 4m^2 x + <p,Ap>)
+//   Args = MrhsArgs (FUSED false): the sites of sweep_site, t-neighbours from the field (HALO: its ghost tiles); XCD swizzle as k_dslash
+//   Args = MrhsFusedArgs (FUSED true): the sweep of a t-sharded slab on the peer transport as ONE launch on ONE stream, with the
+//            workgroup roles of fused_sweep.h (the push workgroups send the faces of all systems, one piece each).  A system's arithmetic
+//            is k_dslash_fused's: same hop order (local first), same partial slots; parked or not a block gives the same bits.
+// Every hop loop stays rolled: four systems' accumulators leave no registers for a second pair of links in flight (220 VGPRs at
+// <8,1,true,false>, 2 waves per SIMD; profiles/sweep_refactor_resources.txt).
+template <int NDIR, int RECON, bool SECOND, bool HALO, class Args>
+__device__ __forceinline__ void mrhs_body(const Args &P) {
+  constexpr bool FUSED = std::is_same<Args, MrhsFusedArgs>::value;
+  const MrhsArgs &A = mrhs_args(P);
   bool act[QX_MAXRHS];
   bool any = false;
 #pragma unroll
   for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
-  const bool skip = !any;              // every system has converged: nothing is pushed, the credits still go back
-  if (fused_push(F.fs, skip)) return;
+  const bool skip = !any;              // every system has converged: nothing is pushed, a fused launch still returns the credits it owes
+  if (skip && !FUSED) return;
   FusedRole R;
-  fused_enter(F.fs, A.nb1, R);
-  for (;;) {
-    int lb;
-    if (!fused_next_block(F.fs, R, lb)) break;
-    int clim;
-    const int c = fused_site(F.fs, R, lb, A.c0, A.c1, A.d0, A.d1, clim);
+  if constexpr (FUSED) {
+    if (fused_push(P.fs, skip)) return;
+    fused_enter(P.fs, A.r.nb1, R);
+  } else {
+    R.bid = blockIdx.x; R.cleanup = false; R.bnd = false; R.parked = false;
+  }
+  for (;;) {                               // one pass; a cleanup workgroup takes every fz.ncl-th parked block
+    // (lb is fused_next_block's to set in the fused kernel: initialised from R.bid there as well, k_dslash_mrhs_fused<8,0,false> takes
+    // 171 VGPRs instead of the 165 of the two-kernel form and drops from 3 to 2 waves per SIMD)
+    int lb, clim, c;
+    if constexpr (!FUSED) lb = R.bid;
+    if constexpr (FUSED) {
+      if (!fused_next_block(P.fs, R, lb)) break;
+      c = fused_site(P.fs, R, lb, A.r, clim);
+    } else {
+      if (A.swz) lb = (lb & 7) * (A.swz >> 3) + (lb >> 3);
+      sweep_site(A.r, lb, c, clim);
+    }
     double dotv[QX_MAXRHS] = {0, 0, 0, 0};
     const bool active = c < clim && !skip;
     const Geom &g = A.g;
     const SiteXYZT s = site_coord(g, c, A.parity);
-    const int tu = __builtin_amdgcn_readfirstlane(s.t);
+    const int tu = FUSED ? __builtin_amdgcn_readfirstlane(s.t) : 0;
     const bool hi1 = tu + 1 >= g.X[3], lo1 = tu - 1 < 0, hi3 = tu + 3 >= g.X[3], lo3 = tu - 3 < 0;
     double2 acc[QX_MAXRHS][3], xsv[QX_MAXRHS][3];
     const double sgn = SECOND ? -1.0 : 1.0;
-    constexpr int NLOAD = RECON == 1 ? 6 : (RECON == 2 ? 7 : 9);
-    constexpr int LROW = NLOAD * 64;
-    const double2 *w = A.W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63);
-    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : nullptr;
+    const LinkCursor<NDIR, RECON> L(A.W, A.S, c);
     auto pair = [&](const int pr, const bool do_f, const bool do_b) __attribute__((always_inline)) {
       const int mu = pr & 3;
       const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<true>(g, c, s, mu, hop);
-      const int pb = nbr_pos<true>(g, c, s, mu, -hop);
-      const double2 *wp = w + (size_t)pr * (2 * LROW);
+      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
+      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
       double2 U[9], Wm[9];
-      if (do_f) {
-#pragma unroll
-        for (int k = 0; k < NLOAD; k++) {
-          d2v t = __builtin_nontemporal_load((const d2v *)&wp[k * 64]);
-          U[k] = make_double2(t.x, t.y);
-        }
-      }
-      if (do_b) {
-#pragma unroll
-        for (int k = 0; k < NLOAD; k++) {
-          d2v t = __builtin_nontemporal_load((const d2v *)&wp[LROW + k * 64]);
-          Wm[k] = make_double2(t.x, t.y);
-        }
-      }
-      if (RECON == 1) {
-        const int lane = c & 63;
-        if (do_f) recon_row2<1>(U, (sm[2 * pr] >> lane) & 1ull);
-        if (do_b) recon_row2<1>(Wm, (sm[2 * pr + 1] >> lane) & 1ull);
-      } else if (RECON == 2) {
-        if (do_f) recon_row2<2>(U, false);
-        if (do_b) recon_row2<2>(Wm, false);
-      }
-      const bool xf = mu == 3 && (hop == 3 ? hi3 : hi1), xb = mu == 3 && (hop == 3 ? lo3 : lo1);     // this hop leaves the slab (wavefront-uniform)
+      L.fetch(pr, do_f, do_b, U, Wm);
+      // fused: this hop leaves the slab (wavefront-uniform) and reads the neighbour's face where the neighbour wrote it
+      const bool xf = FUSED && mu == 3 && (hop == 3 ? hi3 : hi1), xb = FUSED && mu == 3 && (hop == 3 ? lo3 : lo1);
 #pragma unroll
       for (int j = 0; j < QX_MAXRHS; j++) {
         if (!act[j]) continue;
         double2 vf[3], vb[3];
         if (do_f) {
-          const double2 *src = xf ? F.gh_hi[j] : A.in[j];
+          const double2 *src = A.in[j];
+          if constexpr (FUSED) src = xf ? P.gh_hi[j] : A.in[j];
 #pragma unroll
           for (int k = 0; k < 3; k++) vf[k] = src[vec_off(pf, k)];
           mv3<false>(acc[j], U, vf);
         }
         if (do_b) {
-          const double2 *src = xb ? F.gh_lo[j] : A.in[j];
+          const double2 *src = A.in[j];
+          if constexpr (FUSED) src = xb ? P.gh_lo[j] : A.in[j];
 #pragma unroll
           for (int k = 0; k < 3; k++) vb[k] = src[vec_off(pb, k)];
           mv3<true>(acc[j], Wm, vb);
         }
       }
     };
+    // boundary blocks of the fused sweep: `crossing` false takes every hop but the t-hops that leave the slab, true exactly those
     auto edge_pairs = [&](const bool crossing) __attribute__((always_inline)) {
       if (!crossing) {
         constexpr int NSP = NDIR / 2 - NDIR / 8;
@@ -249,7 +148,7 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
         }
         if (R.cleanup) {
 #pragma unroll
-          for (int k = 0; k < 3; k++) acc[j][k] = A.out[j][vec_off(c, k)];
+          for (int k = 0; k < 3; k++) acc[j][k] = A.out[j][vec_off(c, k)];          // the raw accumulator its boundary workgroup parked here
         } else if (SECOND) {
 #pragma unroll
           for (int k = 0; k < 3; k++) {
@@ -269,7 +168,7 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
       }
     }
     if (R.bnd && !skip) {
-      fused_wait_faces(F.fs, R);
+      if constexpr (FUSED) fused_wait_faces(P.fs, R);
       if (active && !R.parked) edge_pairs(true);
     }
     if (active) {
@@ -283,8 +182,12 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
 #pragma unroll
           for (int k = 0; k < 3; k++) {
             acc[j][k].x *= sgn; acc[j][k].y *= sgn;
-            d2v t; t.x = acc[j][k].x; t.y = acc[j][k].y;
-            __builtin_nontemporal_store(t, (d2v *)&A.out[j][vec_off(c, k)]);
+            if (FUSED || A.ntstore) {
+              d2v t; t.x = acc[j][k].x; t.y = acc[j][k].y;
+              __builtin_nontemporal_store(t, (d2v *)&A.out[j][vec_off(c, k)]);
+            } else {
+              A.out[j][vec_off(c, k)] = acc[j][k];
+            }
           }
           if (SECOND) {
 #pragma unroll
@@ -294,7 +197,8 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
       }
     }
     if (SECOND && !skip && !R.parked) {
-      const int pidx = fused_partial_slot(F.fs, R, lb);
+      int pidx = blockIdx.x;               // the dispatch slot, swizzled or not
+      if constexpr (FUSED) pidx = fused_partial_slot(P.fs, R, lb);
 #pragma unroll
       for (int j = 0; j < QX_MAXRHS; j++) {
         if (!act[j]) continue;             // uniform over the grid
@@ -304,8 +208,13 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) {
     }
     if (!R.cleanup) break;
   }
-  fused_finish(F.fs, R);
+  if constexpr (FUSED) fused_finish(P.fs, R);
 }
+
+template <int NDIR, int RECON, bool SECOND, bool HALO>
+__global__ void __launch_bounds__(256) k_dslash_mrhs(MrhsArgs A) { mrhs_body<NDIR, RECON, SECOND, HALO>(A); }
+template <int NDIR, int RECON, bool SECOND>
+__global__ void __launch_bounds__(256) k_dslash_mrhs_fused(MrhsFusedArgs F) { mrhs_body<NDIR, RECON, SECOND, true>(F); }
 
 struct BatchBlas {
   double2 *x[QX_MAXRHS], *r[QX_MAXRHS], *p[QX_MAXRHS], *Ap[QX_MAXRHS];
@@ -420,8 +329,21 @@ void batch_state_free(qexhip_ctx *c) {
   c->batch = nullptr;
 }
 
+// the batch state with at least nfields work fields
+static int batch_state(qexhip_ctx *c, int nfields, BatchState **out) {
+  BatchState *B = (BatchState *)c->batch;
+  if (!B) { B = new BatchState(); c->batch = B; }
+  while ((int)B->f.size() < nfields) {
+    DevField nf;
+    CHK(field_alloc(c, nf));
+    B->f.push_back(nf);
+  }
+  *out = B;
+  return 0;
+}
+
 template <int NDIR, int RECON>
-static void launch_mrhs(qexhip_ctx *c, MrhsArgs &A, bool second, int nb, hipStream_t st) {
+static void launch_mrhs(const qexhip_ctx *c, bool second, int nb, hipStream_t st, const MrhsArgs &A) {
   if (c->g.halo) {
     if (second) hipLaunchKernelGGL((k_dslash_mrhs<NDIR, RECON, true, true>), dim3(nb), dim3(256), 0, st, A);
     else hipLaunchKernelGGL((k_dslash_mrhs<NDIR, RECON, false, true>), dim3(nb), dim3(256), 0, st, A);
@@ -430,24 +352,33 @@ static void launch_mrhs(qexhip_ctx *c, MrhsArgs &A, bool second, int nb, hipStre
     else hipLaunchKernelGGL((k_dslash_mrhs<NDIR, RECON, false, false>), dim3(nb), dim3(256), 0, st, A);
   }
 }
+template <int NDIR, int RECON>
+static void launch_mrhs(const qexhip_ctx *, bool second, int nb, hipStream_t st, const MrhsFusedArgs &F) {
+  if (second) hipLaunchKernelGGL((k_dslash_mrhs_fused<NDIR, RECON, true>), dim3(nb), dim3(256), 0, st, F);
+  else hipLaunchKernelGGL((k_dslash_mrhs_fused<NDIR, RECON, false>), dim3(nb), dim3(256), 0, st, F);
+}
+// nb workgroups of the kernel for this context's links: k_dslash_mrhs for MrhsArgs, k_dslash_mrhs_fused for MrhsFusedArgs
+template <class Args>
+static void dispatch_mrhs(qexhip_ctx *c, const Args &P, bool second, int nb, hipStream_t st) {
+  if (c->ndir == 8) {
+    if (c->recon == 1) launch_mrhs<8, 1>(c, second, nb, st, P);
+    else if (c->recon == 2) launch_mrhs<8, 2>(c, second, nb, st, P);
+    else launch_mrhs<8, 0>(c, second, nb, st, P);
+  } else {
+    if (c->recon == 1) launch_mrhs<16, 1>(c, second, nb, st, P);
+    else if (c->recon == 2) launch_mrhs<16, 2>(c, second, nb, st, P);
+    else launch_mrhs<16, 0>(c, second, nb, st, P);
+  }
+}
 // one launch over [c0, c1) (+ [d0, d1)); returns the number of workgroups = <xs, out> partials it writes from part_off on
 static int launch_range(qexhip_ctx *c, MrhsArgs &A, bool second, int c0, int c1, int d0, int d1, int part_off, hipStream_t st) {
-  A.c0 = c0; A.c1 = c1; A.d0 = d0; A.d1 = d1;
-  A.nb1 = (c1 - c0 + 255) / 256;
-  const int nb = A.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0);
+  const int nb = sweep_ranges(A.r, c0, c1, d0, d1);
+  if (!nb) return 0;
   A.part_off = part_off;
   const bool whole = (c0 == 0 && c1 == c->g.Vh && d1 <= d0);
   A.swz = (whole && c->recon != 0 && nb >= 64 && (nb & 7) == 0) ? nb : 0;     // as dslash.hip: on for compressed links
   A.ntstore = 1;
-  if (c->ndir == 8) {
-    if (c->recon == 1) launch_mrhs<8, 1>(c, A, second, nb, st);
-    else if (c->recon == 2) launch_mrhs<8, 2>(c, A, second, nb, st);
-    else launch_mrhs<8, 0>(c, A, second, nb, st);
-  } else {
-    if (c->recon == 1) launch_mrhs<16, 1>(c, A, second, nb, st);
-    else if (c->recon == 2) launch_mrhs<16, 2>(c, A, second, nb, st);
-    else launch_mrhs<16, 0>(c, A, second, nb, st);
-  }
+  dispatch_mrhs(c, A, second, nb, st);
   return nb;
 }
 // t-sharded: the faces of every system's input field travel in ONE RCCL group; either exchange-first and one launch over the
@@ -469,17 +400,13 @@ static int sweep_mrhs(qexhip_ctx *c, MrhsArgs &A, bool second, int *ndot, DevFie
     CHK(devjoin_flush(c));
     int grid;
     CHK(fused_sweep_setup(c, A.nrhs, infield, inpar, lo_end, hi_beg, &Fz.fs, Fz.gh_hi, Fz.gh_lo, &grid, ndot));
-    A.c0 = lo_end; A.c1 = hi_beg; A.d0 = 0; A.d1 = lo_end; A.nb1 = (hi_beg - lo_end + 255) / 256; A.part_off = 0; A.swz = 0; A.ntstore = 1;
+    // interior | low face; the high face is Fz.fs's.  The fused form is an overlapped one, and sweep_plan overlaps only a non-empty
+    // interior: the ranges are taken as given (no swap), as fused_sweep_setup counted them
+    if (hi_beg <= lo_end || !sweep_ranges(A.r, lo_end, hi_beg, 0, lo_end)) { qexhip_set_error("internal: fused batch sweep without an interior"); return -3; }
+    A.part_off = 0; A.swz = 0; A.ntstore = 1;
     Fz.a = A;
     ScopedTimer tm(c, "dslash_batch", c->stream);
-#define QX_MF(ND, RC) \
-    do { \
-      if (second) hipLaunchKernelGGL((k_dslash_mrhs_fused<ND, RC, true>), dim3(grid), dim3(256), 0, c->stream, Fz); \
-      else hipLaunchKernelGGL((k_dslash_mrhs_fused<ND, RC, false>), dim3(grid), dim3(256), 0, c->stream, Fz); \
-    } while (0)
-    if (c->ndir == 8) { if (c->recon == 1) QX_MF(8, 1); else if (c->recon == 2) QX_MF(8, 2); else QX_MF(8, 0); }
-    else { if (c->recon == 1) QX_MF(16, 1); else if (c->recon == 2) QX_MF(16, 2); else QX_MF(16, 0); }
-#undef QX_MF
+    dispatch_mrhs(c, Fz, second, grid, c->stream);
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -506,13 +433,8 @@ int solve_xx_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const d
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
   if (!c->W) { qexhip_set_error("staggered links not set (qexhip_stag_set_links)"); return -3; }
   for (int j = 0; j < n; j++) if (mass[j] == 0.0) { qexhip_set_error("batch solve: mass must be non-zero"); return -1; }
-  BatchState *B = (BatchState *)c->batch;
-  if (!B) { B = new BatchState(); c->batch = B; }
-  while ((int)B->f.size() < 4 * QX_MAXRHS) {
-    DevField nf;
-    CHK(field_alloc(c, nf));
-    B->f.push_back(nf);
-  }
+  BatchState *B;
+  CHK(batch_state(c, 4 * QX_MAXRHS, &B));
   if (!B->st) HIPCHK(hipMalloc((void **)&B->st, sizeof(CgScal) * QX_MAXRHS));
   if (!B->glob) { HIPCHK(hipMalloc((void **)&B->glob, sizeof(double) * 8)); HIPCHK(hipMemsetAsync(B->glob, 0, sizeof(double) * 8, c->stream)); }
   const int nbd = (g.Vh + 255) / 256 + 4;             // room for the <p,Ap> partials of a sweep per system (a split sweep rounds up per range)
@@ -552,14 +474,8 @@ int solve_xx_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const d
   L.st = B->st; L.glob = B->glob; L.ndot = multi ? -1 : (deferred ? nbd : 0);
   for (MrhsArgs *A : {&A1, &A2}) {
     A->g = g; A->st = B->st; A->nrhs = n;
-    if (c->recon) {
-      A->W = c->Wc + (size_t)(A == &A1 ? 1 - par : par) * g.ntile * c->ndir * (c->recon == 1 ? 384 : 448);
-      A->S = c->Ws + (size_t)(A == &A1 ? 1 - par : par) * g.ntile * c->ndir;
-    } else {
-      A->W = c->W + (size_t)(A == &A1 ? 1 - par : par) * g.ntile * c->ndir * 576;
-      A->S = nullptr;
-    }
     A->parity = (A == &A1) ? 1 - par : par;
+    stag_link_bases(c, A->parity, false, &A->W, &A->S);       // (lossless links: the batch reads the 18 reals kept beside them)
   }
   CgScal st[QX_MAXRHS];
   auto read_states = [&]() -> int {
@@ -636,13 +552,8 @@ int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
 static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                                  int maxits, int *iters, double *r2_final, int sloppy, int *nupdates) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
-  BatchState *B = (BatchState *)c->batch;
-  if (!B) { B = new BatchState(); c->batch = B; }
-  while ((int)B->f.size() < 7 * QX_MAXRHS) {     // 4 CG fields + r, y, d per system
-    DevField nf;
-    CHK(field_alloc(c, nf));
-    B->f.push_back(nf);
-  }
+  BatchState *B;
+  CHK(batch_state(c, 7 * QX_MAXRHS, &B));        // 4 CG fields + r, y, d per system
   Sys S[QX_MAXRHS];
   std::vector<int> active;
   for (int j = 0; j < n; j++) {
@@ -750,13 +661,8 @@ int solve_full_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b
 // the first `count` (<= 4 per system) CG work fields of the batch state, for the mixed-precision batch (which leaves the fp64 CG's idle)
 int batch_work_fields(qexhip_ctx *c, int count, DevField **out) {
   if (count < 0 || count > 4 * QX_MAXRHS) { qexhip_set_error("batch_work_fields: count"); return -1; }
-  BatchState *B = (BatchState *)c->batch;
-  if (!B) { B = new BatchState(); c->batch = B; }
-  while ((int)B->f.size() < 4 * QX_MAXRHS) {     // (callers that hold pointers into B->f have grown it past this already)
-    DevField nf;
-    CHK(field_alloc(c, nf));
-    B->f.push_back(nf);
-  }
+  BatchState *B;
+  CHK(batch_state(c, 4 * QX_MAXRHS, &B));        // (callers that hold pointers into B->f have grown it past this already)
   for (int i = 0; i < count; i++) out[i] = &B->f[i];
   return 0;
 }
@@ -764,13 +670,8 @@ int batch_work_fields(qexhip_ctx *c, int count, DevField **out) {
 // device fields for the systems' sources and solutions (slots of the batch state)
 int batch_io_fields(qexhip_ctx *c, int n, DevField **xs, DevField **bs) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
-  BatchState *B = (BatchState *)c->batch;
-  if (!B) { B = new BatchState(); c->batch = B; }
-  while ((int)B->f.size() < 9 * QX_MAXRHS) {     // 4 CG fields + r, y, d + x, b per system
-    DevField nf;
-    CHK(field_alloc(c, nf));
-    B->f.push_back(nf);
-  }
+  BatchState *B;
+  CHK(batch_state(c, 9 * QX_MAXRHS, &B));        // 4 CG fields + r, y, d + x, b per system
   for (int j = 0; j < n; j++) { xs[j] = &B->f[7 * QX_MAXRHS + 2 * j]; bs[j] = &B->f[7 * QX_MAXRHS + 2 * j + 1]; }
   return 0;
 }

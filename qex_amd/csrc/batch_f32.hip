@@ -49,9 +49,7 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_f32(MrhsF32Args A) {
   double dotv[QX_MAXRHS] = {0, 0, 0, 0};
   if (c < g.Vh) {
     const SiteXYZT s = site_coord(g, c, A.parity);
-    constexpr int NL = RECON == 1 ? 6 : 9;
-    const f4v *w = A.W + (size_t)(c >> 6) * (NDIR / 2 * NL * 64) + (c & 63);
-    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : nullptr;
+    const LinkCursorF<NDIR, RECON> L(A.W, A.S, c);
     const float sgn = SECOND ? -1.f : 1.f;
     float2 acc[QX_MAXRHS][3], xsv[QX_MAXRHS][3];
 #pragma unroll
@@ -71,16 +69,8 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_f32(MrhsF32Args A) {
       const int hop = pr >= 4 ? 3 : 1;
       const int pf = nbr_pos<false>(g, c, s, mu, hop);
       const int pb = nbr_pos<false>(g, c, s, mu, -hop);
-      f4v t[NL];
-#pragma unroll
-      for (int q = 0; q < NL; q++) t[q] = __builtin_nontemporal_load(&w[(size_t)(pr * NL + q) * 64]);
       float2 U[9], W[9];
-      unpack_pair<NL>(t, U, W);
-      if (RECON == 1) {
-        const int lane = c & 63;
-        recon_row2f(U, (sm[2 * pr] >> lane) & 1ull);
-        recon_row2f(W, (sm[2 * pr + 1] >> lane) & 1ull);
-      }
+      L.fetch(pr, U, W);
 #pragma unroll
       for (int j = 0; j < QX_MAXRHS; j++) {
         if (!act[j]) continue;
@@ -270,23 +260,6 @@ void batch_f32_state_free(qexhip_ctx *c) {
   c->batch_f32 = nullptr;
 }
 
-static int bf_field(qexhip_ctx *c, BatchF32State *S, int idx, DevFieldF **f) {
-  DevFieldF &F = S->f[idx];
-  const size_t half = (size_t)c->g.etile * 192;
-  if (F.d && F.half != half) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(F.d));
-    F.d = nullptr;
-  }
-  if (!F.d) {
-    F.half = half;
-    HIPCHK(hipMalloc((void **)&F.d, 2 * F.half * sizeof(float2)));
-    HIPCHK(hipMemsetAsync(F.d, 0, 2 * F.half * sizeof(float2), c->stream));   // padding lanes stay zero
-  }
-  *f = &F;
-  return 0;
-}
-
 // what every batched sloppy entry checks before anything is launched
 int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
@@ -321,9 +294,7 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
   const Geom &g = c->g;
   CHK(batch_sloppy_check(c, n, mass));
   int fmt = 0;
-  const void *Wv = nullptr;
-  const unsigned long long *Sv = nullptr;
-  CHK(f32_links_dev(c, &Wv, &Sv, &fmt));
+  CHK(f32_links(c, &fmt, nullptr));
   BatchF32State *S = (BatchF32State *)c->batch_f32;
   if (!S) { S = new BatchF32State(); c->batch_f32 = S; }
   if (!S->s) HIPCHK(hipMalloc((void **)&S->s, sizeof(SlpScal) * QX_MAXRHS));
@@ -340,19 +311,15 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
   DevField *w64[2 * QX_MAXRHS];
   CHK(batch_work_fields(c, 2 * QX_MAXRHS, w64));                             // r, A x per system
   const int par = par_even ? 0 : 1;
-  const int NL = fmt == 1 ? 6 : 9;
   MrhsF32Args A1, A2;
   SlpBatch L;
   memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2); memset(&L, 0, sizeof L);
   double m2[QX_MAXRHS];
   DevField *rj[QX_MAXRHS], *axj[QX_MAXRHS];
   for (int j = 0; j < n; j++) {
-    DevFieldF *rs, *ps, *aps, *xs, *t;
-    CHK(bf_field(c, S, BF_N * j + BF_R, &rs));
-    CHK(bf_field(c, S, BF_N * j + BF_P, &ps));
-    CHK(bf_field(c, S, BF_N * j + BF_AP, &aps));
-    CHK(bf_field(c, S, BF_N * j + BF_X, &xs));
-    CHK(bf_field(c, S, BF_N * j + BF_T, &t));
+    DevFieldF *const fj = &S->f[BF_N * j];
+    for (int k = 0; k < BF_N; k++) CHK(f32_field_ensure(c, fj[k]));
+    DevFieldF *rs = &fj[BF_R], *ps = &fj[BF_P], *aps = &fj[BF_AP], *xs = &fj[BF_X], *t = &fj[BF_T];
     rj[j] = w64[2 * j]; axj[j] = w64[2 * j + 1];
     m2[j] = mass[j] * mass[j];
     // exactly the start of solve_xx_sloppy_dev: x = 0, b2, r = b, x_s = 0, k_slp_init
@@ -373,8 +340,9 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
   for (MrhsF32Args *A : {&A1, &A2}) {
     const int parity = (A == &A1) ? 1 - par : par;
     A->g = g; A->st = S->s; A->nrhs = n; A->parity = parity;
-    A->W = (const f4v *)Wv + (size_t)parity * g.ntile * (c->ndir / 2) * NL * 64;
-    A->S = fmt == 1 ? Sv + (size_t)parity * g.ntile * c->ndir : nullptr;
+    const void *Wv = nullptr;
+    CHK(f32_links_dev(c, parity, &Wv, &A->S, &fmt));
+    A->W = (const f4v *)Wv;
   }
   SlpScal h[QX_MAXRHS];
   auto read_states = [&]() -> int {

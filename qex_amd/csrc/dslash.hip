@@ -8,7 +8,8 @@
 // unit-stride (x), row-stride (y), plane-stride (z) or slice-stride (t) access, all coalesced.
 // HBM-bound: 1248 B and 570 flop per site (1-hop; 960 B on the lossless 108-byte links, link_residual.h), no MFMA on purpose.
 //
-// Two kernels with disjoint roles (round 6; rounds 4-5 had one kernel with seven template parameters):
+// Two kernels with disjoint roles (round 6; rounds 4-5 had one kernel with seven template parameters) around one dslash_body; the link
+// fetch is LinkCursor's (dslash_core.h), the workgroup -> site mapping sweep_site's (site_index.h), shared with the batched and fp32 sweeps:
 //   k_dslash<NDIR, HALO, INIT, DOT, RECON>     every sweep that reads its t-neighbours from the FIELD: the whole lattice on one GPU, and on a
 //                                              t-sharded slab the launches around an exchange into the ghost tiles (RCCL, or the peer
 //                                              transport's unpacking exchange): one launch behind it, or interior | both faces
@@ -37,8 +38,8 @@ struct DslashArgs {
   double ca, cb;
   double sgn;            // +1 (stagDP / stagD2) or -1 (stagDM)
   double post;           // final scale, the `r := (0.5*sc)*r` of stagD (stagD.nim:409)
-  int parity, c0, c1;    // first site range [c0,c1)
-  int d0, d1, nb1;       // second range [d0,d1) handled by workgroups >= nb1 (both t-faces in one launch)
+  int parity;
+  SweepRanges r;         // [c0,c1), and [d0,d1) for workgroups >= nb1 (both t-faces in one launch; fused: interior, low face)
   const double2 *gh_hi, *gh_lo;   // fused: where ghost POSITIONS are read from: the transport's receive arena (pre-offset: gh[vec_off(pos, k)])
   double *partials;
   const int *done;
@@ -49,7 +50,8 @@ struct DslashArgs {
 
 #include "dslash_core.h"
 
-// The fused sweep's workgroup roles (push | interior | boundary | cleanup) are fused_sweep.h's; this is only the per-site arithmetic.
+// The fused sweep's workgroup roles (push | interior | boundary | cleanup) are fused_sweep.h's, the site ranges site_index.h's
+// (sweep_site), the link fetch dslash_core.h's (LinkCursor); this is only the per-site arithmetic.
 template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON, bool FUSED>
 __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
   const bool skip = A.done && *A.done;
@@ -58,7 +60,7 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
   if (FUSED && fused_push(A.fs, skip)) return;
   FusedRole R;
   R.bid = blockIdx.x; R.cleanup = false; R.bnd = false; R.parked = false;
-  if (FUSED) fused_enter(A.fs, A.nb1, R);
+  if (FUSED) fused_enter(A.fs, A.r.nb1, R);
   const bool cleanup = FUSED && R.cleanup;
   for (;;) {                               // one pass; a cleanup workgroup takes every fz.ncl-th parked block
     int lb = R.bid;                        // logical workgroup: [0, nb1) first range, [nb1, nb2) second, [nb2, ..) third
@@ -70,10 +72,9 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       int per = A.swz >> 3;
       lb = (lb & 7) * per + (lb >> 3);
     }
-    int c = A.c0 + lb * 256 + threadIdx.x;
-    int clim = A.c1;
-    if (FUSED) c = fused_site(A.fs, R, lb, A.c0, A.c1, A.d0, A.d1, clim);
-    else if (lb >= A.nb1) { c = A.d0 + (lb - A.nb1) * 256 + threadIdx.x; clim = A.d1; }
+    int c, clim;
+    if (FUSED) c = fused_site(A.fs, R, lb, A.r, clim);
+    else sweep_site(A.r, lb, c, clim);
     double dotv = 0;
     const bool active = c < clim && !skip;
     const Geom &g = A.g;
@@ -82,10 +83,7 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
     const int tu = FUSED ? __builtin_amdgcn_readfirstlane(s.t) : 0;
     double2 acc[3];
     double2 xsv[3];
-    constexpr int NLOAD = (RECON == 1 || RECON == 3) ? 6 : (RECON == 2 ? 7 : 9);
-    constexpr int LROW = RECON == 3 ? LR_ROW : NLOAD * 64;      // double2 per (tile, direction)
-    const double2 *w = A.W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63);
-    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : (RECON == 3 ? A.S + (size_t)(c >> 6) * NDIR * 2 : nullptr);
+    const LinkCursor<NDIR, RECON> L(A.W, A.S, c);
     // fused: hops that leave the slab read the neighbours' faces where the neighbours WROTE them -- the transport's receive arena --
     // instead of the field's ghost tiles: which base a t-hop reads from is wavefront-uniform, four scalar selects, nothing per lane
     const double2 *in_f1 = A.in, *in_b1 = A.in, *in_f3 = A.in, *in_b3 = A.in;
@@ -102,11 +100,12 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       const int hop = pr >= 4 ? 3 : 1;
       const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
       const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
-      const double2 *wp = w + (size_t)pr * (2 * LROW);
       double2 U[9], W[9], vf[3], vb[3];
-      // links are read exactly once per sweep: stream them past the caches (non-temporal), which
-      // leaves L2 / Infinity Cache to the 8x re-read neighbour vectors.  Measured on MI355X,
-      // 32^4: 120 us -> 108 us per sweep (scratch/tune_dslash.py, profiles/r01_tune_dslash.log).
+      // L.fetch(pr, do_f, do_b, U, W), spelled out: through the call the compiler orders the loop differently (every load first, the
+      // rebuild behind the neighbour loads) and the RECON 1 / 2 instantiations of k_dslash move by -14 .. +6 VGPRs
+      // (profiles/sweep_refactor_resources.txt).  The rows, masks and constants are the cursor's; keep the two texts the same.
+      constexpr int NLOAD = LinkFormat<RECON>::NLOAD, LROW = LinkFormat<RECON>::LROW;
+      const double2 *wp = L.w + (size_t)pr * (2 * LROW);
       if (do_f) {
 #pragma unroll
         for (int k = 0; k < NLOAD; k++) {
@@ -122,15 +121,12 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
         }
       }
       if (RECON == 1) {
-        const int lane = c & 63;
-        if (do_f) recon_row2<1>(U, (sm[2 * pr] >> lane) & 1ull);
-        if (do_b) recon_row2<1>(W, (sm[2 * pr + 1] >> lane) & 1ull);
+        if (do_f) recon_row2<1>(U, (L.sm[2 * pr] >> L.lane) & 1ull);
+        if (do_b) recon_row2<1>(W, (L.sm[2 * pr + 1] >> L.lane) & 1ull);
       } else if (RECON == 3) {
-        // row 2 = rebuild + int16 residuals (link_residual.h), bit for bit the 18-real link; an escaped lane reads it from W
-        const int lane = c & 63;
-        const size_t fr = ((size_t)(c >> 6) * NDIR + 2 * pr) * 576 + lane;
-        if (do_f) recon_row2_res(U, wp - lane, sm + 4 * pr, A.S - 2, fr, lane);
-        if (do_b) recon_row2_res(W, wp - lane + LROW, sm + 4 * pr + 2, A.S - 2, fr + 576, lane);
+        const size_t fr = ((size_t)L.tile * NDIR + 2 * pr) * 576 + L.lane;
+        if (do_f) recon_row2_res(U, wp - L.lane, L.sm + 4 * pr, L.hdr, fr, L.lane);
+        if (do_b) recon_row2_res(W, wp - L.lane + LROW, L.sm + 4 * pr + 2, L.hdr, fr + 576, L.lane);
       } else if (RECON == 2) {
         if (do_f) recon_row2<2>(U, false);
         if (do_b) recon_row2<2>(W, false);
@@ -271,15 +267,12 @@ static int launch(qexhip_ctx *c, DslashArgs &A, int c0, int c1, bool init, bool 
                   int d0 = 0, int d1 = 0, const char *tname = "dslash", hipStream_t st = nullptr, int fused_grid = 0) {
   if (!st) st = c->stream;
   const bool fused = fused_grid > 0;
-  if (c1 <= c0 && d1 <= d0) return 0;
-  if (c1 <= c0) { c0 = d0; c1 = d1; d0 = d1 = 0; }
-  A.c0 = c0; A.c1 = c1; A.d0 = d0; A.d1 = d1;
-  A.nb1 = (c1 - c0 + 255) / 256;
-  const int nb = A.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0);
+  const int nb = sweep_ranges(A.r, c0, c1, d0, d1);
+  if (!nb) return 0;
   // XCD swizzle: measured on for compressed links, off for 18-real links (profiles/r01_tune_dslash.log); output stores are
   // non-temporal (the result is read by the NEXT kernel, after 0.6 GB of links went through the caches).  The lossless format
   // takes it in the one-launch kernel only: the fused kernel's dot partials go by dispatch slot, which the remap would reorder
-  const int nsw = fused ? A.nb1 : nb;          // (the fused launch remaps its interior workgroups only)
+  const int nsw = fused ? A.r.nb1 : nb;          // (the fused launch remaps its interior workgroups only)
   A.swz = ((c->recon != 0 || (c->lres && !fused)) && nsw >= 64 && (nsw & 7) == 0) ? nsw : 0;
   A.ntstore = 1;
   double *psave = A.partials;
@@ -488,22 +481,30 @@ int sweep_autotune(qexhip_ctx *c) {
   return 0;
 }
 
+// The links of output parity `parity` as a sweep kernel takes them: W = the parity's first (tile, direction) row in the format
+// set_links chose (rows 0,1 (+ det) in Wc with recon 1 / 2; the lossless rows where `lossless` -- c->lres for the single-system
+// sweep, whose kernel reads them; false for the batch, which reads the 18 reals beside them; else the 18 reals), S = its masks
+void stag_link_bases(const qexhip_ctx *c, int parity, bool lossless, const double2 **W, const unsigned long long **S) {
+  const size_t rows = (size_t)parity * c->g.ntile * c->ndir;         // (tile, direction) rows before this parity
+  if (c->recon) {
+    *W = c->Wc + rows * (c->recon == 1 ? LinkFormat<1>::LROW : LinkFormat<2>::LROW);
+    *S = c->Ws + rows;
+  } else if (lossless) {
+    *W = c->Wc + rows * LinkFormat<3>::LROW;
+    *S = c->Wm + (size_t)parity * (2 + c->g.ntile * c->ndir * 2) + 2;
+  } else {
+    *W = c->W + rows * LinkFormat<0>::LROW;
+    *S = nullptr;
+  }
+}
+
 int dslash_sweep(qexhip_ctx *c, DevField &out, DevField &in, int parity, const DslashOpts &o) {
   const Geom &g = c->g;
   if (!c->W) { qexhip_set_error("staggered links not set (qexhip_stag_set_links)"); return -3; }
   DslashArgs A;
   memset(&A, 0, sizeof A);
   A.g = g;
-  if (c->recon) {
-    A.W = c->Wc + (size_t)parity * g.ntile * c->ndir * (c->recon == 1 ? 384 : 448);
-    A.S = c->Ws + (size_t)parity * g.ntile * c->ndir;
-  } else if (c->lres) {
-    A.W = c->Wc + (size_t)parity * g.ntile * c->ndir * LR_ROW;
-    A.S = c->Wm + (size_t)parity * (2 + g.ntile * c->ndir * 2) + 2;
-  } else {
-    A.W = c->W + (size_t)parity * g.ntile * c->ndir * 576;
-    A.S = nullptr;
-  }
+  stag_link_bases(c, parity, c->lres != 0, &A.W, &A.S);
   A.in = in.par(1 - parity);
   A.out = out.par(parity);
   A.rin = o.rin ? o.rin->par(parity) : nullptr;

@@ -1,4 +1,5 @@
-// dslash_core.h -- device pieces shared by the Dslash kernels (dslash.hip, batch.hip)
+// dslash_core.h -- device pieces shared by the fp64 Dslash kernels (dslash.hip, batch.hip) and meson.hip: the matrix-vector
+// product, the row-2 rebuilds of the compressed link formats, and LinkCursor -- the ONE place a sweep fetches a hop pair's links
 #pragma once
 #include <hip/hip_runtime.h>
 #include "link_residual.h"
@@ -44,8 +45,7 @@ __device__ __forceinline__ void recon_row2(double2 U[9], bool neg) {
     ry -= U[a].x * U[3 + b].y;
     ry -= U[a].y * U[3 + b].x;
     if (FMT == 1) r2[k] = make_double2(neg ? -rx : rx, neg ? -ry : ry);
-    // explicit fma: "a*b - c*d" leaves the compiler two ways to contract, and it chose differently in different kernels -- the
-    // single-system and the lock-step batched sweep must reconstruct the same bits (tests/test_gpu_batch.py)
+    // explicit fma: "a*b - c*d" leaves the compiler two ways to contract, and it chose differently in different kernels
     else r2[k] = make_double2(fma(ph.x, rx, -(ph.y * ry)), fma(ph.x, ry, ph.y * rx));
   }
 #pragma unroll
@@ -70,13 +70,71 @@ __device__ __forceinline__ void recon_row2_res(double2 U[9], const double2 *row,
   for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
 }
 
-// one link of the operator's storage as the sweep reads it: `w` points at this lane's element of the (tile, dir) row of W
+// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3: lossless (link_residual.h)
+template <int RECON> struct LinkFormat {
+  static constexpr int NLOAD = (RECON == 1 || RECON == 3) ? 6 : (RECON == 2 ? 7 : 9);      // double2 loaded per lane and link
+  static constexpr int LROW = RECON == 3 ? LR_ROW : NLOAD * 64;                             // double2 per (tile, direction) row
+};
+
+// The links of one output site as a sweep reads them: built once per site from the parity's link base W, its mask base S (RECON 1:
+// sign masks [tile][dir], bit = lane; 3: [tile][dir][sign, escape], S[-2] = this parity's 18-real W) and the site c.
+// fetch(pr, ..) gives the forward link of hop pair pr (direction 2 pr; fat links: pairs 0..3, 3-hop links: 4..7) in U and the backward
+// link (direction 2 pr + 1) in Wb, rebuilt to 3x3.  The batched sweep (batch.hip) calls it; dslash_body (dslash.hip) takes the cursor's
+// rows and masks but spells the same statements out in place, because through the call its RECON 1 / 2 kernels change registers
+// (see there).  The two must reconstruct the same bits (tests/test_gpu_batch.py): change them together.
+template <int NDIR, int RECON>
+struct LinkCursor {
+  static constexpr int NLOAD = LinkFormat<RECON>::NLOAD, LROW = LinkFormat<RECON>::LROW;
+  const double2 *w;                  // this lane's element of the site's first (tile, direction) row
+  const unsigned long long *sm;      // the tile's mask row (RECON 1, 3)
+  const unsigned long long *hdr;     // RECON 3: header of the parity's mask block
+  int tile, lane;
+  __device__ __forceinline__ LinkCursor(const double2 *W, const unsigned long long *S, const int c)
+      : w(W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63)),
+        sm(RECON == 1 ? S + (size_t)(c >> 6) * NDIR : (RECON == 3 ? S + (size_t)(c >> 6) * NDIR * 2 : nullptr)),
+        hdr(RECON == 3 ? S - 2 : nullptr), tile(c >> 6), lane(c & 63) {}
+  // do_f / do_b: which of the pair's two links this call takes (literally true on the fast paths)
+  __device__ __forceinline__ void fetch(const int pr, const bool do_f, const bool do_b, double2 U[9], double2 Wb[9]) const {
+    const double2 *wp = w + (size_t)pr * (2 * LROW);
+    // links are read exactly once per sweep: stream them past the caches (non-temporal), which
+    // leaves L2 / Infinity Cache to the 8x re-read neighbour vectors.  Measured on MI355X,
+    // 32^4: 120 us -> 108 us per sweep (scratch/tune_dslash.py, profiles/r01_tune_dslash.log).
+    if (do_f) {
+#pragma unroll
+      for (int k = 0; k < NLOAD; k++) {
+        d2v t = __builtin_nontemporal_load((const d2v *)&wp[k * 64]);
+        U[k] = make_double2(t.x, t.y);
+      }
+    }
+    if (do_b) {
+#pragma unroll
+      for (int k = 0; k < NLOAD; k++) {
+        d2v t = __builtin_nontemporal_load((const d2v *)&wp[LROW + k * 64]);
+        Wb[k] = make_double2(t.x, t.y);
+      }
+    }
+    if (RECON == 1) {
+      if (do_f) recon_row2<1>(U, (sm[2 * pr] >> lane) & 1ull);
+      if (do_b) recon_row2<1>(Wb, (sm[2 * pr + 1] >> lane) & 1ull);
+    } else if (RECON == 3) {
+      // row 2 = rebuild + int16 residuals (link_residual.h), bit for bit the 18-real link; an escaped lane reads it from W
+      const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
+      if (do_f) recon_row2_res(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
+      if (do_b) recon_row2_res(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
+    } else if (RECON == 2) {
+      if (do_f) recon_row2<2>(U, false);
+      if (do_b) recon_row2<2>(Wb, false);
+    }
+  }
+};
+
+// one link of the operator's storage outside a sweep (meson.hip): `w` points at this lane's element of the (tile, dir) row of W
 // (RECON 0: 9 double2) or Wc (RECON 1: rows 0,1; RECON 2: rows 0,1 + det), `sm` at the row's sign mask (RECON 1 only)
 template <int RECON>
 __device__ __forceinline__ void load_link(double2 U[9], const double2 *w, const unsigned long long *sm, int lane) {
-  constexpr int NLOAD = RECON == 1 ? 6 : (RECON == 2 ? 7 : 9);
+  static_assert(RECON != 3, "the lossless rows are read through LinkCursor only");
 #pragma unroll
-  for (int k = 0; k < NLOAD; k++) U[k] = w[k * 64];
+  for (int k = 0; k < LinkFormat<RECON>::NLOAD; k++) U[k] = w[k * 64];
   if (RECON == 1) recon_row2<1>(U, (*sm >> lane) & 1ull);
   else if (RECON == 2) recon_row2<2>(U, false);
 }

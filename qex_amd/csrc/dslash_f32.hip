@@ -164,18 +164,21 @@ int f32_links(qexhip_ctx *c, int *fmt_out, double *dev_out) {
   return 0;
 }
 
-int f32_links_dev(qexhip_ctx *c, const void **W, const unsigned long long **Sm, int *fmt) {
-  CHK(f32_links(c, fmt, nullptr));
+// What a sweep kernel takes for output parity `parity` from the current copy (f32_links has run): the parity's first pair row, its sign
+// masks (format 1, else null), the format.  Launches nothing and rebuilds nothing.
+int f32_links_dev(qexhip_ctx *c, int parity, const void **W, const unsigned long long **Sm, int *fmt) {
   F32State *S = st_of(c);
-  *W = S->W; *Sm = S->S;
+  if (S->fmt < 0) { qexhip_set_error("internal: fp32 links not built (f32_links)"); return -3; }
+  *fmt = S->fmt;
+  const size_t rows = (size_t)parity * c->g.ntile * c->ndir;       // (tile, direction) rows before this parity; a pair holds two
+  *W = S->W + rows / 2 * ((S->fmt == 1 ? 6 : 9) * 64);
+  *Sm = S->fmt == 1 ? S->S + rows : nullptr;
   return 0;
 }
 
 // etile = ntile without a halo: the ghost zones cost nothing on a one-rank context that has none.  A field allocated before the
 // geometry changed (qexhip_comm_force_halo) is allocated again.
-int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {
-  F32State *S = st_of(c);
-  DevFieldF &F = S->f[slot];
+int f32_field_ensure(qexhip_ctx *c, DevFieldF &F) {
   const size_t half = (size_t)c->g.etile * 192;
   if (F.d && F.half != half) {
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -187,8 +190,11 @@ int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {
     HIPCHK(hipMalloc((void **)&F.d, 2 * F.half * sizeof(float2)));
     HIPCHK(hipMemsetAsync(F.d, 0, 2 * F.half * sizeof(float2), c->stream));   // padding lanes stay zero
   }
-  *f = &F;
   return 0;
+}
+int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {
+  *f = &st_of(c)->f[slot];
+  return f32_field_ensure(c, **f);
 }
 
 // ---- fp32 Dslash sweep --------------------------------------------------------------------------------------------
@@ -213,7 +219,7 @@ struct DslashF32Args {
 };
 struct DslashF32HaloArgs {         // (a type of its own: the HALO = false kernels keep their kernel arguments and code)
   DslashF32Args a;
-  int c0, c1, d0, d1, nb1;
+  SweepRanges r;
 };
 template <bool HALO> struct F32SweepArgs { using T = DslashF32Args; };
 template <> struct F32SweepArgs<true> { using T = DslashF32HaloArgs; };
@@ -225,20 +231,13 @@ __global__ void __launch_bounds__(256) k_dslash_f32(typename F32SweepArgs<HALO>:
   const DslashF32Args &A = f32_args(P);
   if (A.done && *A.done) return;
   const Geom &g = A.g;
-  int c = blockIdx.x * 256 + threadIdx.x;
-  bool active = c < g.Vh;
-  if constexpr (HALO) {
-    int clim = P.c1;
-    if ((int)blockIdx.x < P.nb1) c = P.c0 + blockIdx.x * 256 + threadIdx.x;
-    else { c = P.d0 + (blockIdx.x - P.nb1) * 256 + threadIdx.x; clim = P.d1; }
-    active = c < clim;
-  }
+  int c = blockIdx.x * 256 + threadIdx.x, clim = g.Vh;
+  if constexpr (HALO) sweep_site(P.r, blockIdx.x, c, clim);
+  const bool active = c < clim;
   double dotv = 0;
   if (active) {
     const SiteXYZT s = site_coord(g, c, A.parity);
-    constexpr int NL = RECON == 1 ? 6 : 9;
-    const f4v *w = A.W + (size_t)(c >> 6) * (NDIR / 2 * NL * 64) + (c & 63);
-    const unsigned long long *sm = RECON == 1 ? A.S + (size_t)(c >> 6) * NDIR : nullptr;
+    const LinkCursorF<NDIR, RECON> L(A.W, A.S, c);
     float2 acc[3], xsv[3];
     if (INIT || DOT) {
 #pragma unroll
@@ -253,16 +252,8 @@ __global__ void __launch_bounds__(256) k_dslash_f32(typename F32SweepArgs<HALO>:
       const int hop = pr >= 4 ? 3 : 1;
       const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
       const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
-      f4v t[NL];
-#pragma unroll
-      for (int q = 0; q < NL; q++) t[q] = __builtin_nontemporal_load(&w[(size_t)(pr * NL + q) * 64]);
       float2 U[9], W[9], vf[3], vb[3];
-      unpack_pair<NL>(t, U, W);
-      if (RECON == 1) {
-        const int lane = c & 63;
-        recon_row2f(U, (sm[2 * pr] >> lane) & 1ull);
-        recon_row2f(W, (sm[2 * pr + 1] >> lane) & 1ull);
-      }
+      L.fetch(pr, U, W);
 #pragma unroll
       for (int k = 0; k < 3; k++) { vf[k] = A.in[vec_off(pf, k)]; vb[k] = A.in[vec_off(pb, k)]; }
       mv3f<false>(acc, U, vf);
@@ -288,15 +279,13 @@ __global__ void __launch_bounds__(256) k_dslash_f32(typename F32SweepArgs<HALO>:
 // one launch of the halo kernel over [c0,c1) (+ [d0,d1) behind it) on stream st, dot partials from A.partials + part_off
 static int launch_f32_halo(qexhip_ctx *c, int fmt, const DslashF32Args &A, int c0, int c1, int d0, int d1, bool init, bool dot,
                            int part_off, const char *tname, hipStream_t st) {
-  if (c1 <= c0 && d1 <= d0) return 0;
-  if (c1 <= c0) { c0 = d0; c1 = d1; d0 = d1 = 0; }
   DslashF32HaloArgs P;
   memset(&P, 0, sizeof P);
+  const int nb = sweep_ranges(P.r, c0, c1, d0, d1);
+  if (!nb) return 0;
   P.a = A;
   P.a.partials = A.partials + part_off;
-  P.c0 = c0; P.c1 = c1; P.d0 = d0; P.d1 = d1;
-  P.nb1 = (c1 - c0 + 255) / 256;
-  const dim3 grid(P.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0)), block(256);
+  const dim3 grid(nb), block(256);
   ScopedTimer tm(c, tname, st);
 #define QX_F32H(ND, R)                                                                                       \
   do {                                                                                                       \
@@ -319,14 +308,14 @@ static int launch_f32_halo(qexhip_ctx *c, int fmt, const DslashF32Args &A, int c
 // stream is comm_allreduce_parts (slp_update), which takes the join of a split sweep with it where the mailboxes carry the sum.
 static int sweep_f32(qexhip_ctx *c, DevFieldF &out, DevFieldF &in, int parity, const DevFieldF *xs, double cb, bool neg,
                      bool dot, const int *done, int *nparts) {
-  F32State *S = st_of(c);
   const Geom &g = c->g;
-  const int NL = S->fmt == 1 ? 6 : 9;
   DslashF32Args A;
   memset(&A, 0, sizeof A);
   A.g = g;
-  A.W = S->W + (size_t)parity * g.ntile * (c->ndir / 2) * NL * 64;
-  A.S = S->fmt == 1 ? S->S + (size_t)parity * g.ntile * c->ndir : nullptr;
+  int fmt = 0;
+  const void *Wv = nullptr;
+  CHK(f32_links_dev(c, parity, &Wv, &A.S, &fmt));
+  A.W = (const f4v *)Wv;
   A.in = in.par(1 - parity);
   A.out = out.par(parity);
   A.xs = xs ? xs->par(parity) : nullptr;
@@ -343,15 +332,15 @@ static int sweep_f32(qexhip_ctx *c, DevFieldF &out, DevFieldF &in, int parity, c
     CHK(devjoin_flush(c));
     if (!overlap) {
       CHK(comm_halo_exchange_f32(c, in, 1 - parity, 0));
-      CHK(launch_f32_halo(c, S->fmt, A, 0, g.Vh, 0, 0, init, dot, 0, "dslash_f32", c->stream));
+      CHK(launch_f32_halo(c, fmt, A, 0, g.Vh, 0, 0, init, dot, 0, "dslash_f32", c->stream));
       *nparts = (g.Vh + 255) / 256;
     } else {
       // split by sites (also where sweep_form(c, overlap) == 2: no fused fp32 sweep yet)
       const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
       HIPCHK(hipEventRecord(c->ev_ready, c->stream));
       CHK(comm_halo_exchange_f32(c, in, 1 - parity, 1));
-      CHK(launch_f32_halo(c, S->fmt, A, lo_end, hi_beg, 0, 0, init, dot, 0, "dslash_f32", c->stream));
-      CHK(launch_f32_halo(c, S->fmt, A, 0, lo_end, hi_beg, g.Vh, init, dot, nb_int, "dslash_f32_bnd", c->cstream));
+      CHK(launch_f32_halo(c, fmt, A, lo_end, hi_beg, 0, 0, init, dot, 0, "dslash_f32", c->stream));
+      CHK(launch_f32_halo(c, fmt, A, 0, lo_end, hi_beg, g.Vh, init, dot, nb_int, "dslash_f32_bnd", c->cstream));
       CHK(devjoin_signal(c, c->cstream));
       if (dot && c->peer) CHK(devjoin_defer(c));
       else CHK(devjoin_wait(c, c->stream, c->cstream));
@@ -368,8 +357,8 @@ static int sweep_f32(qexhip_ctx *c, DevFieldF &out, DevFieldF &in, int parity, c
     else if (dot) hipLaunchKernelGGL((k_dslash_f32<ND, false, false, true, R>), grid, block, 0, c->stream, A);     \
     else hipLaunchKernelGGL((k_dslash_f32<ND, false, false, false, R>), grid, block, 0, c->stream, A);             \
   } while (0)
-  if (c->ndir == 8) { if (S->fmt == 1) QX_F32(8, 1); else QX_F32(8, 0); }
-  else { if (S->fmt == 1) QX_F32(16, 1); else QX_F32(16, 0); }
+  if (c->ndir == 8) { if (fmt == 1) QX_F32(8, 1); else QX_F32(8, 0); }
+  else { if (fmt == 1) QX_F32(16, 1); else QX_F32(16, 0); }
 #undef QX_F32
   HIPCHK(hipGetLastError());
   *nparts = (g.Vh + 255) / 256;

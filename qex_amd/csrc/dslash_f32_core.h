@@ -1,5 +1,6 @@
-// dslash_f32_core.h -- device pieces of the single-precision Dslash sweep (dslash_f32.hip).  New fp32 overloads only: the fp64
-// pieces in dslash_core.h stay as they are.
+// dslash_f32_core.h -- device pieces of the single-precision Dslash sweeps (dslash_f32.hip, batch_f32.hip): the matrix-vector product,
+// the row-2 rebuild of the sign format, and LinkCursorF -- the ONE place an fp32 sweep fetches a hop pair's links.  fp32 counterparts
+// only: the fp64 pieces are dslash_core.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,3 +58,27 @@ __device__ __forceinline__ void unpack_pair(const f4v t[NL], float2 U[9], float2
     if (q < n) U[q] = e; else W[q - n] = e;
   }
 }
+
+// The fp32 links of one output site as a sweep reads them (dslash_core.h's LinkCursor for the fp32 copy): built once per site from
+// the parity's link base W ([tile][pair][NL][64] float4), its sign masks S ([tile][dir], bit = lane; RECON 1 only) and the site c.
+// fetch(pr, ..): the NL float4 of hop pair pr, streamed non-temporally like the fp64 links, as the forward link U and the backward
+// link Wb, rebuilt to 3x3.  The single-system and the lock-step batched fp32 sweep both go through here.
+template <int NDIR, int RECON>
+struct LinkCursorF {
+  static constexpr int NL = RECON == 1 ? 6 : 9;      // float4 per lane and pair
+  const f4v *w;                      // this lane's element of the site's first pair
+  const unsigned long long *sm;      // the tile's sign-mask row (RECON 1)
+  int lane;
+  __device__ __forceinline__ LinkCursorF(const f4v *W, const unsigned long long *S, const int c)
+      : w(W + (size_t)(c >> 6) * (NDIR / 2 * NL * 64) + (c & 63)), sm(RECON == 1 ? S + (size_t)(c >> 6) * NDIR : nullptr), lane(c & 63) {}
+  __device__ __forceinline__ void fetch(const int pr, float2 U[9], float2 Wb[9]) const {
+    f4v t[NL];
+#pragma unroll
+    for (int q = 0; q < NL; q++) t[q] = __builtin_nontemporal_load(&w[(size_t)(pr * NL + q) * 64]);
+    unpack_pair<NL>(t, U, Wb);
+    if (RECON == 1) {
+      recon_row2f(U, (sm[2 * pr] >> lane) & 1ull);
+      recon_row2f(Wb, (sm[2 * pr + 1] >> lane) & 1ull);
+    }
+  }
+};

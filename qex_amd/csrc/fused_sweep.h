@@ -20,6 +20,7 @@
 // fused_next_block, fused_site, fused_wait_faces (boundary blocks) and fused_partial_slot, and fused_finish at the end.
 #pragma once
 #include "peer_device.h"
+#include "site_index.h"
 
 // What a fused launch carries beside its kernel's own arguments (the ghost base pointers stay with the kernel: one pair per system).
 // Site ranges: interior [c0,c1) for logical workgroups [0, nb1), low face [d0,d1) from nb1, high face [e0,e1) from nb2.
@@ -100,12 +101,11 @@ __device__ __forceinline__ bool fused_next_block(const FusedSweep &F, FusedRole 
 }
 
 // this lane's site of logical workgroup lb, and the end of its range
-__device__ __forceinline__ int fused_site(const FusedSweep &F, const FusedRole &R, const int lb, const int c0, const int c1,
-                                          const int d0, const int d1, int &clim) {
-  int c = c0 + lb * 256 + threadIdx.x;
-  clim = c1;
+__device__ __forceinline__ int fused_site(const FusedSweep &F, const FusedRole &R, const int lb, const SweepRanges &r, int &clim) {
+  int c = r.c0 + lb * 256 + threadIdx.x;
+  clim = r.c1;
   if (R.bnd) {
-    c = d0 + (lb - R.nb1) * 256 + threadIdx.x; clim = d1;
+    c = r.d0 + (lb - R.nb1) * 256 + threadIdx.x; clim = r.d1;
     if (lb >= F.nb2) { c = F.e0 + (lb - F.nb2) * 256 + threadIdx.x; clim = F.e1; }
   }
   return c;

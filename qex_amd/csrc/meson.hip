@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_sym_shift(Geom g, const double2 *W, con
   if (i >= 2 * g.Vh) return;
   const int p = i >= g.Vh, c = i - p * g.Vh;
   const SiteXYZT s = site_coord(g, c, p);
-  constexpr int LROW = (RECON == 1 ? 6 : (RECON == 2 ? 7 : 9)) * 64;   // double2 per (tile, direction)
+  constexpr int LROW = LinkFormat<RECON>::LROW;   // double2 per (tile, direction)
   const size_t row = ((size_t)p * g.ntile + (c >> 6)) * ndir + 2 * mu;  // (parity, tile, dir 2mu)
   const int lane = c & 63;
   const double2 *in = p ? x0 : x1;

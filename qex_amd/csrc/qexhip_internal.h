@@ -329,6 +329,7 @@ struct DslashOpts {
                                    // sites leaves its join from the comm stream to that kernel's prologue where the mailboxes carry the sum
 };
 int dslash_sweep(qexhip_ctx *c, DevField &out, DevField &in, int parity, const DslashOpts &o);
+void stag_link_bases(const qexhip_ctx *c, int parity, bool lossless, const double2 **W, const unsigned long long **S);   // a parity's link and mask base
 int sweep_autotune(qexhip_ctx *c);      // measure the sweep's forms once per operator shape (collective)
 void sweep_plan(const qexhip_ctx *c, int *lo_end, int *hi_beg, int *overlap);   // boundary / interior ranges and the overlap decision
 int sweep_form(const qexhip_ctx *c, int overlap);                              // 2 fused / 0 by sites: what an overlapped sweep runs as
@@ -338,8 +339,9 @@ double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs = 1
 enum { F32_T = 0, F32_R, F32_P, F32_AP, F32_X, F32_IN, F32_NF };   // fp32 work fields
 #define SLP_DELTA 0.1                                    // reliable-update delta (QEX's reliable_delta, qudaSet.nim:63)
 int f32_links(qexhip_ctx *c, int *fmt, double *dev);     // the fp32 copy of the links, rebuilt when links_gen moved
-int f32_links_dev(qexhip_ctx *c, const void **W, const unsigned long long **S, int *fmt);   // f32_links + the copy's device pointers (W: float4)
+int f32_links_dev(qexhip_ctx *c, int parity, const void **W, const unsigned long long **S, int *fmt);   // behind f32_links: the copy's bases for one output parity (W: float4); pure accessor
 int f32_field(qexhip_ctx *c, int slot, DevFieldF **f);
+int f32_field_ensure(qexhip_ctx *c, DevFieldF &F);       // (re)allocates F, zeroed, at the current geometry's size
 int f32_op_xx(qexhip_ctx *c, DevFieldF &r, DevFieldF &x, double m2, int par_even, int dot, const int *done, int *nparts);
 int f32_from_f64(qexhip_ctx *c, DevFieldF &y, const DevField &x, int parity, double a);              // y = f32(a x)
 int f32_to_f64(qexhip_ctx *c, DevField &y, const DevFieldF &x, int parity, double a, int accumulate);  // y (+)= a x

@@ -1,4 +1,4 @@
-// site_index.h -- checkerboard site <-> coordinate arithmetic shared by all kernels.
+// site_index.h -- checkerboard site <-> coordinate arithmetic shared by all kernels, and which sites a sweep's workgroup owns.
 //
 // Index convention = QEX V=1 layout (src/layout/qlayout.nim:110-131): lex index with x fastest,
 // c = lex/2 within a parity, parity = (x+y+z+t)&1.  Neighbour sense follows the shifts:
@@ -48,4 +48,24 @@ __host__ __device__ __forceinline__ int nbr_pos(const Geom &g, int c, const Site
       return c + (wrap(tn, g.X[3]) - s.t) * g.F;
     }
   }
+}
+
+// The sites of one sweep launch, 256 per workgroup: [c0, c1) for the logical workgroups below nb1, [d0, d1) for the rest (both t-faces of
+// a slab in one launch).  The fused sweep's third range and its boundary roles are fused_sweep.h's (fused_site), over the same numbers.
+struct SweepRanges { int c0, c1, d0, d1, nb1; };
+
+// host: fills r; an empty first range gives its place to the second.  Returns the number of workgroups, 0 when there is nothing to do
+inline int sweep_ranges(SweepRanges &r, int c0, int c1, int d0, int d1) {
+  if (c1 <= c0) { c0 = d0; c1 = d1; d0 = d1 = 0; }
+  if (c1 <= c0) return 0;
+  r.c0 = c0; r.c1 = c1; r.d0 = d0; r.d1 = d1;
+  r.nb1 = (c1 - c0 + 255) / 256;
+  return r.nb1 + (d1 > d0 ? (d1 - d0 + 255) / 256 : 0);
+}
+
+// device: this lane's site c of logical workgroup lb, and the end clim of its range
+__device__ __forceinline__ void sweep_site(const SweepRanges &r, const int lb, int &c, int &clim) {
+  c = r.c0 + lb * 256 + threadIdx.x;
+  clim = r.c1;
+  if (lb >= r.nb1) { c = r.d0 + (lb - r.nb1) * 256 + threadIdx.x; clim = r.d1; }
 }
