@@ -236,7 +236,10 @@ int qexhip_stag_solve_sloppy(qexhip_handle h, double *x, const double *b, double
                              int use_prev, int sloppy, int *iters, double *r2_final, int *nupdates);
 
 /* multi-shift solveXX (src/physics/stagSolve.nim:296-345 + src/solvers/cgm.nim:84-315).
- * shifts[0] = base mass, shifts[k>0] = sigma_k added to m0^2; xs[k] full-volume vectors. */
+ * shifts[0] = base mass, shifts[k>0] = sigma_k added to the base operator 4 m0^2 - (2D)(2D) (i.e. shift k is that operator at
+ * m_k^2 = m0^2 + sigma_k / 4); xs[k] full-volume vectors.  fp64 throughout; the stop is the BASE system's iterated residual, the
+ * shifted systems follow it through the zeta recurrences and their residuals are not checked.  The mixed-precision form, which
+ * checks every shift's true residual, is qexhip_stag_solve_xx_multi_sloppy below. */
 int qexhip_stag_solve_xx_multi(qexhip_handle h, double *const *xs, const double *b,
                                const double *shifts, int nmass, double r2req, int maxits,
                                int par_even, int *iters, double *hist, int histcap);
@@ -244,6 +247,27 @@ int qexhip_stag_solve_xx_multi(qexhip_handle h, double *const *xs, const double 
 int qexhip_stag_solve_multi(qexhip_handle h, double *const *xs, const double *b,
                             const double *masses, int nmass, double r2req, int maxits,
                             int *iters, double *r2_final);
+/* Mixed-precision multi-shift solves (QUDA's scheme).  sloppy as qexhip_stag_solve_xx_sloppy: 0 IS the fp64 entry above (nupdates = 0,
+ * refine_iters all 0, r2_over_b2 all -1: the fp64 solver does not compute them), 1 single, 2 runs single.  QEXHIP_ERR_ARG before
+ * anything is launched for sloppy outside 0..2, for base mass 0 with sloppy > 0, and for nmass outside 1..32.
+ * Phase 1: the multi-shift CG with r, Ap, all nmass search directions and solution increments in fp32 (vectors in units of |b| for
+ * the whole solve), the zeta recurrences in double, and reliable updates on the base system as in the single solve (all shifts'
+ * increments flushed into the fp64 x_k in one launch, r = b - A_0 x_0 recomputed in fp64); it ends when the base system's TRUE
+ * residual is <= r2req |b|^2, or at maxits.  Phase 2: for every k >= 1 the true r_k = b - A_k x_k is computed in fp64; a shift with
+ * |r_k|^2 > r2req |b|^2 is refined by a sloppy CG on A_k d = r_k (own maxits; one rank without ghost zones: lock-step batches of up
+ * to 4 shifts, else one shift at a time) and |r_k|^2 recomputed once.
+ *   iters          fp32 iterations of phase 1
+ *   r2_over_b2[k]  the true |b - A_k x_k|^2 / |b|^2 of the returned x_k (nmass values)
+ *   nupdates       reliable updates of phase 1 (may be NULL)
+ *   refine_iters   nmass values (may be NULL): fp32 iterations spent refining shift k (0: not refined; [0] is always 0)
+ * t-sharded: collective, every rank returns the same values.  qexhip_release_workspace frees the fp32 fields. */
+int qexhip_stag_solve_xx_multi_sloppy(qexhip_handle h, double *const *xs, const double *b, const double *shifts, int nmass,
+                                      double r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2,
+                                      int *nupdates, int *refine_iters);
+/* qexhip_stag_solve_multi with the inner multi-shift solveXX in mixed precision (every shift of every inner solve refined to the
+ * inner target); the outer loop and the return values are the fp64 entry's; nupdates: the updates of all inner solves. */
+int qexhip_stag_solve_multi_sloppy(qexhip_handle h, double *const *xs, const double *b, const double *masses, int nmass,
+                                   double r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);
 
 /* ---------------- field algebra hooks ----------------
  * norm2 / redot with fp64 accumulation (src/field/fieldET.nim:605-625,704-724) and the
@@ -294,6 +318,10 @@ int qexhip_dev_solve_xx_continue(qexhip_handle h, int x_id, double r2req, int ma
  * x_ids[k] receives the solution of shift k; shifts as qexhip_stag_solve_xx_multi.  Blocks until finished. */
 int qexhip_dev_solve_xx_multi(qexhip_handle h, const int *x_ids, int b_id, const double *shifts, int nmass,
                               double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);
+/* qexhip_stag_solve_xx_multi_sloppy on resident fields (x_ids distinct, none of them b_id) */
+int qexhip_dev_solve_xx_multi_sloppy(qexhip_handle h, const int *x_ids, int b_id, const double *shifts, int nmass, double r2req,
+                                     int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates,
+                                     int *refine_iters);
 
 /* Free the multi-shift solvers' persistent workspace (up to 3 x nmass full fields kept between solves; QEX allocates its
  * ps / ys per call with newOneOf and leaves them to the GC, src/solvers/cgm.nim:120-131, src/physics/stagSolve.nim:376-381).

@@ -218,14 +218,39 @@ class Staggered {
       sp.flops += flops(its[j]); sp.r2 = fin[j]; sp.reliableUpdates += nup[j];
     }
   }
-  // multi-mass Staggered.solve(xs, b, ms, sp) (stagSolve.nim:347-446)
-  void solve(std::vector<Field> &xs, const Field &b, const std::vector<double> &ms, SolverParams &sp) {
-    if (sp.sloppySolve) throw std::invalid_argument("sloppySolve: single-mass solves only");
+  // multi-mass Staggered.solve(xs, b, ms, sp) (stagSolve.nim:347-446).  sloppy = -1: fp64, and a sloppy SolverParams is refused (as
+  // before); 0, 1, 2: the precision of the inner multi-shift CG, chosen explicitly (qexhip_stag_solve_multi_sloppy), overriding
+  // sp.sloppySolve; sp.reliableUpdates gets the updates
+  void solve(std::vector<Field> &xs, const Field &b, const std::vector<double> &ms, SolverParams &sp, int sloppy = -1) {
+    if (sloppy < -1 || sloppy > 2) throw std::invalid_argument("solve: sloppy = -1 (unset), 0, 1 or 2");
+    if (sloppy < 0 && sp.sloppySolve)
+      throw std::invalid_argument("sloppySolve: single-mass solves only (pass sloppy = 1 to solve for the mixed-precision multi-shift solve)");
     std::vector<double *> p;
     for (auto &x : xs) p.push_back(x.data());
-    int its = 0; double fin = 0;
-    timed(sp, its, [&] { check(qexhip_stag_solve_multi(c_.h, p.data(), b.data(), ms.data(), (int)ms.size(), sp.r2req, sp.maxits, &its, &fin)); });
-    sp.r2 = fin;
+    int its = 0, nup = 0; double fin = 0;
+    if (sloppy < 0) timed(sp, its, [&] { check(qexhip_stag_solve_multi(c_.h, p.data(), b.data(), ms.data(), (int)ms.size(), sp.r2req, sp.maxits, &its, &fin)); });
+    else timed(sp, its, [&] { check(qexhip_stag_solve_multi_sloppy(c_.h, p.data(), b.data(), ms.data(), (int)ms.size(), sp.r2req, sp.maxits, sloppy, &its, &fin, &nup)); });
+    sp.r2 = fin; sp.reliableUpdates += nup;
+  }
+  // mixed-precision multi-shift solveXX (qexhip_stag_solve_xx_multi_sloppy): shifts[0] = base mass; returns the true
+  // |b - A_k x_k|^2 / |b|^2 per shift; sp.iterations gets the fp32 iterations of phase 1, refineIterations (if given) those of phase 2
+  std::vector<double> solveXXMulti(std::vector<Field> &xs, const Field &b, const std::vector<double> &shifts, SolverParams &sp,
+                                   bool parEven = true, int sloppy = 1, std::vector<int> *refineIterations = nullptr) {
+    std::vector<double *> p;
+    for (auto &x : xs) p.push_back(x.data());
+    const int n = (int)shifts.size();
+    std::vector<double> r2(n);
+    std::vector<int> ref(n);
+    int its = 0, nup = 0;
+    timed(sp, its, [&] {
+      check(qexhip_stag_solve_xx_multi_sloppy(c_.h, p.data(), b.data(), shifts.data(), n, sp.r2req, sp.maxits, parEven ? 1 : 0, sloppy, &its,
+                                              r2.data(), &nup, ref.data()));
+    });
+    sp.reliableUpdates += nup;
+    sp.r2 = 0;
+    for (double v : r2) sp.r2 = std::max(sp.r2, v);
+    if (refineIterations) *refineIterations = ref;
+    return r2;
   }
 };
 inline Staggered newStag(Context &c, const Field &g) { return Staggered(c, g); }

@@ -56,6 +56,8 @@ SYMBOLS = [
     ("qexhip_stag_solve_prev", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),
     ("qexhip_stag_solve_xx_multi", _ci, [_vp, _vp, _vp, _vp, _ci, _cd, _ci, _ci, _pi, _vp, _ci]),
     ("qexhip_stag_solve_multi", _ci, [_vp, _vp, _vp, _vp, _ci, _cd, _ci, _pi, _pd]),
+    ("qexhip_stag_solve_xx_multi_sloppy", _ci, [_vp, _vp, _vp, _vp, _ci, _cd, _ci, _ci, _ci, _pi, _pd, _pi, _pi]),
+    ("qexhip_stag_solve_multi_sloppy", _ci, [_vp, _vp, _vp, _vp, _ci, _cd, _ci, _ci, _pi, _pd, _pi]),
     ("qexhip_norm2", _ci, [_vp, _vp, _ci, _pd]),
     ("qexhip_redot", _ci, [_vp, _vp, _vp, _ci, _pd]),
     ("qexhip_axpy", _ci, [_vp, _cd, _vp, _vp, _ci]),
@@ -70,6 +72,7 @@ SYMBOLS = [
     ("qexhip_dev_solve_xx", _ci, [_vp, _ci, _ci, _cd, _cd, _ci, _ci, _pi, _pd, _vp, _ci]),
     ("qexhip_dev_solve_xx_continue", _ci, [_vp, _ci, _cd, _ci, _pi, _pd, _vp, _ci]),
     ("qexhip_dev_solve_xx_multi", _ci, [_vp, _pi, _ci, _pd, _ci, _cd, _ci, _ci, _pi, _vp, _ci]),
+    ("qexhip_dev_solve_xx_multi_sloppy", _ci, [_vp, _pi, _ci, _pd, _ci, _cd, _ci, _ci, _ci, _pi, _pd, _pi, _pi]),
     ("qexhip_release_workspace", _ci, [_vp]),
     ("qexhip_dev_norm2", _ci, [_vp, _ci, _ci, _pd]),
     ("qexhip_dev_redot", _ci, [_vp, _ci, _ci, _ci, _pd]),

@@ -184,6 +184,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   hisq_state_free(c);
   batch_state_free(c);
   batch_f32_state_free(c);
+  msf_state_free(c);
   gauge_free(c);
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
@@ -495,6 +496,44 @@ extern "C" int qexhip_stag_solve_multi(qexhip_handle c, double *const *xs, const
   return multi_common(c, xs, b, masses, nmass, r2req, maxits, 1, 1, iters, r2_final, nullptr, 0);
 }
 
+// Mixed-precision multi-shift solves.  sloppy = 0 IS the fp64 entry (nupdates = 0, refine_iters all 0); r2_over_b2[k] then is not
+// computed by the fp64 solver and comes back as -1.
+extern "C" int qexhip_stag_solve_xx_multi_sloppy(qexhip_handle c, double *const *xs, const double *b, const double *shifts, int nmass,
+                                                 double r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2,
+                                                 int *nupdates, int *refine_iters) {
+  if (!c || !xs || !b || !shifts) return QEXHIP_ERR_ARG;
+  CHK(multi_sloppy_check(c, sloppy, shifts, nmass));
+  if (nupdates) *nupdates = 0;
+  if (refine_iters) for (int k = 0; k < nmass; k++) refine_iters[k] = 0;
+  if (!sloppy) {
+    if (r2_over_b2) for (int k = 0; k < nmass; k++) r2_over_b2[k] = -1.0;
+    return qexhip_stag_solve_xx_multi(c, xs, b, shifts, nmass, r2req, maxits, par_even, iters, nullptr, 0);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb;
+  CHK(host_in(c, WK_IN, b, &fb));
+  std::vector<DevField *> xp(nmass);
+  for (int k = 0; k < nmass; k++) CHK(pool_field(c, POOL_XS + k, &xp[k]));
+  CHK(solve_xx_multi_sloppy_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, r2_over_b2, nupdates, refine_iters));
+  for (int k = 0; k < nmass; k++) CHK(field_download(c, *xp[k], xs[k]));
+  return 0;
+}
+extern "C" int qexhip_stag_solve_multi_sloppy(qexhip_handle c, double *const *xs, const double *b, const double *masses, int nmass,
+                                              double r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates) {
+  if (!c || !xs || !b || !masses) return QEXHIP_ERR_ARG;
+  CHK(multi_sloppy_check(c, sloppy, masses, nmass));
+  if (nupdates) *nupdates = 0;
+  if (!sloppy) return qexhip_stag_solve_multi(c, xs, b, masses, nmass, r2req, maxits, iters, r2_final);
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb;
+  CHK(host_in(c, WK_IN, b, &fb));
+  std::vector<DevField *> xp(nmass);
+  for (int k = 0; k < nmass; k++) CHK(pool_field(c, POOL_XS + k, &xp[k]));
+  CHK(solve_multi_dev(c, xp, *fb, masses, nmass, r2req, maxits, iters, r2_final, sloppy, nupdates));
+  for (int k = 0; k < nmass; k++) CHK(field_download(c, *xp[k], xs[k]));
+  return 0;
+}
+
 // ---- field algebra hooks ----
 extern "C" int qexhip_norm2(qexhip_handle c, const double *x, int parity, double *out) {
   if (!c || !x || !out) return QEXHIP_ERR_ARG;
@@ -674,6 +713,30 @@ extern "C" int qexhip_dev_solve_xx_multi(qexhip_handle c, const int *x_ids, int 
   }
   return solve_xx_multi_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, hist, histcap);
 }
+// qexhip_stag_solve_xx_multi_sloppy on resident fields
+extern "C" int qexhip_dev_solve_xx_multi_sloppy(qexhip_handle c, const int *x_ids, int b_id, const double *shifts, int nmass,
+                                                double r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2,
+                                                int *nupdates, int *refine_iters) {
+  if (!c || !x_ids || !shifts) return QEXHIP_ERR_ARG;
+  CHK(multi_sloppy_check(c, sloppy, shifts, nmass));
+  if (nupdates) *nupdates = 0;
+  if (refine_iters) for (int k = 0; k < nmass; k++) refine_iters[k] = 0;
+  if (!sloppy) {
+    if (r2_over_b2) for (int k = 0; k < nmass; k++) r2_over_b2[k] = -1.0;
+    return qexhip_dev_solve_xx_multi(c, x_ids, b_id, shifts, nmass, r2req, maxits, par_even, iters, nullptr, 0);
+  }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb;
+  CHK(find_field(c, b_id, &fb));
+  std::vector<DevField *> xp(nmass);
+  for (int k = 0; k < nmass; k++) {
+    CHK(find_field(c, x_ids[k], &xp[k]));
+    if (x_ids[k] == b_id) { qexhip_set_error("dev_solve_xx_multi_sloppy: x_ids[%d] is the source field", k); return QEXHIP_ERR_ARG; }
+    for (int j = 0; j < k; j++)
+      if (x_ids[j] == x_ids[k]) { qexhip_set_error("dev_solve_xx_multi_sloppy: x_ids[%d] == x_ids[%d]", j, k); return QEXHIP_ERR_ARG; }
+  }
+  return solve_xx_multi_sloppy_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, r2_over_b2, nupdates, refine_iters);
+}
 
 // The multi-shift solvers keep up to 3 x nmass full fields (search directions, per-parity and host-entry solutions) between
 // calls so that a trajectory's repeated solves allocate nothing; a host that is about to need the memory for something
@@ -692,6 +755,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   }
   gauge_release_scratch(c);
   f32_state_free(c);                 // the mixed-precision CG's fp32 links and fields: rebuilt by the next sloppy solve
+  msf_state_free(c);                 // and the mixed multi-shift CG's fp32 search directions / increments
   batch_f32_state_free(c);           // and the batched form's fp32 fields
   return 0;
 }

@@ -10,8 +10,6 @@
 #include <algorithm>
 #include <cstring>
 
-#define CGM_MAXM 32
-
 struct CgmScal {
   int nmass, cont, pending, pad;
   double alpha, beta, alphaim1, betaim1;
@@ -248,9 +246,10 @@ int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, 
   return 0;
 }
 
-// Staggered.solve(xs, b, ms, sp)  (stagSolve.nim:347-446)
+// Staggered.solve(xs, b, ms, sp)  (stagSolve.nim:347-446); sloppy > 0: the inner multi-shift solveXX is the mixed-precision one
+// (solve_xx_multi_sloppy_dev: every shift refined to the inner target), *nupdates <- the reliable updates of all inner solves
 int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *masses,
-                    int nmass, double r2req, int maxits, int *iters, double *r2_final) {
+                    int nmass, double r2req, int maxits, int *iters, double *r2_final, int sloppy, int *nupdates) {
   if (nmass < 1 || nmass > CGM_MAXM) { qexhip_set_error("multishift: 1 <= nmass <= %d", CGM_MAXM); return -1; }
   DevField *r, *xt;
   CHK(get_work(c, WK_R2, &r));
@@ -273,7 +272,7 @@ int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, con
   double b2 = h[0], b2e = h[1], b2o = h[2];
   double r2 = b2e + b2o;
   const double r2stop = r2req * b2;
-  int its = 0;
+  int its = 0, nupd = 0;
   while (r2 > r2stop) {
     int mx = maxits - its;
     if (mx <= 0) break;
@@ -284,9 +283,11 @@ int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, con
     int even = 1;
     if (b2e > r2stope) { rq = r2stope / b2e; even = 1; }
     else if (b2o > r2stopo) { rq = r2stopo / b2o; even = 0; }
-    int n = 0;
-    CHK(solve_xx_multi_dev(c, ys, *r, shifts.data(), nmass, rq, mx, even, &n, nullptr, 0));
+    int n = 0, nu = 0;
+    if (sloppy) CHK(solve_xx_multi_sloppy_dev(c, ys, *r, shifts.data(), nmass, rq, mx, even, &n, nullptr, &nu, nullptr));
+    else CHK(solve_xx_multi_dev(c, ys, *r, shifts.data(), nmass, rq, mx, even, &n, nullptr, 0));
     its += n;
+    nupd += nu;
     for (int k = 0; k < nmass; k++) CHK(blas_axpy(c, 4.0, *ys[k], *xs[k], even ? 0 : 1));
     CHK(op_D(c, *xt, *xs[0], mass, -1.0));
     CHK(op_D(c, *r, *xt, mass, 1.0));
@@ -304,5 +305,6 @@ int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, con
   HIPCHK(hipStreamSynchronize(c->stream));
   if (iters) *iters = its;
   if (r2_final) *r2_final = (b2 != 0.0) ? r2 / b2 : 0.0;
+  if (nupdates) *nupdates = nupd;
   return 0;
 }

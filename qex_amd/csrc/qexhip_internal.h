@@ -201,6 +201,7 @@ struct qexhip_ctx {
   unsigned long links_gen = 0;                       // bumped by every writer of W / Wc (links_compress ends each of them): the fp32 copy's staleness test
   void *f32 = nullptr;                               // F32State (dslash_f32.hip): fp32 links + fields + SlpScal of the mixed-precision CG
   void *batch_f32 = nullptr;                         // BatchF32State (batch_f32.hip): fp32 fields + SlpScal[4] of the mixed-precision batched CG
+  void *msf32 = nullptr;                             // MsfState (multishift_f32.hip): fp32 search directions / increments of the mixed-precision multi-shift CG
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -353,6 +354,15 @@ int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const De
 int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity);
 int slp_resid(qexhip_ctx *c, SlpScal *s, DevField &r, const DevField &b, const DevField &Ax, int parity);
 
+// ---- multishift_f32.hip: the fp32 iteration of the mixed-precision multi-shift CG ----
+#define CGM_MAXM 32                                      // shifts per multi-shift solve (fp64 and mixed)
+void msf_state_free(qexhip_ctx *c);
+int msf_r2_buffer(qexhip_ctx *c, double **dev);          // 32 device scalars: the per-shift |b - A_k x_k|^2 of the refinement phase
+int msf_start(qexhip_ctx *c, SlpScal *s, DevFieldF &rs, const DevField &b, std::vector<DevField *> &xs, const double *shifts, int nmass,
+              int parity, DevFieldF **ps0);
+int msf_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &rs, const DevFieldF &Ap, const DevField &r, int parity, int ndot);
+int msf_flush(qexhip_ctx *c, SlpScal *s, int nmass);
+
 // ---- blas.hip ----
 int blas_zero(qexhip_ctx *c, DevField &f, int parity);
 int blas_copy(qexhip_ctx *c, DevField &dst, const DevField &src, int parity);
@@ -390,9 +400,14 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
 int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts,
                        int nmass, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);
 int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *masses,
-                    int nmass, double r2req, int maxits, int *iters, double *r2_final);
+                    int nmass, double r2req, int maxits, int *iters, double *r2_final, int sloppy = 0, int *nupdates = nullptr);
+// mixed-precision multi-shift solveXX: fp32 multi-shift iterations with reliable updates on the base shift, then per-shift refinement
+// on the true residual (solver.cpp).  r2_over_b2[k]: |b - A_k x_k|^2 / |b|^2 of the returned x_k; refine_iters, nupdates may be null.
+int multi_sloppy_check(qexhip_ctx *c, int sloppy, const double *vals, int nmass);      // QEXHIP_ERR_ARG before anything is launched
+int solve_xx_multi_sloppy_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts, int nmass, double r2req,
+                              int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates, int *refine_iters);
 // persistent multi-shift workspace (multishift.hip): search directions, per-parity solutions, host-entry solutions
-enum { POOL_PS = 0, POOL_YS = 32, POOL_XS = 64 };
+enum { POOL_PS = 0, POOL_YS = 32, POOL_XS = 64, POOL_REF = 96 };   // POOL_REF: 4 corrections + 4 residuals of the sloppy solve's refinement
 int pool_field(qexhip_ctx *c, int idx, DevField **f);
 
 // ---- force.hip ----

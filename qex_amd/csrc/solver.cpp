@@ -260,6 +260,135 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
   return 0;
 }
 
+// ---- mixed-precision multi-shift solveXX (QUDA's scheme: fp32 multi-shift iterations, then per-shift refinement) ----
+// Phase 1: the multi-shift CG of solve_xx_multi_dev with every iterated vector in fp32 (multishift_f32.hip) and reliable updates on the
+// BASE system: gated on device flags and posted every opt_sloppy_check-th iteration and at maxits like the single solve's; one launch
+// flushes all shifts, the fp64 op_xx runs on x_0 alone, and the base system's true residual decides the stop.  After a residual
+// replacement the shifted residuals are no longer exactly zeta_k r -- expected, and the reason for
+// Phase 2: for every k >= 1 the true r_k = b - A_k x_k (fp64 op_xx; A_k = A_0 + sg[k], i.e. op_xx at m_k^2 = m^2 + sg[k]/4); a shift
+// with |r_k|^2 > r2req |b|^2 is refined -- A_k d = r_k to r2req |b|^2 / |r_k|^2 with the sloppy CG, x_k += d -- and |r_k|^2 recomputed
+// once: the value reported.  One rank without ghost zones: lock-step batches of up to four shifts (solve_xx_batch_sloppy_dev: each
+// system returns the bits it returns alone); with ghost zones or more ranks, where the batch is refused, solve_xx_sloppy_dev one
+// shift at a time.  Sharded: every reduction is rank-global (msf_iterate, slp_resid, blas_norm2), so every rank takes the same
+// updates, the same stop and the same refinement decisions; slp_agree checks it at the end of every 32-iteration chunk.
+int multi_sloppy_check(qexhip_ctx *c, int sloppy, const double *vals, int nmass) {
+  if (sloppy < 0 || sloppy > 2) {
+    qexhip_set_error("sloppy = %d: 0 (SloppyNone, fp64), 1 (SloppySingle) or 2 (SloppyHalf, runs single)", sloppy);
+    return QEXHIP_ERR_ARG;
+  }
+  if (nmass < 1 || nmass > CGM_MAXM) { qexhip_set_error("multishift: 1 <= nmass <= %d (nmass = %d)", CGM_MAXM, nmass); return QEXHIP_ERR_ARG; }
+  if (sloppy && vals[0] == 0.0) {
+    qexhip_set_error("sloppy multi-shift solve: base mass 0 unsupported (op_xx's <p,Ap> needs 4 m^2 > 0)");
+    return QEXHIP_ERR_ARG;
+  }
+  return 0;
+}
+
+int solve_xx_multi_sloppy_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts, int nmass, double r2req,
+                              int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates, int *refine_iters) {
+  CHK(multi_sloppy_check(c, 1, shifts, nmass));
+  const int par = par_even ? 0 : 1;
+  DevField *r, *Ax;
+  CHK(get_work(c, WK_R, &r));
+  CHK(get_work(c, WK_AP, &Ax));
+  CHK(f32_links(c, nullptr, nullptr));
+  DevFieldF *rs, *aps, *ps0;
+  CHK(f32_field(c, F32_R, &rs));
+  CHK(f32_field(c, F32_AP, &aps));
+  SlpScal *s;
+  CHK(slp_alloc(c, &s));
+  const double m2 = shifts[0] * shifts[0];
+  for (int k = 0; k < nmass; k++) CHK(blas_zero(c, *xs[k], 2));
+  CHK(blas_norm2(c, b, par, &c->dscal[0]));
+  CHK(blas_copy(c, *r, b, par));
+  CHK(slp_init(c, s, r2req, maxits));
+  CHK(msf_start(c, s, *rs, b, xs, shifts, nmass, par, &ps0));
+  SlpScal h;
+  auto read_state = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(&h, c->pinned, sizeof(SlpScal));
+    return 0;
+  };
+  CHK(read_state());
+  const int every = std::max(1, c->opt_sloppy_check);
+  int k = 0;
+  {
+    ScopedTimer tm(c, "multi_phase1", c->stream);       // (timers on: the stream time of the whole phase, host read-backs included)
+    while (!h.done && k < maxits) {
+      const int n = std::min(32, maxits - k);
+      for (int i = 0; i < n; i++, k++) {
+        int ndot = 0;
+        CHK(f32_op_xx(c, *aps, *ps0, m2, par_even, 1, &s->done, &ndot));
+        CHK(msf_iterate(c, s, *rs, *aps, *r, par, ndot));
+        if ((k + 1) % every == 0 || k + 1 >= maxits) {
+          CHK(msf_flush(c, s, nmass));
+          CHK(op_xx(c, *Ax, *xs[0], m2, par_even, 0, &s->noupd));
+          CHK(slp_resid(c, s, *r, b, *Ax, par));
+        }
+      }
+      CHK(read_state());
+      CHK(slp_agree(c, h));
+    }
+  }
+  if (iters) *iters = h.k;
+  if (nupdates) *nupdates = h.nupd;
+  if (refine_iters) for (int j = 0; j < nmass; j++) refine_iters[j] = 0;
+  const double b2 = h.b2;
+  if (r2_over_b2) {
+    r2_over_b2[0] = (b2 != 0.0) ? h.r2t / b2 : 0.0;
+    for (int j = 1; j < nmass; j++) r2_over_b2[j] = 0.0;
+  }
+  if (b2 == 0.0 || nmass == 1) return 0;
+  // ---- phase 2 ----
+  const bool batched = c->nranks == 1 && !c->g.halo;
+  double *dr2;
+  CHK(msf_r2_buffer(c, &dr2));
+  DevField *d[4], *rk[4];
+  for (int j = 0; j < 4; j++) {
+    CHK(pool_field(c, POOL_REF + j, &d[j]));
+    CHK(pool_field(c, POOL_REF + 4 + j, &rk[j]));
+  }
+  const double r2stop = r2req * b2;
+  ScopedTimer tm2(c, "multi_phase2", c->stream);
+  auto resid = [&](int kk, double mk, DevField &out, double *dev) -> int {     // out = b - A_k x_k, |out|^2 (rank-global) -> *dev
+    CHK(op_xx(c, *Ax, *xs[kk], mk * mk, par_even, 0, nullptr));
+    CHK(blas_axpby(c, 1.0, b, -1.0, *Ax, out, par));
+    return blas_norm2(c, out, par, dev);
+  };
+  for (int k0 = 1; k0 < nmass; k0 += 4) {
+    const int ng = std::min(4, nmass - k0);
+    double mk[4], r2k[4];
+    for (int j = 0; j < ng; j++) {
+      mk[j] = sqrt(m2 + 0.25 * shifts[k0 + j]);
+      CHK(resid(k0 + j, mk[j], *rk[j], &dr2[j]));
+    }
+    CHK(read_scalars(c, dr2, ng, r2k));
+    int sel[4], ns = 0;
+    for (int j = 0; j < ng; j++) if (r2k[j] > r2stop) sel[ns++] = j;
+    if (ns > 0) {
+      DevField *dx[4], *db[4];
+      double mm[4], rq[4];
+      int its[4] = {0, 0, 0, 0};
+      for (int q = 0; q < ns; q++) { dx[q] = d[sel[q]]; db[q] = rk[sel[q]]; mm[q] = mk[sel[q]]; rq[q] = r2stop / r2k[sel[q]]; }
+      if (batched) {
+        CHK(solve_xx_batch_sloppy_dev(c, ns, dx, db, mm, rq, maxits, par_even, its, nullptr, nullptr));
+      } else {
+        for (int q = 0; q < ns; q++) CHK(solve_xx_sloppy_dev(c, *dx[q], *db[q], mm[q], rq[q], maxits, par_even, &its[q], nullptr, nullptr));
+      }
+      for (int q = 0; q < ns; q++) {
+        const int j = sel[q];
+        CHK(blas_axpy(c, 1.0, *dx[q], *xs[k0 + j], par));
+        if (refine_iters) refine_iters[k0 + j] = its[q];
+        CHK(resid(k0 + j, mk[j], *rk[j], &dr2[j]));       // (Ax: solve_xx_sloppy_dev's work vector too, free again here)
+      }
+      CHK(read_scalars(c, dr2, ng, r2k));
+    }
+    if (r2_over_b2) for (int j = 0; j < ng; j++) r2_over_b2[k0 + j] = r2k[j] / b2;
+  }
+  return 0;
+}
+
 // the inner solveXX of the full solve: fp64 CG, or the mixed-precision one (sloppy > 0)
 static int inner_xx(qexhip_ctx *c, DevField &x, DevField &b, double m, double r2req, int maxits, int par_even, int *its,
                     int sloppy, int *nupd) {

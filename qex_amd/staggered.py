@@ -56,6 +56,7 @@ class SolverParams:
         self.r2 = 0.0
         self.r2hist = None
         self.reliableUpdates = 0   # mixed-precision solves (sloppySolve != 0): fp64 true-residual updates
+        self.refineIterations = []  # mixed-precision multi-shift solveXX: fp32 iterations spent refining each shift
 
     @property
     def finalIterations(self):
@@ -216,10 +217,21 @@ class Context:
         check(lib().qexhip_dev_solve_xx_continue(self._h, x_id, float(r2req), int(maxits), C.byref(its), C.byref(fin), _p(hist), histcap))
         return its.value, fin.value, hist[: min(histcap, its.value + 1)]
 
-    def dev_solve_xx_multi(self, x_ids, b_id, shifts, r2req, maxits, par_even=True, histcap=0):
-        """multi-shift solveXX on resident fields (stagSolve.nim:296-345); shifts[0] = base mass"""
+    def dev_solve_xx_multi(self, x_ids, b_id, shifts, r2req, maxits, par_even=True, histcap=0, sloppy=None):
+        """multi-shift solveXX on resident fields (stagSolve.nim:296-345); shifts[0] = base mass.  sloppy = 0, 1 or 2: the
+        mixed-precision solve (qexhip_dev_solve_xx_multi_sloppy; no history), returning (fp32 iterations of phase 1, true r2/b2
+        per shift, reliable updates, refinement iterations per shift)"""
         n = len(x_ids)
         its = C.c_int(0)
+        if sloppy is not None:
+            sloppy = _batch_sloppy(sloppy)
+            if histcap > 0:
+                raise ValueError("sloppy= with histcap > 0: the mixed-precision multi-shift solve keeps no residual history")
+            fin, nup, ref = (C.c_double * n)(), C.c_int(0), (C.c_int * n)()
+            check(lib().qexhip_dev_solve_xx_multi_sloppy(self._h, (C.c_int * n)(*[int(v) for v in x_ids]), int(b_id),
+                                                         (C.c_double * n)(*[float(v) for v in shifts]), n, float(r2req), int(maxits),
+                                                         1 if par_even else 0, sloppy, C.byref(its), fin, C.byref(nup), ref))
+            return its.value, list(fin), nup.value, list(ref)
         hist = np.zeros(max(histcap, 1))
         check(lib().qexhip_dev_solve_xx_multi(self._h, (C.c_int * n)(*[int(v) for v in x_ids]), b_id,
                                               (C.c_double * n)(*[float(v) for v in shifts]), n, float(r2req), int(maxits),
@@ -469,13 +481,37 @@ class Staggered:
     def solveOO(self, r, x, m, sp, histcap=0):
         self.solveXX(r, x, m, sp, False, histcap)
 
-    def solve(self, x, b, m, sp):
-        """Staggered.solve: x (array or list of arrays) <- D(m)^-1 b  (stagSolve.nim:224-294,347-446)"""
+    def solve(self, x, b, m, sp, sloppy=None):
+        """Staggered.solve: x (array or list of arrays) <- D(m)^-1 b  (stagSolve.nim:224-294,347-446).
+        sloppy (mass lists only): None = fp64, and a SolverParams that asks for a sloppy solve is refused; 0, 1 or 2 = the precision
+        of the inner multi-shift CG, chosen explicitly whatever sp says (qexhip_stag_solve_multi_sloppy)."""
+        multi = isinstance(x, (list, tuple))
+        if sloppy is not None:
+            sloppy = _batch_sloppy(sloppy)
+            if not multi:
+                raise ValueError("sloppy= applies to mass lists; a single-mass solve takes its precision from sp.sloppySolve")
+            t0 = time.time()
+            its, fin, nup = C.c_int(0), C.c_double(0), C.c_int(0)
+            ms = np.array([float(v) for v in m], dtype=np.float64)
+            ptrs = (C.c_void_p * len(x))(*[_p(a).value for a in x])
+            check(lib().qexhip_stag_solve_multi_sloppy(self.ctx._h, ptrs, _p(b), _p(ms), len(x), float(sp.r2req), int(sp.maxits),
+                                                       sloppy, C.byref(its), C.byref(fin), C.byref(nup)))
+            sp.calls += 1
+            sp.iterations += its.value
+            sp.iterationsMax = max(sp.iterationsMax, its.value)
+            sp.seconds += time.time() - t0
+            sp.flops += self._flops(its.value)
+            sp.r2 = fin.value
+            sp.reliableUpdates += nup.value
+            if sp.verbosity > 1:
+                print("stagSolve(HIP): " + sp.getStats())
+            return
         t0 = time.time()
         its, fin = C.c_int(0), C.c_double(0)
         sloppy = int(getattr(sp, "sloppySolve", SloppyNone))
-        if isinstance(x, (list, tuple)) and sloppy != SloppyNone:
-            raise ValueError("sloppySolve applies to single-mass solves only (multi-shift solves run in fp64)")
+        if multi and sloppy != SloppyNone:
+            raise ValueError("sloppySolve applies to single-mass solves only: a multi-shift solve runs in fp64 unless the "
+                             "mixed-precision one is asked for with the keyword sloppy=1 (solve / solveXX_multi / dev_solve_xx_multi)")
         if sloppy != SloppyNone:
             nup = C.c_int(0)
             check(lib().qexhip_stag_solve_sloppy(self.ctx._h, _p(x), _p(b), float(m), float(sp.r2req), int(sp.maxits),
@@ -560,10 +596,34 @@ class Staggered:
         precision explicitly (as in solve_batch) and returns (fp32 iterations, true r2/b2, reliable updates) per system."""
         return self._batch("xx", xs, bs, ms, r2req, maxits, parEven, sloppy)
 
-    def solveXX_multi(self, xs, b, shifts, sp, parEven=True, histcap=0):
-        """Staggered.solveXX(xs, b, ms, sp, subset) (stagSolve.nim:296-345): shifts[0] = base mass."""
+    def solveXX_multi(self, xs, b, shifts, sp, parEven=True, histcap=0, sloppy=None):
+        """Staggered.solveXX(xs, b, ms, sp, subset) (stagSolve.nim:296-345): shifts[0] = base mass.
+        sloppy: None = fp64, and a SolverParams that asks for a sloppy solve is refused; 0, 1 or 2 = the mixed-precision multi-shift
+        solve (fp32 iterations with reliable updates on the base shift, then every shift refined on its true residual), chosen
+        explicitly whatever sp says.  It returns the true |b - A_k x_k|^2/|b|^2 per shift (-1 each for sloppy=0, where the fp64
+        solver does not compute them, and sp.r2 is left unchanged as by the fp64 call); sp.iterations gets the fp32 iterations of phase 1, sp.reliableUpdates its updates,
+        sp.refineIterations the refinement iterations per shift, sp.r2 the largest per-shift residual.  No residual history."""
+        if sloppy is not None:
+            sloppy = _batch_sloppy(sloppy)
+            if histcap > 0:
+                raise ValueError("sloppy= with histcap > 0: the mixed-precision multi-shift solve keeps no residual history")
+            n = len(xs)
+            its, nup = C.c_int(0), C.c_int(0)
+            fin, ref = (C.c_double * n)(), (C.c_int * n)()
+            sh = np.array([float(v) for v in shifts], dtype=np.float64)
+            ptrs = (C.c_void_p * n)(*[_p(a).value for a in xs])
+            check(lib().qexhip_stag_solve_xx_multi_sloppy(self.ctx._h, ptrs, _p(b), _p(sh), n, float(sp.r2req), int(sp.maxits),
+                                                          1 if parEven else 0, sloppy, C.byref(its), fin, C.byref(nup), ref))
+            sp.iterations += its.value
+            sp.reliableUpdates += nup.value
+            sp.refineIterations = list(ref)
+            if sloppy:
+                sp.r2 = max(fin)
+            sp.r2hist = None
+            return list(fin)
         if int(getattr(sp, "sloppySolve", SloppyNone)) != SloppyNone:
-            raise ValueError("sloppySolve applies to single-mass solves only (multi-shift solves run in fp64)")
+            raise ValueError("sloppySolve applies to single-mass solves only: a multi-shift solve runs in fp64 unless the "
+                             "mixed-precision one is asked for with the keyword sloppy=1 (solve / solveXX_multi / dev_solve_xx_multi)")
         its = C.c_int(0)
         sh = np.array([float(v) for v in shifts], dtype=np.float64)
         hist = np.zeros(max(histcap, 1))
