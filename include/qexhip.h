@@ -410,6 +410,31 @@ int qexhip_polyakov_loops(qexhip_handle h, double out[8]);
  * and peo[nu][x_nu mod 2]; out[2 d + eo] = peo[d][eo] / (physVol * 0.5 * (nd - 1) * nc), of the resident field */
 int qexhip_plaq_s4(qexhip_handle h, double out[8]);
 
+/* ---------------- gauge fixing (src/gauge/gaugefix.nim) ----------------
+ * Coulomb (dirs = {0,1,2}) or Landau (dirs = {0,1,2,3}) gauge fixing of the resident links (qexhip_gauge_set) by a resident
+ * transform field t, one SU(3) matrix per site, host format [vol][3][3][2] in the V = 1 even-odd site order.  `dirs` is any
+ * subset of {0,1,2,3} without repeats.  QEXHIP_ERR_ARG, before anything is launched and with nothing written, for bad dirs,
+ * orf outside (0,2], maxits < 0, and when the gauge field or the transform is not resident.
+ *   set_transform   t := the given field, NULL = the identity (`t := 1`, gaugefix.nim:376); get_transform downloads it
+ *   gauge_fix       getGaugeFixTransform (gaugefix.nim:312-355): even/odd SU(2)-subgroup over-relaxation (relaxE / relaxO :286-310,
+ *                   overRelaxSu2 :241-284) until gdsq = gre + gro <= gstop, then line-minimisation steps (gfLineMin :197-227)
+ *                   while it stays there; stops after 11 consecutive evaluations with gdsq <= gstop, or after maxits updates
+ *                   (which the reference lacks; reaching it is not an error).  An evaluation and the relax sweep behind it are
+ *                   one pass here, so the first update after gdsq has fallen to gstop is still a relax sweep.  iters = updates
+ *                   done; metrics = {met, gre, gro, gdsq} of the last evaluation (gfMetrics :145-174), which is t's as returned;
+ *                   hist (may be NULL) receives met, gre, gro of the evaluation before update k at hist[3 k], k < min(iters, histcap).
+ *                   Option "gfix_check" (default 16): relax iterations between two read-backs of the device-side loop state;
+ *                   the result does not depend on it.
+ *   gauge_transform gaugeTransform (gaugefix.nim:8-20): g_mu(x) <- t(x) g_mu(x) t(x+mu)^+ on the resident links, all four mu
+ *   link_trace      linkTrace (gaugefix.nim:135-142): sum_{mu in dirs} Re tr g_mu / (ndirs * physVol * 3) of the resident links
+ * t-sharded contexts: collective; t is the rank's slab, sums are rank-global.  qexhip_release_workspace frees the transform. */
+int qexhip_gfix_set_transform(qexhip_handle h, const double *t);
+int qexhip_gfix_get_transform(qexhip_handle h, double *t);
+int qexhip_gauge_fix(qexhip_handle h, const int *dirs, int ndirs, double gstop, double orf, int maxits, int *iters, double metrics[4],
+                     double *hist, int histcap);
+int qexhip_gauge_transform(qexhip_handle h);
+int qexhip_gauge_link_trace(qexhip_handle h, const int *dirs, int ndirs, double *out);
+
 /* ---------------- link construction upstream of the solver ----------------
  * g, fl, ll: double[vol][4][3][3][2].
  * qexhip_fat7: makeImpLinks (src/gauge/fat7l.nim:77-161), coef = {oneLink, threeStaple, fiveStaple,

@@ -263,6 +263,28 @@ inline std::array<double, 6> plaq(Context &c, const Field &g) {
   check(qexhip_plaq(c.h, p.data()));
   return p;
 }
+// getGaugeFixTransform(t, g, dirs, gstop, orf) (gaugefix.nim:312-355) on the resident links, starting from t (resized to
+// vol * 18 and set to the identity when empty); t stays resident for gaugeTransform.  Returns the iterations; metrics (may be
+// null) receives met, gre, gro, gdsq of the last evaluation.
+inline int getGaugeFixTransform(Context &c, Field &t, const std::vector<int> &dirs, double gstop = 1e-5, double orf = 1.8,
+                                int maxits = 100000, double *metrics = nullptr) {
+  if (!t.empty() && t.size() != (size_t)c.lo.nSites * 18) throw Error("getGaugeFixTransform: t must be empty or hold nSites * 18 doubles");
+  check(qexhip_gfix_set_transform(c.h, t.empty() ? nullptr : t.data()));
+  int its = 0;
+  double m[4];
+  check(qexhip_gauge_fix(c.h, dirs.data(), (int)dirs.size(), gstop, orf, maxits, &its, m, nullptr, 0));
+  if (metrics) std::copy(m, m + 4, metrics);
+  t.resize((size_t)c.lo.nSites * 18);
+  check(qexhip_gfix_get_transform(c.h, t.data()));
+  return its;
+}
+// gaugeTransform (gaugefix.nim:8-20) of the resident links by the resident t; linkTrace (gaugefix.nim:135-142)
+inline void gaugeTransform(Context &c) { check(qexhip_gauge_transform(c.h)); }
+inline double linkTrace(Context &c, const std::vector<int> &dirs) {
+  double r = 0;
+  check(qexhip_gauge_link_trace(c.h, dirs.data(), (int)dirs.size(), &r));
+  return r;
+}
 // g.gaugeFlow(steps, eps): measure(wflowT)  (wflow.nim:21-67); g is modified in place
 template <class Measure>
 inline void gaugeFlow(Context &c, Field &g, int steps, double eps, Measure &&measure) {

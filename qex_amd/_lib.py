@@ -117,6 +117,11 @@ SYMBOLS = [
     ("qexhip_wline", _ci, [_vp, _pi, _ci, _vp]),
     ("qexhip_polyakov_loops", _ci, [_vp, _vp]),
     ("qexhip_plaq_s4", _ci, [_vp, _vp]),
+    ("qexhip_gfix_set_transform", _ci, [_vp, _vp]),
+    ("qexhip_gfix_get_transform", _ci, [_vp, _vp]),
+    ("qexhip_gauge_fix", _ci, [_vp, _pi, _ci, _cd, _cd, _ci, _pi, _pd, _pd, _ci]),
+    ("qexhip_gauge_transform", _ci, [_vp]),
+    ("qexhip_gauge_link_trace", _ci, [_vp, _pi, _ci, _pd]),
     ("qexhip_rng_new", _ci, [_vp, _ci, C.c_ulonglong, _pi, _pi, _ci]),
     ("qexhip_rng_free", _ci, [_vp]),
     ("qexhip_rng_uniform", _ci, [_vp, _ci, _vp]),

@@ -185,6 +185,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   batch_state_free(c);
   batch_f32_state_free(c);
   msf_state_free(c);
+  gfix_state_free(c);
   gauge_free(c);
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
@@ -757,6 +758,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   f32_state_free(c);                 // the mixed-precision CG's fp32 links and fields: rebuilt by the next sloppy solve
   msf_state_free(c);                 // and the mixed multi-shift CG's fp32 search directions / increments
   batch_f32_state_free(c);           // and the batched form's fp32 fields
+  gfix_state_free(c);                // and the gauge-fixing transform with its polish scratch (qexhip_gfix_set_transform re-creates it)
   return 0;
 }
 
@@ -878,6 +880,10 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
   else if (n == "sloppy_check") {
     if (value < 1) { qexhip_set_error("option sloppy_check: >= 1 fp32 iterations"); return QEXHIP_ERR_ARG; }
     c->opt_sloppy_check = value;
+  }
+  else if (n == "gfix_check") {
+    if (value < 1) { qexhip_set_error("option gfix_check: >= 1 relax iterations"); return QEXHIP_ERR_ARG; }
+    c->opt_gfix_check = value;
   }
   else { qexhip_set_error("unknown option"); return QEXHIP_ERR_ARG; }
   return 0;
@@ -1161,6 +1167,24 @@ extern "C" int qexhip_polyakov_loops(qexhip_handle c, double out[8]) {
   if (!c || !out) return QEXHIP_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
   return gauge_polyakov(c, out);
+}
+// gauge fixing (gaugefix.hip): gaugefix.nim:376 `t := 1`, :312-355 getGaugeFixTransform, :8-20 gaugeTransform, :135-142 linkTrace
+extern "C" int qexhip_gfix_set_transform(qexhip_handle c, const double *t) { if (!c) return QEXHIP_ERR_ARG; return gfix_set_transform(c, t); }
+extern "C" int qexhip_gfix_get_transform(qexhip_handle c, double *t) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!t) { qexhip_set_error("gfix_get_transform: null argument"); return QEXHIP_ERR_ARG; }
+  return gfix_get_transform(c, t);
+}
+extern "C" int qexhip_gauge_fix(qexhip_handle c, const int *dirs, int ndirs, double gstop, double orf, int maxits, int *iters,
+                                double metrics[4], double *hist, int histcap) {
+  if (!c) return QEXHIP_ERR_ARG;
+  return gauge_fix(c, dirs, ndirs, gstop, orf, maxits, iters, metrics, hist, histcap);
+}
+extern "C" int qexhip_gauge_transform(qexhip_handle c) { if (!c) return QEXHIP_ERR_ARG; return gauge_transform(c); }
+extern "C" int qexhip_gauge_link_trace(qexhip_handle c, const int *dirs, int ndirs, double *out) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!out) { qexhip_set_error("gauge_link_trace: null argument"); return QEXHIP_ERR_ARG; }
+  return gauge_link_trace(c, dirs, ndirs, out);
 }
 extern "C" int qexhip_wflow(qexhip_handle c, int nsteps, double eps) { if (!c || nsteps < 0) return QEXHIP_ERR_ARG; return gauge_wflow(c, nsteps, eps); }
 

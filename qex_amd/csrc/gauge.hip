@@ -21,20 +21,6 @@
 #include <cstdlib>
 #include <initializer_list>
 
-struct GaugeNat {
-  double2 *U = nullptr, *F = nullptr, *P = nullptr;
-  double2 *U2 = nullptr;   // second link buffer: the fused flow stage reads U and writes exp(v) U here, then they swap
-  double2 *D2 = nullptr;   // double links U_a(x) U_a(x+a) of the rectangle force (k_double_links / k_force_rect)
-  size_t n2 = 0;  // double2 elements per field (incl. ghost tiles when t is sharded)
-  int ghost_valid = 0;   // depth to which the ghost slices of U are current
-  double *pp = nullptr; int npp = 0;   // per-workgroup plaquette partials of k_plaq
-  double2 *M = nullptr;      // resident MD momenta (qexhip_md_*)
-  double2 *Usave = nullptr;  // links saved around a force-gradient shift
-  int save_ghost_valid = 0;
-};
-
-static int gauge_ghosts(qexhip_ctx *c, int depth);
-static int read_global(qexhip_ctx *c, double *dev, int n, double *host);
 static int ordered_sites(qexhip_ctx *c, const int **order, int *chunk, int *nb, double **part);
 
 __device__ __forceinline__ size_t link_off(const Geom &g, const int x[4], int mu) {
@@ -996,7 +982,7 @@ static int gn_alloc_fp(qexhip_ctx *c) {
   return 0;
 }
 // refresh the ghost slices of the resident links to at least `depth` (1..3); no-op unless t is sharded
-static int gauge_ghosts(qexhip_ctx *c, int depth) {
+int gauge_ghosts(qexhip_ctx *c, int depth) {
   const Geom &g = c->g;
   if (!g.halo || c->gn->ghost_valid >= depth) return 0;
   if (g.X[3] < depth) { qexhip_set_error("local t extent %d < ghost depth %d needed by this kernel", g.X[3], depth); return -1; }
@@ -1016,7 +1002,7 @@ static int gauge_ghosts(qexhip_ctx *c, int depth) {
   return 0;
 }
 // rank-sum of n device scalars, then read back
-static int read_global(qexhip_ctx *c, double *dev, int n, double *host) {
+int read_global(qexhip_ctx *c, double *dev, int n, double *host) {
   if (multi_rank(c)) CHK(comm_allreduce(c, dev, n));
   return read_scalars(c, dev, n, host);
 }

@@ -23,6 +23,16 @@ __device__ __forceinline__ size_t link_off_t(const Geom &g, const int x[4], int 
   int c = lex >> 1;
   return (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
 }
+// the same site in a one-matrix-per-site field M[parity][tile][9][64] with the links' ghost tiles (the transform field of gaugefix.hip)
+template <bool HALO>
+__device__ __forceinline__ size_t site_off_t(const Geom &g, const int x[4]) {
+  int t = x[3];
+  if (HALO) t = t < 0 ? t + g.X[3] + 6 : t;
+  int lex = x[0] + g.X[0] * (x[1] + g.X[1] * (x[2] + g.X[2] * t));
+  int p = (x[0] + x[1] + x[2] + x[3]) & 1;
+  int c = lex >> 1;
+  return ((size_t)p * g.etile + (c >> 6)) * 576 + (c & 63);
+}
 template <bool HALO>
 __device__ __forceinline__ void shifted_t(const Geom &g, const int x[4], int mu, int d, int y[4]) {
   y[0] = x[0]; y[1] = x[1]; y[2] = x[2]; y[3] = x[3];

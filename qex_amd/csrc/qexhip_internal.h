@@ -97,7 +97,18 @@ struct DevJoin {
                                          // prologue, anything else posts it first (devjoin_flush)
 };
 
-struct GaugeNat;  // natural-layout gauge field for plaquette / flow (gauge.hip)
+// natural-layout gauge field for plaquette / flow (gauge.hip) and gauge fixing (gaugefix.hip)
+struct GaugeNat {
+  double2 *U = nullptr, *F = nullptr, *P = nullptr;
+  double2 *U2 = nullptr;   // second link buffer: the fused flow stage reads U and writes exp(v) U here, then they swap
+  double2 *D2 = nullptr;   // double links U_a(x) U_a(x+a) of the rectangle force (k_double_links / k_force_rect)
+  size_t n2 = 0;  // double2 elements per field (incl. ghost tiles when t is sharded)
+  int ghost_valid = 0;   // depth to which the ghost slices of U are current
+  double *pp = nullptr; int npp = 0;   // per-workgroup plaquette partials of k_plaq
+  double2 *M = nullptr;      // resident MD momenta (qexhip_md_*)
+  double2 *Usave = nullptr;  // links saved around a force-gradient shift
+  int save_ghost_valid = 0;
+};
 struct PeerComm;  // peer-memory transport (peer.hip)
 
 enum { WK_SLOTS = 16 };   // >= WK_N (below)
@@ -129,7 +140,7 @@ struct qexhip_ctx {
   int part2_off = 0;
   double *dscal = nullptr;                           // 64 device scalars (reductions), by owner: [0..4] solvers (b2, r2, norms of
                                                      // the full solve), [8..9] the BLAS entry points, [16..21] plaquettes, [24..32]
-                                                     // flow observables / action / line sums, [40..51]
+                                                     // flow observables / action / line sums, [34] link trace (gaugefix.hip), [40..51]
                                                      // s4 / Polyakov sums, [56..59] comm_allreduce_max, [60] comm_init's agreement,
                                                      // [62] link-compression test
   CgScal *cg = nullptr;                              // device CG state
@@ -202,6 +213,8 @@ struct qexhip_ctx {
   void *f32 = nullptr;                               // F32State (dslash_f32.hip): fp32 links + fields + SlpScal of the mixed-precision CG
   void *batch_f32 = nullptr;                         // BatchF32State (batch_f32.hip): fp32 fields + SlpScal[4] of the mixed-precision batched CG
   void *msf32 = nullptr;                             // MsfState (multishift_f32.hip): fp32 search directions / increments of the mixed-precision multi-shift CG
+  void *gfix = nullptr;                              // GfState (gaugefix.hip): transform field t, polish scratch, device loop state
+  int opt_gfix_check = 16;                           // option "gfix_check": relax iterations posted between two read-backs of the gauge-fixing state
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -464,6 +477,17 @@ int gauge_plaq_s4(qexhip_ctx *c, double out[8]);
 void gauge_free(qexhip_ctx *c);
 void gauge_release_scratch(qexhip_ctx *c);
 const double2 *gauge_links_dev(qexhip_ctx *c);   // resident natural-layout links (nullptr before qexhip_gauge_set)
+int gauge_ghosts(qexhip_ctx *c, int depth);      // refresh the ghost slices of the resident links to at least `depth` (no-op unless t is sharded)
+int read_global(qexhip_ctx *c, double *dev, int n, double *host);   // rank-sum of n device scalars, then read back
+// ---- gaugefix.hip (src/gauge/gaugefix.nim) ----
+int gfix_set_transform(qexhip_ctx *c, const double *t);
+int gfix_get_transform(qexhip_ctx *c, double *t);
+int gfix_check_args(qexhip_ctx *c, const char *who, const int *dirs, int ndirs, int need_t);   // QEXHIP_ERR_ARG before anything is launched
+int gauge_fix(qexhip_ctx *c, const int *dirs, int ndirs, double gstop, double orf, int maxits, int *iters, double metrics[4],
+              double *hist, int histcap);
+int gauge_transform(qexhip_ctx *c);
+int gauge_link_trace(qexhip_ctx *c, const int *dirs, int ndirs, double *out);
+void gfix_state_free(qexhip_ctx *c);
 // ---- rng.hip (device-side generation) ----
 struct qexhip_rng;
 int rng_dev_generate(qexhip_ctx *c, qexhip_rng *R, int what, DevField *f, double2 *P);   // what: 0 gaussian vector, 1 u1 vector, 2 randomTAH -> P

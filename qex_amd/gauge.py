@@ -6,8 +6,18 @@ staggered phases, and synthetic configurations for benchmarks.
     rephase    src/physics/stagD.nim:72-80        setBC then stagPhase
 
 These are sign flips on host arrays (numpy); the arithmetic of the hot path is in libqexhip.
+
+Gauge fixing (src/gauge/gaugefix.nim) runs on the device, on the context's resident links (qex_amd.gaugeSet):
+
+    getGaugeFixTransform   src/gauge/gaugefix.nim:312-355
+    gaugeTransform         src/gauge/gaugefix.nim:8-20
+    linkTrace              src/gauge/gaugefix.nim:135-142
 """
+import ctypes as C
+
 import numpy as np
+
+from ._lib import check, lib
 
 
 def unit(lo):
@@ -98,3 +108,51 @@ def synthetic_repeated_su3(lat, t_block, seed=987654321, t_offset=0, t_global=No
         for par in range(2):
             g[par * vh + vh - f:(par + 1) * vh, 3] *= -1.0
     return g
+
+
+def _dirs(dirs):
+    d = [int(v) for v in dirs]
+    return (C.c_int * len(d))(*d), len(d)
+
+
+def getGaugeFixTransform(ctx, dirs, gstop=1e-5, orf=1.8, maxits=100000, verb=0, t0=None):
+    """getGaugeFixTransform(t, g, dirs, gstop, orf, verb) (gaugefix.nim:312-355) for the resident links, from t0 (None: t = 1).
+    dirs = [0, 1, 2] is Coulomb gauge, [0, 1, 2, 3] Landau gauge.  Returns (t, info): t is the (vol, 3, 3, 2) transform, which
+    stays resident for gaugeTransform(ctx); info holds iters, met, gre, gro, gdsq of the last evaluation and hist, the
+    (iters, 3) array of met, gre, gro before every update.  `maxits` bounds the updates (the reference has no bound; reaching it
+    is not an error).  verb > 0 prints the reference's [GFIX] lines every verb iterations, and the last evaluation."""
+    if t0 is not None and (t0.dtype != np.float64 or not t0.flags["C_CONTIGUOUS"]):
+        raise ValueError("fields must be C-contiguous float64 arrays")
+    check(lib().qexhip_gfix_set_transform(ctx._h, None if t0 is None else t0.ctypes.data_as(C.c_void_p)))
+    arr, n = _dirs(dirs)
+    its = C.c_int(0)
+    met = (C.c_double * 4)()
+    hist = np.zeros((max(int(maxits), 1), 3))
+    check(lib().qexhip_gauge_fix(ctx._h, arr, n, float(gstop), float(orf), int(maxits), C.byref(its), met,
+                                 hist.ctypes.data_as(C.POINTER(C.c_double)), int(maxits)))
+    hist = hist[:its.value].copy()
+    info = {"iters": its.value, "met": met[0], "gre": met[1], "gro": met[2], "gdsq": met[3], "hist": hist}
+    if verb > 0:
+        rows = [(k, *hist[k]) for k in range(0, its.value, int(verb))] + [(its.value, met[0], met[1], met[2])]
+        for k, m, ge, go in rows:
+            print("[GFIX] iterations: %d" % k)
+            print("[GFIX] link trace: %.16g" % m)
+            print("[GFIX] gradE: %.16g" % (2.0 * ge))
+            print("[GFIX] gradO: %.16g" % (2.0 * go))
+            print("[GFIX] grad:  %.16g" % (ge + go))
+    t = np.zeros((ctx.vol, 3, 3, 2))
+    check(lib().qexhip_gfix_get_transform(ctx._h, t.ctypes.data_as(C.c_void_p)))
+    return t, info
+
+
+def gaugeTransform(ctx):
+    """g.gaugeTransform(g, t) (gaugefix.nim:8-20) with the resident t on the resident links: g_mu(x) <- t(x) g_mu(x) t(x+mu)^+"""
+    check(lib().qexhip_gauge_transform(ctx._h))
+
+
+def linkTrace(ctx, dirs):
+    """linkTrace(g, dirs) (gaugefix.nim:135-142) of the resident links"""
+    arr, n = _dirs(dirs)
+    out = C.c_double(0)
+    check(lib().qexhip_gauge_link_trace(ctx._h, arr, n, C.byref(out)))
+    return out.value

@@ -101,6 +101,13 @@ proc qexhip_gauge_reunit(h: QexhipHandle): cint {.qh.}
 proc qexhip_wline(h: QexhipHandle; path: ptr cint; n: cint; o: ptr cdouble): cint {.qh.}
 proc qexhip_polyakov_loops(h: QexhipHandle; o: ptr cdouble): cint {.qh.}
 proc qexhip_plaq_s4(h: QexhipHandle; o: ptr cdouble): cint {.qh.}
+# gauge fixing (gauge/gaugefix.nim:8-20,135-142,312-355): t = nil is the identity; dirs [0,1,2] Coulomb, [0,1,2,3] Landau
+proc qexhip_gfix_set_transform(h: QexhipHandle; t: ptr cdouble): cint {.qh.}
+proc qexhip_gfix_get_transform(h: QexhipHandle; t: ptr cdouble): cint {.qh.}
+proc qexhip_gauge_fix(h: QexhipHandle; dirs: ptr cint; ndirs: cint; gstop, orf: cdouble; maxits: cint; iters: ptr cint;
+                      metrics, hist: ptr cdouble; histcap: cint): cint {.qh.}
+proc qexhip_gauge_transform(h: QexhipHandle): cint {.qh.}
+proc qexhip_gauge_link_trace(h: QexhipHandle; dirs: ptr cint; ndirs: cint; o: ptr cdouble): cint {.qh.}
 proc qexhip_io_read_gauge(path: cstring; lat: ptr cint; g: ptr cdouble; suma, sumb: ptr cuint): cint {.qh.}
 proc qexhip_rng_get_state(r: pointer; o: ptr cuint): cint {.qh.}
 proc qexhip_rng_set_state(r: pointer; i: ptr cuint): cint {.qh.}
