@@ -362,6 +362,76 @@ int qexhip_dev_sym_shift(qexhip_handle h, int r_id, int x_id, int mu);
 /* norm2slice (src/observables/sources.nim:10-18): out[v] = sum_{x: x_dir = v} |f(x)|^2 over the global extent of dir (dir 0..3) */
 int qexhip_dev_norm2slice(qexhip_handle h, int id, int dir, double *out);
 
+/* ---------------- low modes of the even/odd operator and deflated solves ----------------
+ * src/eigens/hisqev.nim: the lowest singular pairs (sv_i, v_i) of D_oe on the even sites (`hisqev` with EigOpts, hisqev.nim:380-560,
+ * block Lanczos of src/eigens/svdLanczos.nim + Rayleigh-Ritz passes), and the deflated solveEE of its main program (:653-705).
+ * Everything here lives on the EVEN sites.  The operator is H = -D_eo D_oe in this header's normalisation: qexhip_dev_op_xx(r, x, m2, 1)
+ * is 4 (m2 + H) x.  Eigenvalues are lambda_i = sv_i^2.  Whatever links the operator currently holds define H (newStag, newStag3, HISQ,
+ * nHYP).
+ *
+ * A BASIS is a resident set of nvecs half-volume vectors (even body sites only: half the memory of a field), identified by a small
+ * id like fields.  It remembers the links it was computed (or last written) on: using it after any set_links variant is
+ * QEXHIP_ERR_STATE in the deflated solves.  nvecs <= QEXHIP_EIG_MAX_NVECS (the largest m of the in-place rotation), else
+ * QEXHIP_ERR_ARG.  qexhip_release_workspace frees the eigensolver's work fields, never a basis; qexhip_finalize frees the bases.
+ *   get_vector / set_vector   field_id.even := v_i  /  v_i := field_id.even (the odd half of the field is not touched / not read)
+ * The three block kernels, as hooks for tests (the linear algebra of src/eigens/linalgFuncs.nim on sets of vectors):
+ *   block_dot    out[2 j], out[2 j + 1] = Re, Im of <v_{i0+j}, w.even>, j < n: one pass over the n vectors, w read once per 128 of them;
+ *                fp64 accumulation in a fixed order (bit-identical run to run); t-sharded: ONE rank sum of 2 n doubles
+ *   block_axpy   y.even += sum_j (coef[2 j] + i coef[2 j + 1]) v_{i0+j}: one pass over the n vectors, y read and written once
+ *   rotate       V[:, 0:k] <- V[:, 0:m] Q in place, Q real m x k column-major (Q[j + m c]), 1 <= k <= m <= nvecs.  Vectors k .. m-1
+ *                are LEFT AS THEY WERE (not zeroed, not orthogonal to the new ones): they are scratch afterwards. */
+#define QEXHIP_EIG_MAX_NVECS 512
+int qexhip_eig_new(qexhip_handle h, int nvecs, int *basis);
+int qexhip_eig_free(qexhip_handle h, int basis);
+int qexhip_eig_get_vector(qexhip_handle h, int basis, int i, int field_id);
+int qexhip_eig_set_vector(qexhip_handle h, int basis, int i, int field_id);
+int qexhip_eig_block_dot(qexhip_handle h, int basis, int i0, int n, int w_field_id, double *out);
+int qexhip_eig_block_axpy(qexhip_handle h, int basis, int i0, int n, const double *coef, int y_field_id);
+int qexhip_eig_rotate(qexhip_handle h, int basis, int m, int k, const double *Q);
+/* EigOpts (src/eigens/hisqev.nim: nev, nvecs, relerr, abserr, maxup) for the thick-restart Lanczos with Chebyshev acceleration:
+ *   nev, nvecs     pairs wanted / size of the Krylov basis (= vectors of the basis object used), 1 <= nev <= nvecs <= QEXHIP_EIG_MAX_NVECS
+ *   relerr, abserr a pair counts as converged when its residual |H v - lambda v| <= max(abserr, relerr * lambda)
+ *   max_restarts   thick restarts allowed (maxup); reaching it is not an error
+ *   cheb_degree    0: plain Lanczos on H; p > 0: Lanczos on T_p(s(H)), s mapping [cheb_lo, cheb_hi] onto [-1, 1]: cheb_lo is put
+ *                  just above the wanted eigenvalues, cheb_hi at or above the top of the spectrum; cheb_hi = 0: estimated as 1.1 x the
+ *                  largest Ritz value of 20 plain Lanczos steps
+ *   seed           of the start vector (the device Gaussian generator, one stream per GLOBAL site: runs repeat, for any rank count) */
+typedef struct qexhip_eig_opts {
+  int nev, nvecs;
+  double relerr, abserr;
+  int max_restarts, cheb_degree;
+  double cheb_lo, cheb_hi;
+  unsigned long long seed;
+} qexhip_eig_opts;
+/* the option checks of qexhip_stag_eigs alone: QEXHIP_ERR_ARG or 0.  Host only, no handle. */
+int qexhip_eig_check_opts(const qexhip_eig_opts *opts);
+/* hisqev (src/eigens/hisqev.nim): the nev lowest eigenpairs of H into vectors 0 .. nev-1 of `basis` (nvecs <= the basis's size; the
+ * other vectors are scratch), sorted ascending, each with |v_i| = 1.
+ *   nconv      pairs with resid_i <= max(abserr, relerr * evals_i)
+ *   evals[nev] Rayleigh quotients <v_i, H v_i>;  resid[nev] the TRUE residuals |H v_i - evals_i v_i|, recomputed with the fp64 operator
+ *   stats[4]   (may be NULL) operator applications, restarts, Lanczos steps, true-residual checks
+ * nconv < nev after max_restarts is not an error.  Bad options: QEXHIP_ERR_ARG before anything is launched.  t-sharded: collective,
+ * every reduction rank-global, every rank returns the same numbers and holds its slab of every vector. */
+int qexhip_stag_eigs(qexhip_handle h, int basis, const qexhip_eig_opts *opts, int *nconv, double *evals, double *resid, long stats[4]);
+/* the Rayleigh quotients the basis holds for its leading n vectors (computing those it lacks: vectors written by set_vector) */
+int qexhip_eig_evals(qexhip_handle h, int basis, int n, double *evals);
+/* The deflated solveEE of hisqev.nim:653-705 (`rsolve`): x0 = sum_{i<nev} v_i <v_i, b> / (4 (lambda_i + m^2)); r0 = b - A x0 in fp64;
+ * the EXISTING CG (sloppy = 0: qexhip_dev_solve_xx; 1: the mixed-precision one) on A d = r0 to r2req |b|^2 / |r0|^2; x = x0 + d.
+ * iters = the CG's iterations; r2_over_b2 = the true |b - A x|^2 / |b|^2.  nev = 0 gives exactly the bits and the iteration count of
+ * the undeflated entry.  Basis vectors are taken as orthonormal.  QEXHIP_ERR_STATE when the operator's links changed since the basis
+ * was computed.  dev_: resident fields (x_id != b_id); stag_: host fields.  solve_deflated: Staggered.solve (qexhip_stag_solve_sloppy
+ * semantics, use_prev = 0) whose inner solveEE calls deflate. */
+int qexhip_dev_solve_xx_deflated(qexhip_handle h, int basis, int nev, int x_id, int b_id, double mass, double r2req, int maxits,
+                                 int sloppy, int *iters, double *r2_over_b2);
+int qexhip_stag_solve_xx_deflated(qexhip_handle h, int basis, int nev, double *x, const double *b, double mass, double r2req,
+                                  int maxits, int sloppy, int *iters, double *r2_over_b2);
+int qexhip_stag_solve_deflated(qexhip_handle h, int basis, int nev, double *x, const double *b, double mass, double r2req, int maxits,
+                               int sloppy, int *iters, double *r2_final);
+/* Dense real symmetric eigensolver on the host (cyclic Jacobi, no external library): what the eigensolver diagonalises at every
+ * restart (the reference calls LAPACK there, src/eigens/lapack.nim).  a: n x n symmetric; w[n]: eigenvalues ascending; z (may be
+ * NULL): n x n column-major, column i the unit eigenvector of w[i].  Needs no device. */
+int qexhip_symeig_host(const double *a, int n, double *w, double *z);
+
 /* ---------------- gauge field, plaquette, Wilson flow ----------------
  * qexhip_gauge_set/get: the `g` of src/gauge/wflow.nim:21 (unphased links, periodic). */
 int qexhip_gauge_set(qexhip_handle h, const double *g);

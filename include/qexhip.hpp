@@ -194,6 +194,50 @@ class Staggered {
     SolverParams sp; sp.r2req = res * res; sp.maxits = 100000;
     solve(x, b, m, sp);
   }
+  // hisqev (src/eigens/hisqev.nim): the nev lowest eigenpairs of H = -D_eo D_oe on the even sites (eigenvalues = sv^2) in a resident
+  // basis of half-volume vectors; opts as EigOpts + the Chebyshev acceleration (qexhip_eig_opts).  The basis is freed with the object.
+  struct EigBasis {
+    Context &c; int id = 0, nconv = 0;
+    std::vector<double> evals, resid;
+    long stats[4] = {0, 0, 0, 0};        // operator applications, restarts, Lanczos steps, true-residual checks
+    EigBasis(Context &c_, int nvecs) : c(c_) { check(qexhip_eig_new(c.h, nvecs, &id)); }
+    ~EigBasis() { if (id) qexhip_eig_free(c.h, id); }
+    EigBasis(const EigBasis &) = delete;
+    EigBasis &operator=(const EigBasis &) = delete;
+    // v_i as a full-volume host field (odd sites zero) / v_i := the even half of a host field
+    void vector(int i, Field &out) const {
+      int f = 0; check(qexhip_field_new(c.h, &f));
+      int rc = qexhip_eig_get_vector(c.h, id, i, f);
+      if (rc == 0) rc = qexhip_field_download(c.h, f, out.data());
+      qexhip_field_free(c.h, f); check(rc);
+    }
+    void setVector(int i, const Field &in) {
+      int f = 0; check(qexhip_field_new(c.h, &f));
+      int rc = qexhip_field_upload(c.h, f, in.data());
+      if (rc == 0) rc = qexhip_eig_set_vector(c.h, id, i, f);
+      qexhip_field_free(c.h, f); check(rc);
+    }
+    // the three block kernels on a resident field (hooks): <v_j, w>, y += sum_j coef_j v_j, V[:, 0:k] <- V[:, 0:m] Q (column-major Q)
+    void blockDot(int i0, int n, int wField, double *out) const { check(qexhip_eig_block_dot(c.h, id, i0, n, wField, out)); }
+    void blockAxpy(int i0, int n, const double *coef, int yField) { check(qexhip_eig_block_axpy(c.h, id, i0, n, coef, yField)); }
+    void rotate(int m, int k, const double *Q) { check(qexhip_eig_rotate(c.h, id, m, k, Q)); }
+  };
+  void eigs(EigBasis &B, const qexhip_eig_opts &o) {
+    B.evals.assign(o.nev > 0 ? o.nev : 0, 0.0); B.resid = B.evals;
+    check(qexhip_stag_eigs(c_.h, B.id, &o, &B.nconv, B.evals.data(), B.resid.data(), B.stats));
+  }
+  // the deflated solveEE of hisqev.nim:653-705 with the leading nev vectors of B; sp.r2 = the TRUE residual
+  void solveEE(Field &r, const Field &x, double m, SolverParams &sp, const EigBasis &B, int nev) {
+    int its = 0; double fin = 0;
+    timed(sp, its, [&] { check(qexhip_stag_solve_xx_deflated(c_.h, B.id, nev, r.data(), x.data(), m, sp.r2req, sp.maxits, sp.sloppySolve, &its, &fin)); });
+    sp.r2 = fin; sp.r2hist.clear();
+  }
+  // Staggered.solve whose inner solveEE calls deflate
+  void solve(Field &x, const Field &b, double m, SolverParams &sp, const EigBasis &B, int nev) {
+    int its = 0; double fin = 0;
+    timed(sp, its, [&] { check(qexhip_stag_solve_deflated(c_.h, B.id, nev, x.data(), b.data(), m, sp.r2req, sp.maxits, sp.sloppySolve, &its, &fin)); });
+    sp.r2 = fin;
+  }
   // n <= 4 independent solves on these links in lock-step (one stream of the links per sweep for all of them);
   // per system the result of solve(x[j], b[j], m[j], sps[j]).  sloppy = -1: fp64, and a sloppy SolverParams is refused (as before);
   // 0, 1, 2: the precision of the batch, chosen explicitly (qexhip_stag_solve_batch_sloppy; one rank only when > 0), overriding

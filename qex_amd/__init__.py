@@ -10,7 +10,7 @@ from .gauge import setBC, stagPhase, rephase, unit, synthetic_random_su3, synthe
 from .gauge import getGaugeFixTransform, gaugeTransform, linkTrace  # noqa: F401
 from .staggered import (  # noqa: F401
     Context, device_count, Staggered, SolverParams, newStag, newStag3, link_residual_host, plaq, gaugeForce, gaugeFlow, gaugeSet, gaugeFlowResident, flowEQ, flowMeasure, gaugeAction, gaugeUpdate, reunit, wline, ploops, s4_gauge, ResidentMD, HisqCoefs, HypCoefs, makeImpLinks, fat7lDeriv, EVEN, ODD, ALL,
-    SloppyNone, SloppySingle, SloppyHalf,
+    SloppyNone, SloppySingle, SloppyHalf, EigBasis, EigOpts, eig_check_opts, symeig_host,
 )
 from .io import loadGauge, loadGaugeSlab, saveGauge, getFileLattice, gaugeFileInfo, writeField, readField, fileMetadata  # noqa: F401
 from .rng import RngField, RngMilc6, MRG32k3a  # noqa: F401

@@ -74,6 +74,20 @@ SYMBOLS = [
     ("qexhip_dev_solve_xx_multi", _ci, [_vp, _pi, _ci, _pd, _ci, _cd, _ci, _ci, _pi, _vp, _ci]),
     ("qexhip_dev_solve_xx_multi_sloppy", _ci, [_vp, _pi, _ci, _pd, _ci, _cd, _ci, _ci, _ci, _pi, _pd, _pi, _pi]),
     ("qexhip_release_workspace", _ci, [_vp]),
+    ("qexhip_eig_new", _ci, [_vp, _ci, _pi]),
+    ("qexhip_eig_free", _ci, [_vp, _ci]),
+    ("qexhip_eig_get_vector", _ci, [_vp, _ci, _ci, _ci]),
+    ("qexhip_eig_set_vector", _ci, [_vp, _ci, _ci, _ci]),
+    ("qexhip_eig_block_dot", _ci, [_vp, _ci, _ci, _ci, _ci, _vp]),
+    ("qexhip_eig_block_axpy", _ci, [_vp, _ci, _ci, _ci, _vp, _ci]),
+    ("qexhip_eig_rotate", _ci, [_vp, _ci, _ci, _ci, _vp]),
+    ("qexhip_eig_check_opts", _ci, [_vp]),
+    ("qexhip_stag_eigs", _ci, [_vp, _ci, _vp, _pi, _vp, _vp, C.POINTER(C.c_long)]),
+    ("qexhip_eig_evals", _ci, [_vp, _ci, _ci, _vp]),
+    ("qexhip_dev_solve_xx_deflated", _ci, [_vp, _ci, _ci, _ci, _ci, _cd, _cd, _ci, _ci, _pi, _pd]),
+    ("qexhip_stag_solve_xx_deflated", _ci, [_vp, _ci, _ci, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),
+    ("qexhip_stag_solve_deflated", _ci, [_vp, _ci, _ci, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),
+    ("qexhip_symeig_host", _ci, [_pd, _ci, _pd, _pd]),   # data pointer, not a handle
     ("qexhip_dev_norm2", _ci, [_vp, _ci, _ci, _pd]),
     ("qexhip_dev_redot", _ci, [_vp, _ci, _ci, _ci, _pd]),
     ("qexhip_dev_D", _ci, [_vp, _ci, _ci, _cd, _cd]),

@@ -186,6 +186,8 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   batch_f32_state_free(c);
   msf_state_free(c);
   gfix_state_free(c);
+  eig_state_free(c);
+  eig_bases_free(c);
   gauge_free(c);
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
@@ -759,7 +761,141 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   msf_state_free(c);                 // and the mixed multi-shift CG's fp32 search directions / increments
   batch_f32_state_free(c);           // and the batched form's fp32 fields
   gfix_state_free(c);                // and the gauge-fixing transform with its polish scratch (qexhip_gfix_set_transform re-creates it)
+  eig_state_free(c);                 // and the eigensolver's Lanczos work fields and buffers (never the user's bases)
   return 0;
+}
+
+// ---- low modes and deflation (eig.hip, eigsolve.cpp, solver.cpp) ----
+extern "C" int qexhip_eig_new(qexhip_handle c, int nvecs, int *basis) {
+  if (nvecs < 1 || nvecs > EIG_MAX_NVECS) { qexhip_set_error("eig_new: 1 <= nvecs <= %d (nvecs = %d)", EIG_MAX_NVECS, nvecs); return QEXHIP_ERR_ARG; }
+  if (!c || !basis) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  return eig_basis_new(c, nvecs, basis);
+}
+extern "C" int qexhip_eig_free(qexhip_handle c, int basis) {
+  if (!c) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  return eig_basis_free(c, basis);
+}
+extern "C" int qexhip_eig_get_vector(qexhip_handle c, int basis, int i, int field_id) {
+  if (!c) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevField *f;
+  CHK(eig_basis_find(c, basis, &B));
+  CHK(find_field(c, field_id, &f));
+  HIPCHK(hipSetDevice(c->device));
+  return eig_get_vector(c, *B, i, *f);
+}
+extern "C" int qexhip_eig_set_vector(qexhip_handle c, int basis, int i, int field_id) {
+  if (!c) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevField *f;
+  CHK(eig_basis_find(c, basis, &B));
+  CHK(find_field(c, field_id, &f));
+  HIPCHK(hipSetDevice(c->device));
+  return eig_set_vector(c, *B, i, *f);
+}
+extern "C" int qexhip_eig_block_dot(qexhip_handle c, int basis, int i0, int n, int w_field_id, double *out) {
+  if (!c || !out) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevField *f;
+  CHK(eig_basis_find(c, basis, &B));
+  CHK(find_field(c, w_field_id, &f));
+  if (i0 < 0 || n < 1 || i0 > B->nvecs - n) { qexhip_set_error("eig_block_dot: vectors %d..%d of a basis of %d", i0, i0 + n - 1, B->nvecs); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  double2 *dots;
+  CHK(eig_coef_buffers(c, &dots, nullptr));
+  CHK(eig_block_dot(c, *B, i0, n, *f, dots));
+  HIPCHK(hipMemcpyAsync(out, dots, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return peer_check(c);
+}
+extern "C" int qexhip_eig_block_axpy(qexhip_handle c, int basis, int i0, int n, const double *coef, int y_field_id) {
+  if (!c || !coef) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevField *f;
+  CHK(eig_basis_find(c, basis, &B));
+  CHK(find_field(c, y_field_id, &f));
+  if (i0 < 0 || n < 1 || i0 > B->nvecs - n) { qexhip_set_error("eig_block_axpy: vectors %d..%d of a basis of %d", i0, i0 + n - 1, B->nvecs); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  double2 *cf;
+  CHK(eig_coef_buffers(c, nullptr, &cf));
+  HIPCHK(hipMemcpyAsync(cf, coef, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  CHK(eig_block_axpy(c, *B, i0, n, cf, 1.0, *f));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int qexhip_eig_rotate(qexhip_handle c, int basis, int m, int k, const double *Q) {
+  if (!c || !Q) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(eig_basis_find(c, basis, &B));
+  HIPCHK(hipSetDevice(c->device));
+  CHK(eig_rotate(c, *B, m, k, Q));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int qexhip_stag_eigs(qexhip_handle c, int basis, const qexhip_eig_opts *o, int *nconv, double *evals, double *resid, long stats[4]) {
+  CHK(qexhip_eig_check_opts(o));
+  if (!c) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(eig_basis_find(c, basis, &B));
+  if (o->nvecs > B->nvecs) { qexhip_set_error("eigs: nvecs = %d but the basis holds %d vectors", o->nvecs, B->nvecs); return QEXHIP_ERR_ARG; }
+  if (!c->W) { qexhip_set_error("eigs: no links set"); return QEXHIP_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  return eig_solve(c, *B, *o, nconv, evals, resid, stats);
+}
+extern "C" int qexhip_eig_evals(qexhip_handle c, int basis, int n, double *evals) {
+  if (!c || !evals) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(eig_basis_find(c, basis, &B));
+  if (n < 0 || n > B->nvecs) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  CHK(eig_rayleigh(c, *B, n));
+  for (int i = 0; i < n; i++) evals[i] = B->evals[i];
+  return 0;
+}
+static int deflate_args(qexhip_ctx *c, int basis, int nev, int sloppy, double mass, EigBasis **B) {
+  CHK(sloppy_check(c, sloppy));
+  CHK(eig_basis_find(c, basis, B));
+  if (nev < 0 || nev > (*B)->nvecs) { qexhip_set_error("deflated solve: nev = %d of a basis of %d vectors", nev, (*B)->nvecs); return QEXHIP_ERR_ARG; }
+  if (sloppy && mass == 0.0) { qexhip_set_error("sloppy solve: mass 0 unsupported"); return QEXHIP_ERR_ARG; }
+  return 0;
+}
+extern "C" int qexhip_dev_solve_xx_deflated(qexhip_handle c, int basis, int nev, int x_id, int b_id, double mass, double r2req, int maxits,
+                                            int sloppy, int *iters, double *r2_over_b2) {
+  if (!c) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(deflate_args(c, basis, nev, sloppy, mass, &B));
+  DevField *fx, *fb;
+  CHK(find_field(c, x_id, &fx));
+  CHK(find_field(c, b_id, &fb));
+  if (x_id == b_id) { qexhip_set_error("dev_solve_xx_deflated: the solution field is the source field"); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  return solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2_over_b2);
+}
+extern "C" int qexhip_stag_solve_xx_deflated(qexhip_handle c, int basis, int nev, double *x, const double *b, double mass, double r2req,
+                                             int maxits, int sloppy, int *iters, double *r2_over_b2) {
+  if (!c || !x || !b) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(deflate_args(c, basis, nev, sloppy, mass, &B));
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb, *fx;
+  CHK(host_in(c, WK_IN, b, &fb));
+  CHK(get_work(c, WK_OUT, &fx));
+  CHK(solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2_over_b2));
+  return field_download(c, *fx, x);
+}
+extern "C" int qexhip_stag_solve_deflated(qexhip_handle c, int basis, int nev, double *x, const double *b, double mass, double r2req,
+                                          int maxits, int sloppy, int *iters, double *r2_final) {
+  if (!c || !x || !b) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(deflate_args(c, basis, nev, sloppy, mass, &B));
+  if (B->gen != c->links_gen) { qexhip_set_error("deflated solve: the basis was computed on other links"); return QEXHIP_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fb, *fx;
+  CHK(host_in(c, WK_IN, b, &fb));
+  CHK(get_work(c, WK_OUT, &fx));
+  c->deflate_basis = basis; c->deflate_nev = nev;
+  const int rc = solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, 0, sloppy ? 1 : 0, nullptr);
+  c->deflate_basis = 0; c->deflate_nev = 0;
+  CHK(rc);
+  return field_download(c, *fx, x);
 }
 
 // norm2 / redot / Staggered.D on resident fields (the host-pointer forms above upload their arguments first)

@@ -111,6 +111,17 @@ struct GaugeNat {
 };
 struct PeerComm;  // peer-memory transport (peer.hip)
 
+// A resident basis of half-volume vectors (eig.hip): nvecs vectors of the EVEN parity's body tiles only, each in the vec_off layout
+// ([tile][3][64] double2, n2 = ntile*192 elements, spare lanes of a ragged last tile zero), contiguous per vector.
+struct EigBasis {
+  double2 *v = nullptr;
+  int nvecs = 0;
+  size_t n2 = 0;
+  unsigned long gen = 0;        // c->links_gen its vectors were computed / last set on
+  std::vector<double> evals;    // Rayleigh quotients <v_i, H v_i> of the leading nevals vectors (H = -D_eo D_oe)
+  int nevals = 0;
+};
+
 enum { WK_SLOTS = 16 };   // >= WK_N (below)
 
 struct qexhip_ctx {
@@ -215,6 +226,9 @@ struct qexhip_ctx {
   void *msf32 = nullptr;                             // MsfState (multishift_f32.hip): fp32 search directions / increments of the mixed-precision multi-shift CG
   void *gfix = nullptr;                              // GfState (gaugefix.hip): transform field t, polish scratch, device loop state
   int opt_gfix_check = 16;                           // option "gfix_check": relax iterations posted between two read-backs of the gauge-fixing state
+  std::map<int, EigBasis> bases; int next_basis = 1; // the user's eigenvector bases (qexhip_eig_new)
+  void *eig = nullptr;                               // EigWork (eig.hip): Lanczos work fields, coefficient / partial / Q buffers
+  int deflate_basis = 0, deflate_nev = 0;            // set around a deflated full solve: its inner solveEE calls deflate with this basis
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -422,6 +436,32 @@ int solve_xx_multi_sloppy_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevFie
 // persistent multi-shift workspace (multishift.hip): search directions, per-parity solutions, host-entry solutions
 enum { POOL_PS = 0, POOL_YS = 32, POOL_XS = 64, POOL_REF = 96 };   // POOL_REF: 4 corrections + 4 residuals of the sloppy solve's refinement
 int pool_field(qexhip_ctx *c, int idx, DevField **f);
+
+int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevField &b, double mass, double r2req, int maxits,
+                          int sloppy, int *iters, double *r2_over_b2);
+
+// ---- eig.hip: basis of half-volume vectors + the three block kernels; eigsolve.cpp: thick-restart Lanczos ----
+#define EIG_MAX_NVECS 512       // the in-place rotation keeps m x R site rows in LDS with R >= 16: m <= 512 at 128 KiB
+enum { EIG_W = 0, EIG_T0, EIG_T1, EIG_AP, EIG_R0, EIG_D, EIG_NF };   // EigWork fields
+int eig_basis_find(qexhip_ctx *c, int id, EigBasis **B);
+int eig_basis_new(qexhip_ctx *c, int nvecs, int *id);
+int eig_basis_free(qexhip_ctx *c, int id);
+void eig_bases_free(qexhip_ctx *c);                 // qexhip_finalize
+void eig_state_free(qexhip_ctx *c);                 // the work fields and buffers only (qexhip_release_workspace)
+int eig_field(qexhip_ctx *c, int slot, DevField **f);
+int eig_coef_buffers(qexhip_ctx *c, double2 **dots, double2 **coef);      // EIG_MAX_NVECS complex numbers each, on the device
+int eig_get_vector(qexhip_ctx *c, const EigBasis &B, int i, DevField &f, double scale = 1.0);   // f.even := scale v_i
+int eig_set_vector(qexhip_ctx *c, EigBasis &B, int i, const DevField &f, double scale = 1.0);   // v_i := scale f.even
+int eig_move_vector(qexhip_ctx *c, EigBasis &B, int dst, int src);
+// dots[j] = <v_{i0+j}, w.even>, j < n, rank-global, on the device
+int eig_block_dot(qexhip_ctx *c, const EigBasis &B, int i0, int n, const DevField &w, double2 *dots);
+// y.even += scale * sum_j coef[j] v_{i0+j}
+int eig_block_axpy(qexhip_ctx *c, const EigBasis &B, int i0, int n, const double2 *coef, double scale, DevField &y);
+// V[:, 0:k] <- V[:, 0:m] Q, Q real m x k column-major on the host
+int eig_rotate(qexhip_ctx *c, EigBasis &B, int m, int k, const double *Q);
+int eig_rayleigh(qexhip_ctx *c, EigBasis &B, int n);     // fills B.evals[0..n) where missing (one operator application each)
+struct qexhip_eig_opts;
+int eig_solve(qexhip_ctx *c, EigBasis &B, const qexhip_eig_opts &o, int *nconv, double *evals, double *resid, long stats[4]);
 
 // ---- force.hip ----
 int stag_outer_host(qexhip_ctx *c, double *f_host, const double *x_host, double se, double so, int accumulate);

@@ -389,9 +389,76 @@ int solve_xx_multi_sloppy_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevFie
   return 0;
 }
 
-// the inner solveXX of the full solve: fp64 CG, or the mixed-precision one (sloppy > 0)
+// ---- deflated solveXX (src/eigens/hisqev.nim:653-705, `rsolve` of its main program) ----
+// With low modes (v_i, lambda_i) of H = -D_eo D_oe on the even sites, A = 4 (m^2 + H):
+//   1. x0 = sum_i v_i <v_i, b> / (4 (lambda_i + m^2))               block dot + block axpy (eig.hip)
+//   2. r0 = b - A x0                                                   fp64
+//   3. A d = r0 to r2req |b|^2 / |r0|^2                                the EXISTING fp64 / mixed-precision CG
+//   4. x = x0 + d;  r2_over_b2 = the true |b - A x|^2 / |b|^2
+// nev = 0 is the undeflated solver itself (same bits, same iteration count).
+int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevField &b, double mass, double r2req, int maxits,
+                          int sloppy, int *iters, double *r2_over_b2) {
+  if (nev < 0 || nev > B.nvecs) { qexhip_set_error("deflated solve: nev = %d of a basis of %d vectors", nev, B.nvecs); return QEXHIP_ERR_ARG; }
+  if (B.gen != c->links_gen) {
+    qexhip_set_error("deflated solve: the basis was computed on other links (the operator's links changed since)");
+    return QEXHIP_ERR_STATE;
+  }
+  if (nev == 0) {
+    if (!sloppy) return solve_xx_dev(c, x, b, mass, r2req, maxits, 1, iters, r2_over_b2, nullptr, 0);
+    return solve_xx_sloppy_dev(c, x, b, mass, r2req, maxits, 1, iters, r2_over_b2, nullptr);
+  }
+  const double m2 = mass * mass;
+  CHK(eig_rayleigh(c, B, nev));
+  double2 *dots, *coef;
+  CHK(eig_coef_buffers(c, &dots, &coef));
+  DevField *r0, *d, *Ax;
+  CHK(eig_field(c, EIG_R0, &r0));
+  CHK(eig_field(c, EIG_D, &d));
+  CHK(eig_field(c, EIG_AP, &Ax));
+  std::vector<double2> h(nev);
+  CHK(eig_block_dot(c, B, 0, nev, b, dots));
+  HIPCHK(hipMemcpyAsync(h.data(), dots, sizeof(double2) * nev, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < nev; i++) {
+    const double s = 0.25 / (B.evals[i] + m2);
+    h[i].x *= s; h[i].y *= s;
+  }
+  HIPCHK(hipMemcpyAsync(coef, h.data(), sizeof(double2) * nev, hipMemcpyHostToDevice, c->stream));
+  CHK(blas_zero(c, x, 2));
+  CHK(eig_block_axpy(c, B, 0, nev, coef, 1.0, x));
+  HIPCHK(hipStreamSynchronize(c->stream));              // (h is read by the copy above)
+  CHK(op_xx(c, *Ax, x, m2, 1, 0, nullptr));
+  CHK(blas_axpby(c, 1.0, b, -1.0, *Ax, *r0, 0));
+  CHK(blas_norm2(c, b, 0, &c->dscal[2]));
+  CHK(blas_norm2(c, *r0, 0, &c->dscal[3]));
+  double n[2];
+  CHK(read_scalars(c, &c->dscal[2], 2, n));
+  const double b2 = n[0];
+  int its = 0;
+  if (b2 > 0 && n[1] > r2req * b2) {
+    const double rq = r2req * b2 / n[1];
+    if (!sloppy) CHK(solve_xx_dev(c, *d, *r0, mass, rq, maxits, 1, &its, nullptr, nullptr, 0));
+    else CHK(solve_xx_sloppy_dev(c, *d, *r0, mass, rq, maxits, 1, &its, nullptr, nullptr));
+    CHK(blas_axpy(c, 1.0, *d, x, 0));
+    CHK(op_xx(c, *Ax, x, m2, 1, 0, nullptr));
+    CHK(blas_axpby(c, 1.0, b, -1.0, *Ax, *r0, 0));
+    CHK(blas_norm2(c, *r0, 0, &c->dscal[3]));
+    CHK(read_scalars(c, &c->dscal[3], 1, &n[1]));
+  }
+  if (iters) *iters = its;
+  if (r2_over_b2) *r2_over_b2 = b2 != 0.0 ? n[1] / b2 : 0.0;
+  return 0;
+}
+
+// the inner solveXX of the full solve: fp64 CG, or the mixed-precision one (sloppy > 0); even-parity solves deflate with the basis a
+// deflated full solve has set
 static int inner_xx(qexhip_ctx *c, DevField &x, DevField &b, double m, double r2req, int maxits, int par_even, int *its,
                     int sloppy, int *nupd) {
+  if (par_even && c->deflate_nev > 0) {
+    EigBasis *B;
+    CHK(eig_basis_find(c, c->deflate_basis, &B));
+    return solve_xx_deflated_dev(c, *B, c->deflate_nev, x, b, m, r2req, maxits, sloppy ? 1 : 0, its, nullptr);
+  }
   if (!sloppy) return solve_xx_dev(c, x, b, m, r2req, maxits, par_even, its, nullptr, nullptr, 0);
   int nu = 0;
   CHK(solve_xx_sloppy_dev(c, x, b, m, r2req, maxits, par_even, its, nullptr, &nu));

@@ -108,6 +108,31 @@ proc qexhip_gauge_fix(h: QexhipHandle; dirs: ptr cint; ndirs: cint; gstop, orf: 
                       metrics, hist: ptr cdouble; histcap: cint): cint {.qh.}
 proc qexhip_gauge_transform(h: QexhipHandle): cint {.qh.}
 proc qexhip_gauge_link_trace(h: QexhipHandle; dirs: ptr cint; ndirs: cint; o: ptr cdouble): cint {.qh.}
+# low modes and deflation (eigens/hisqev.nim): a basis of half-volume vectors on the even sites, the three block kernels as hooks,
+# the eigensolver (EigOpts + Chebyshev acceleration) and the deflated solveEE / solve of hisqev.nim:653-705
+type QexhipEigOpts* {.bycopy.} = object
+  nev*, nvecs*: cint
+  relerr*, abserr*: cdouble
+  max_restarts*, cheb_degree*: cint
+  cheb_lo*, cheb_hi*: cdouble
+  seed*: culonglong
+proc qexhip_eig_new(h: QexhipHandle; nvecs: cint; basis: ptr cint): cint {.qh.}
+proc qexhip_eig_free(h: QexhipHandle; basis: cint): cint {.qh.}
+proc qexhip_eig_get_vector(h: QexhipHandle; basis, i, field: cint): cint {.qh.}
+proc qexhip_eig_set_vector(h: QexhipHandle; basis, i, field: cint): cint {.qh.}
+proc qexhip_eig_block_dot(h: QexhipHandle; basis, i0, n, wField: cint; o: ptr cdouble): cint {.qh.}
+proc qexhip_eig_block_axpy(h: QexhipHandle; basis, i0, n: cint; coef: ptr cdouble; yField: cint): cint {.qh.}
+proc qexhip_eig_rotate(h: QexhipHandle; basis, m, k: cint; Q: ptr cdouble): cint {.qh.}
+proc qexhip_eig_check_opts(o: ptr QexhipEigOpts): cint {.qh.}
+proc qexhip_stag_eigs(h: QexhipHandle; basis: cint; o: ptr QexhipEigOpts; nconv: ptr cint; evals, resid: ptr cdouble; stats: ptr clong): cint {.qh.}
+proc qexhip_eig_evals(h: QexhipHandle; basis, n: cint; evals: ptr cdouble): cint {.qh.}
+proc qexhip_dev_solve_xx_deflated(h: QexhipHandle; basis, nev, x, b: cint; mass, r2req: cdouble; maxits, sloppy: cint; iters: ptr cint;
+                                  r2: ptr cdouble): cint {.qh.}
+proc qexhip_stag_solve_xx_deflated(h: QexhipHandle; basis, nev: cint; x, b: ptr cdouble; mass, r2req: cdouble; maxits, sloppy: cint;
+                                   iters: ptr cint; r2: ptr cdouble): cint {.qh.}
+proc qexhip_stag_solve_deflated(h: QexhipHandle; basis, nev: cint; x, b: ptr cdouble; mass, r2req: cdouble; maxits, sloppy: cint;
+                                iters: ptr cint; r2: ptr cdouble): cint {.qh.}
+proc qexhip_symeig_host(a: ptr cdouble; n: cint; w, z: ptr cdouble): cint {.qh.}
 proc qexhip_io_read_gauge(path: cstring; lat: ptr cint; g: ptr cdouble; suma, sumb: ptr cuint): cint {.qh.}
 proc qexhip_rng_get_state(r: pointer; o: ptr cuint): cint {.qh.}
 proc qexhip_rng_set_state(r: pointer; i: ptr cuint): cint {.qh.}

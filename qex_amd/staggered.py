@@ -246,6 +246,14 @@ class Context:
                                                1 if par_even else 0, int(sloppy), C.byref(its), C.byref(fin), C.byref(nup)))
         return its.value, fin.value, nup.value
 
+    def dev_solve_xx_deflated(self, basis, nev, x_id, b_id, mass, r2req, maxits, sloppy=SloppyNone):
+        """the deflated solveEE of hisqev.nim:653-705 on resident fields with the leading nev vectors of an EigBasis
+        (qexhip_dev_solve_xx_deflated); returns (CG iterations, true |b - A x|^2/|b|^2)"""
+        its, fin = C.c_int(0), C.c_double(0)
+        check(lib().qexhip_dev_solve_xx_deflated(self._h, int(basis.id), int(nev), int(x_id), int(b_id), float(mass), float(r2req),
+                                                 int(maxits), int(sloppy), C.byref(its), C.byref(fin)))
+        return its.value, fin.value
+
     def dev_op_xx_sloppy(self, r_id, x_id, m2, par_even=True):
         """r[par] = 4 m2 x - (2D)(2D) x with the sloppy solve's fp32 links and sweep (x rounded to fp32, the result back to fp64)"""
         check(lib().qexhip_dev_op_xx_sloppy(self._h, int(r_id), int(x_id), float(m2), 1 if par_even else 0))
@@ -353,8 +361,116 @@ class Context:
         check(lib().qexhip_xpay(self._h, _p(x), a, _p(y), _SUBSET[subset]))
 
 
+class EigOpts(C.Structure):
+    """qexhip_eig_opts: EigOpts of src/eigens/hisqev.nim (nev, nvecs, relerr, abserr, maxup) + the Chebyshev acceleration"""
+    _fields_ = [("nev", C.c_int), ("nvecs", C.c_int), ("relerr", C.c_double), ("abserr", C.c_double), ("max_restarts", C.c_int),
+                ("cheb_degree", C.c_int), ("cheb_lo", C.c_double), ("cheb_hi", C.c_double), ("seed", C.c_ulonglong)]
+
+
+def eig_check_opts(**kw):
+    """the option checks of Staggered.eigs alone (host only): the library's return code, 0 or QEXHIP_ERR_ARG (-1)"""
+    o = EigOpts(**kw)
+    return lib().qexhip_eig_check_opts(C.byref(o))
+
+
+def symeig_host(a):
+    """qexhip_symeig_host: (w ascending, z with z[:, i] the eigenvector of w[i]) of a real symmetric matrix; no device needed"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    n = a.shape[0] if a.ndim == 2 else 0
+    if a.ndim != 2 or a.shape[1] != n:
+        raise ValueError("symeig_host: a square matrix")
+    w, z = np.zeros(n), np.zeros((n, n))
+    pd = C.POINTER(C.c_double)
+    check(lib().qexhip_symeig_host(a.ctypes.data_as(pd), n, w.ctypes.data_as(pd), z.ctypes.data_as(pd)))
+    return w, np.ascontiguousarray(z.T)       # the library's z is column-major
+
+
+class EigBasis:
+    """A resident basis of nvecs half-volume vectors on the even sites (qexhip_eig_new).  Staggered.eigs fills `evals`, `resid`,
+    `nconv` and `stats`; `vector(i)` downloads v_i as a full-volume host field (odd sites zero)."""
+
+    def __init__(self, ctx, nvecs):
+        self.ctx, self.nvecs = ctx, int(nvecs)
+        bid = C.c_int(0)
+        check(lib().qexhip_eig_new(ctx._h, self.nvecs, C.byref(bid)))
+        self.id = bid.value
+        self.evals, self.resid, self.nconv, self.stats = np.zeros(0), np.zeros(0), 0, {}
+
+    def free(self):
+        if self.id:
+            check(lib().qexhip_eig_free(self.ctx._h, self.id))
+            self.id = 0
+
+    def get_vector(self, i, field_id):
+        check(lib().qexhip_eig_get_vector(self.ctx._h, self.id, int(i), int(field_id)))
+
+    def set_vector(self, i, field):
+        """v_i := the even half of a resident field (id) or of a host array"""
+        if isinstance(field, np.ndarray):
+            fid = self.ctx.field_new(field)
+            try:
+                check(lib().qexhip_eig_set_vector(self.ctx._h, self.id, int(i), fid))
+            finally:
+                self.ctx.field_free(fid)
+        else:
+            check(lib().qexhip_eig_set_vector(self.ctx._h, self.id, int(i), int(field)))
+
+    def vector(self, i):
+        fid = self.ctx.field_new()
+        try:
+            self.get_vector(i, fid)
+            return self.ctx.field_download(fid)
+        finally:
+            self.ctx.field_free(fid)
+
+    def block_dot(self, i0, n, w_id):
+        """[<v_j, w.even> for j in i0 .. i0+n-1] with w a resident field: complex array"""
+        out = np.zeros(2 * n)
+        check(lib().qexhip_eig_block_dot(self.ctx._h, self.id, int(i0), int(n), int(w_id), out.ctypes.data))
+        return out[0::2] + 1j * out[1::2]
+
+    def block_axpy(self, i0, coef, y_id):
+        """y.even += sum_j coef[j] v_{i0+j} on the resident field y"""
+        cf = np.asarray(coef, dtype=np.complex128)
+        buf = np.ascontiguousarray(np.stack([cf.real, cf.imag], axis=-1))
+        check(lib().qexhip_eig_block_axpy(self.ctx._h, self.id, int(i0), len(cf), buf.ctypes.data, int(y_id)))
+
+    def rotate(self, Q):
+        """V[:, 0:k] <- V[:, 0:m] Q in place, Q real (m, k); vectors k .. m-1 are scratch afterwards"""
+        Q = np.asarray(Q, dtype=np.float64)
+        m, k = Q.shape
+        qf = np.asfortranarray(Q)
+        check(lib().qexhip_eig_rotate(self.ctx._h, self.id, m, k, qf.ctypes.data))
+
+    def rayleigh(self, n):
+        ev = np.zeros(n)
+        check(lib().qexhip_eig_evals(self.ctx._h, self.id, int(n), ev.ctypes.data))
+        return ev
+
+
 class Staggered:
     """Staggered[G,T] (stagD.nim:19-22): the links `g` carry BC and phases (rephase)."""
+
+    def eigs(self, nev, nvecs=None, relerr=1e-4, abserr=1e-6, max_restarts=100, cheb_degree=0, cheb_lo=0.0, cheb_hi=0.0,
+             seed=987654321, basis=None):
+        """hisqev (src/eigens/hisqev.nim): the nev lowest eigenpairs of H = -D_eo D_oe on the even sites (eigenvalues = sv^2), by
+        thick-restart Lanczos on T_p(H) (qexhip_stag_eigs).  Returns an EigBasis (a new one of nvecs vectors unless `basis` is given)
+        with evals (ascending), resid (true residuals), nconv, stats."""
+        nvecs = int(nvecs) if nvecs is not None else max(2 * int(nev), int(nev) + 8)
+        o = EigOpts(int(nev), nvecs, float(relerr), float(abserr), int(max_restarts), int(cheb_degree), float(cheb_lo), float(cheb_hi), int(seed))
+        check(lib().qexhip_eig_check_opts(C.byref(o)))
+        B = basis if basis is not None else EigBasis(self.ctx, nvecs)
+        ev, rs = np.zeros(nev), np.zeros(nev)
+        nc, st = C.c_int(0), (C.c_long * 4)()
+        try:
+            check(lib().qexhip_stag_eigs(self.ctx._h, B.id, C.byref(o), C.byref(nc), ev.ctypes.data, rs.ctypes.data, st))
+        except Exception:
+            if basis is None:
+                B.free()
+            raise
+        B.evals, B.resid, B.nconv = ev, rs, nc.value
+        B.stats = dict(zip(("op_applications", "restarts", "lanczos_steps", "residual_checks"), [int(v) for v in st]))
+        return B
 
     def __init__(self, ctx, g, g3=None, smear=None, bc="pppa"):
         """smear = None: g (, g3) are the final links.  smear = HisqCoefs(): the operator uses the
@@ -449,13 +565,22 @@ class Staggered:
         # (s.g.len*4*72+60)*nEven*iterations  (stagSolve.nim:92)
         return float((self.nlinks * 4 * 72 + 60) * (self.ctx.vol // 2) * its)
 
-    def solveXX(self, r, x, m, sp, parEven=True, histcap=0):
-        """solveXX(s, r, x, m, sp0, parEven) (stagSolve.nim:57-132): r <- solution, x = rhs."""
+    def solveXX(self, r, x, m, sp, parEven=True, histcap=0, deflate=None, nev=None):
+        """solveXX(s, r, x, m, sp0, parEven) (stagSolve.nim:57-132): r <- solution, x = rhs.
+        deflate = an EigBasis (even sites only): the deflated solve of hisqev.nim:653-705 with its leading nev vectors (default: the
+        pairs Staggered.eigs returned); sp.r2 is then the TRUE residual and no history is kept."""
         t0 = time.time()
         its, fin = C.c_int(0), C.c_double(0)
         hist = np.zeros(max(histcap, 1))
         sloppy = int(getattr(sp, "sloppySolve", SloppyNone))
-        if sloppy != SloppyNone:
+        if deflate is not None:
+            if not parEven:
+                raise ValueError("deflate= applies to the even sites (solveEE)")
+            n = len(deflate.evals) if nev is None else int(nev)
+            check(lib().qexhip_stag_solve_xx_deflated(self.ctx._h, deflate.id, n, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
+                                                      sloppy, C.byref(its), C.byref(fin)))
+            histcap = 0
+        elif sloppy != SloppyNone:
             # mixed precision (no residual history: the fp32 iterations' residuals are not the true ones)
             nup = C.c_int(0)
             check(lib().qexhip_stag_solve_xx_sloppy(self.ctx._h, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
@@ -475,17 +600,33 @@ class Staggered:
         if sp.verbosity > 1:
             print(("solveEE" if parEven else "solveOO") + "(HIP): " + sp.getStats())
 
-    def solveEE(self, r, x, m, sp, histcap=0):
-        self.solveXX(r, x, m, sp, True, histcap)
+    def solveEE(self, r, x, m, sp, histcap=0, deflate=None, nev=None):
+        self.solveXX(r, x, m, sp, True, histcap, deflate=deflate, nev=nev)
 
     def solveOO(self, r, x, m, sp, histcap=0):
         self.solveXX(r, x, m, sp, False, histcap)
 
-    def solve(self, x, b, m, sp, sloppy=None):
+    def solve(self, x, b, m, sp, sloppy=None, deflate=None, nev=None):
         """Staggered.solve: x (array or list of arrays) <- D(m)^-1 b  (stagSolve.nim:224-294,347-446).
+        deflate = an EigBasis (single mass, from x = 0): the inner solveEE calls deflate with its leading nev vectors.
         sloppy (mass lists only): None = fp64, and a SolverParams that asks for a sloppy solve is refused; 0, 1 or 2 = the precision
         of the inner multi-shift CG, chosen explicitly whatever sp says (qexhip_stag_solve_multi_sloppy)."""
         multi = isinstance(x, (list, tuple))
+        if deflate is not None:
+            if multi or sloppy is not None or sp.usePrevSoln:
+                raise ValueError("deflate= applies to single-mass solves from x = 0 (precision from sp.sloppySolve)")
+            t0 = time.time()
+            its, fin = C.c_int(0), C.c_double(0)
+            n = len(deflate.evals) if nev is None else int(nev)
+            check(lib().qexhip_stag_solve_deflated(self.ctx._h, deflate.id, n, _p(x), _p(b), float(m), float(sp.r2req), int(sp.maxits),
+                                                   int(getattr(sp, "sloppySolve", SloppyNone)), C.byref(its), C.byref(fin)))
+            sp.calls += 1
+            sp.iterations += its.value
+            sp.iterationsMax = max(sp.iterationsMax, its.value)
+            sp.seconds += time.time() - t0
+            sp.flops += self._flops(its.value)
+            sp.r2 = fin.value
+            return
         if sloppy is not None:
             sloppy = _batch_sloppy(sloppy)
             if not multi:
