@@ -362,6 +362,33 @@ int qexhip_dev_sym_shift(qexhip_handle h, int r_id, int x_id, int mu);
 /* norm2slice (src/observables/sources.nim:10-18): out[v] = sum_{x: x_dir = v} |f(x)|^2 over the global extent of dir (dir 0..3) */
 int qexhip_dev_norm2slice(qexhip_handle h, int id, int dir, double *out);
 
+/* ---------------- stochastic scalar trace on resident fields ----------------
+ * The pieces of src/observables/scalarTrace.nim (disconnected pbp: Tr (D+m)^-1(x,x) from diluted noise sources) between the noise
+ * fill (qexhip_rng_dev_*_vector) and the batched solves (qexhip_dev_solve_batch*).
+ *
+ * A "cfield" is a resident complex site field (lo.Complex, 16 B per site), identified by small positive ids of its own.  It is
+ * created zeroed; scale multiplies every site by the real s; download returns [site][2] (re, im) in the site order of
+ * qexhip_field_download (V=1 even-odd order of the rank-local lattice).  qexhip_finalize frees what is left. */
+int qexhip_cfield_new(qexhip_handle h, int *id);
+int qexhip_cfield_free(qexhip_handle h, int id);
+int qexhip_cfield_zero(qexhip_handle h, int id);
+int qexhip_cfield_scale(qexhip_handle h, int id, double s);
+int qexhip_cfield_download(qexhip_handle h, int id, double *host);
+/* Time + pattern dilution (src/algorithms/dilution.nim, scalarTrace.nim:169-185) of src into n <= 4 colour vectors in one launch:
+ *   dst_k(x) = scale * src(x)  where the GLOBAL time of x is t[k] and x belongs to pattern idx[k];  +0.0 elsewhere
+ * kind 0 (EO):     idx in 0..1, the global parity (x0+x1+x2+t)&1
+ * kind 1 (CORNER): idx in 0..7, (x0&1) | (x1&1)<<1 | (x2&1)<<2
+ * The destinations are distinct fields, none of them src.  On a t-sharded context a rank that does not own t[k] zeroes dst_k. */
+int qexhip_dev_dilute(qexhip_handle h, int n, const int *dst_ids, int src_id, int kind, const int *idx, const int *t, double scale);
+/* trce(x) += coef * sum_colour conj(a_k(x)) b_k(x) for k = 0..n-1 (n <= 4) in one launch; the n terms are added one at a time in
+ * ascending k, so the result is bit for bit that of n calls with one pair each.  a_ids[k] == b_ids[k] (the improved trace
+ * mass * phi.dot phi, scalarTrace.nim:195-198) loads the vector once and adds an imaginary part of exactly 0. */
+int qexhip_dev_trace_accum(qexhip_handle h, int cfield, int n, const int *a_ids, const int *b_ids, double coef);
+/* out[2*t], out[2*t+1] = Re, Im of the sum of the cfield over the global time slice t; out holds 2 * (global t extent) doubles.
+ * Rank-global; the summation order is fixed and every entry is computed on the rank that owns its slice, so the table is
+ * bit-identical run to run and for any number of ranks. */
+int qexhip_dev_cfield_slices(qexhip_handle h, int cfield, double *out);
+
 /* ---------------- low modes of the even/odd operator and deflated solves ----------------
  * src/eigens/hisqev.nim: the lowest singular pairs (sv_i, v_i) of D_oe on the even sites (`hisqev` with EigOpts, hisqev.nim:380-560,
  * block Lanczos of src/eigens/svdLanczos.nim + Rayleigh-Ritz passes), and the deflated solveEE of its main program (:653-705).
@@ -703,6 +730,10 @@ int qexhip_rng_free(qexhip_rng *rng);
 int qexhip_rng_uniform(qexhip_rng *rng, int ncomp, double *v);
 int qexhip_rng_gaussian_vector(qexhip_rng *rng, double *v);
 int qexhip_rng_u1_vector(qexhip_rng *rng, double *v);
+/* v.z4 r / v.z2 r (distributionUtils.nim:102-180, without FUELCompat): one uniform u per colour component;
+ * z4: u < 0.25 -> 1, < 0.5 -> i, < 0.75 -> -1, else -i;  z2: u < 0.5 -> 1, else -1 */
+int qexhip_rng_z4_vector(qexhip_rng *rng, double *v);
+int qexhip_rng_z2_vector(qexhip_rng *rng, double *v);
 int qexhip_rng_random_tah(qexhip_rng *rng, double *p);
 int qexhip_rng_gauge_random(qexhip_rng *rng, double *g);
 int qexhip_rng_gauge_warm(qexhip_rng *rng, double s, double *g);
@@ -725,6 +756,9 @@ int qexhip_rng_set_state(qexhip_rng *rng, const unsigned *in);
  *                        keeps them, qexhip_md_momentum_norm2 gives 2 T + const. */
 int qexhip_rng_dev_gaussian_vector(qexhip_handle h, qexhip_rng *rng, int field_id);
 int qexhip_rng_dev_u1_vector(qexhip_handle h, qexhip_rng *rng, int field_id);
+/* z4 / z2 noise: the values are exact, so field and generator state equal the host fill's bit for bit */
+int qexhip_rng_dev_z4_vector(qexhip_handle h, qexhip_rng *rng, int field_id);
+int qexhip_rng_dev_z2_vector(qexhip_handle h, qexhip_rng *rng, int field_id);
 int qexhip_md_refresh_momenta(qexhip_handle h, qexhip_rng *rng);
 
 /* ---------------- resident molecular dynamics ----------------

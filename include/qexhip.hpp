@@ -329,6 +329,41 @@ inline double linkTrace(Context &c, const std::vector<int> &dirs) {
   check(qexhip_gauge_link_trace(c.h, dirs.data(), (int)dirs.size(), &r));
   return r;
 }
+// The complex site field `trce` of scalarTrace.nim, resident on the device, with the accumulation and slice sums on it; field
+// arguments are ids of resident colour vectors (qexhip_field_new).
+class TraceField {
+  Context &c_;
+ public:
+  int id = 0;
+  explicit TraceField(Context &c) : c_(c) { check(qexhip_cfield_new(c.h, &id)); }
+  ~TraceField() { if (id) qexhip_cfield_free(c_.h, id); }
+  TraceField(const TraceField &) = delete;
+  void zero() { check(qexhip_cfield_zero(c_.h, id)); }
+  void scale(double s) { check(qexhip_cfield_scale(c_.h, id, s)); }
+  // trce += coef * a_k.dot b_k, k ascending (at most four pairs a call)
+  void accum(const std::vector<int> &a, const std::vector<int> &b, double coef = 1.0) {
+    if (a.size() != b.size()) throw Error("TraceField::accum: a and b differ in length");
+    check(qexhip_dev_trace_accum(c_.h, id, (int)a.size(), a.data(), b.data(), coef));
+  }
+  std::vector<std::complex<double>> slices(int ntGlobal) {
+    std::vector<double> o(2 * (size_t)ntGlobal);
+    check(qexhip_dev_cfield_slices(c_.h, id, o.data()));
+    std::vector<std::complex<double>> r(ntGlobal);
+    for (int t = 0; t < ntGlobal; t++) r[t] = {o[2 * t], o[2 * t + 1]};
+    return r;
+  }
+  void download(Field &out) {
+    out.resize((size_t)c_.lo.nSites * 2);
+    check(qexhip_cfield_download(c_.h, id, out.data()));
+  }
+};
+enum DilutionKind { dkEvenOdd = 0, dkCorners3D = 1 };     // src/algorithms/dilution.nim
+// dst_k = scale * src on the sites of global time t[k] in pattern idx[k], zero elsewhere (at most four destinations a call)
+inline void dilute(Context &c, const std::vector<int> &dst, int src, DilutionKind kind, const std::vector<int> &idx, const std::vector<int> &t,
+                   double scale = 1.0) {
+  if (dst.size() != idx.size() || dst.size() != t.size()) throw Error("dilute: dst, idx and t differ in length");
+  check(qexhip_dev_dilute(c.h, (int)dst.size(), dst.data(), src, (int)kind, idx.data(), t.data(), scale));
+}
 // g.gaugeFlow(steps, eps): measure(wflowT)  (wflow.nim:21-67); g is modified in place
 template <class Measure>
 inline void gaugeFlow(Context &c, Field &g, int steps, double eps, Measure &&measure) {

@@ -141,11 +141,15 @@ SYMBOLS = [
     ("qexhip_rng_uniform", _ci, [_vp, _ci, _vp]),
     ("qexhip_rng_gaussian_vector", _ci, [_vp, _vp]),
     ("qexhip_rng_u1_vector", _ci, [_vp, _vp]),
+    ("qexhip_rng_z4_vector", _ci, [_vp, _vp]),
+    ("qexhip_rng_z2_vector", _ci, [_vp, _vp]),
     ("qexhip_rng_random_tah", _ci, [_vp, _vp]),
     ("qexhip_rng_gauge_random", _ci, [_vp, _vp]),
     ("qexhip_rng_gauge_warm", _ci, [_vp, _cd, _vp]),
     ("qexhip_rng_dev_gaussian_vector", _ci, [_vp, _vp, _ci]),
     ("qexhip_rng_dev_u1_vector", _ci, [_vp, _vp, _ci]),
+    ("qexhip_rng_dev_z4_vector", _ci, [_vp, _vp, _ci]),
+    ("qexhip_rng_dev_z2_vector", _ci, [_vp, _vp, _ci]),
     ("qexhip_md_refresh_momenta", _ci, [_vp, _vp]),
     ("qexhip_dev_zero", _ci, [_vp, _ci, _ci]),
     ("qexhip_dev_solve_batch", _ci, [_vp, _ci, _pi, _pi, _pd, _pd, _ci, _pi, _pd]),
@@ -153,6 +157,14 @@ SYMBOLS = [
     ("qexhip_dev_meson_corners", _ci, [_vp, _ci, _pi, _pi, _ci, _vp]),
     ("qexhip_dev_sym_shift", _ci, [_vp, _ci, _ci, _ci]),
     ("qexhip_dev_norm2slice", _ci, [_vp, _ci, _ci, _vp]),
+    ("qexhip_cfield_new", _ci, [_vp, _pi]),
+    ("qexhip_cfield_free", _ci, [_vp, _ci]),
+    ("qexhip_cfield_zero", _ci, [_vp, _ci]),
+    ("qexhip_cfield_scale", _ci, [_vp, _ci, _cd]),
+    ("qexhip_cfield_download", _ci, [_vp, _ci, _vp]),
+    ("qexhip_dev_dilute", _ci, [_vp, _ci, _pi, _ci, _ci, _pi, _pi, _cd]),
+    ("qexhip_dev_trace_accum", _ci, [_vp, _ci, _ci, _pi, _pi, _cd]),
+    ("qexhip_dev_cfield_slices", _ci, [_vp, _ci, _vp]),
     ("qexhip_nhyp_fforce_dev", _ci, [_vp, _vp, _ci, _pi, _pd, _pd, _pd, _ci, _pi, _pi, _pi]),
     ("qexhip_rng_state_words", _ci, [_vp]),
     ("qexhip_rng_get_state", _ci, [_vp, _vp]),

@@ -188,6 +188,8 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   gfix_state_free(c);
   eig_state_free(c);
   eig_bases_free(c);
+  for (auto &kv : c->cfields) (void)hipFree(kv.second.d);
+  c->cfields.clear();
   gauge_free(c);
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
@@ -970,6 +972,97 @@ extern "C" int qexhip_dev_norm2slice(qexhip_handle c, int id, int dir, double *o
   return norm2slice(c, *f, dir, out);
 }
 
+// ---- stochastic scalar trace (scalarTrace.nim, dilution.nim): complex site fields, dilution, <a, b> accumulation, slice sums ----
+static int find_cfield(qexhip_ctx *c, int id, DevCField **f) {
+  auto it = c->cfields.find(id);
+  if (id <= 0 || it == c->cfields.end()) { qexhip_set_error("unknown cfield id %d", id); return QEXHIP_ERR_ARG; }
+  *f = &it->second;
+  return 0;
+}
+extern "C" int qexhip_cfield_new(qexhip_handle c, int *id) {
+  if (!c || !id) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  DevCField f;
+  CHK(cfield_alloc(c, f));
+  *id = c->next_cfield++;
+  c->cfields[*id] = f;
+  return 0;
+}
+extern "C" int qexhip_cfield_free(qexhip_handle c, int id) {
+  if (!c) return QEXHIP_ERR_ARG;
+  DevCField *f;
+  CHK(find_cfield(c, id, &f));
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipFree(f->d));
+  c->cfields.erase(id);
+  return 0;
+}
+extern "C" int qexhip_cfield_zero(qexhip_handle c, int id) {
+  if (!c) return QEXHIP_ERR_ARG;
+  DevCField *f;
+  CHK(find_cfield(c, id, &f));
+  HIPCHK(hipSetDevice(c->device));
+  return cfield_zero(c, *f);
+}
+extern "C" int qexhip_cfield_scale(qexhip_handle c, int id, double s) {
+  if (!c) return QEXHIP_ERR_ARG;
+  DevCField *f;
+  CHK(find_cfield(c, id, &f));
+  HIPCHK(hipSetDevice(c->device));
+  return cfield_scale(c, *f, s);
+}
+extern "C" int qexhip_cfield_download(qexhip_handle c, int id, double *host) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!host) { qexhip_set_error("cfield_download: null argument"); return QEXHIP_ERR_ARG; }
+  DevCField *f;
+  CHK(find_cfield(c, id, &f));
+  HIPCHK(hipSetDevice(c->device));
+  return cfield_download(c, *f, host);
+}
+extern "C" int qexhip_dev_dilute(qexhip_handle c, int n, const int *dst_ids, int src_id, int kind, const int *idx, const int *t,
+                                 double scale) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!dst_ids || !idx || !t) { qexhip_set_error("dev_dilute: null argument"); return QEXHIP_ERR_ARG; }
+  if (n < 1 || n > 4) { qexhip_set_error("dev_dilute: n = %d, must be 1..4", n); return QEXHIP_ERR_ARG; }
+  if (kind < 0 || kind > 1) { qexhip_set_error("dev_dilute: kind = %d, must be 0 (EO) or 1 (CORNER)", kind); return QEXHIP_ERR_ARG; }
+  const int ntg = c->g.X[3] * c->rankGeom[3], npat = kind == 0 ? 2 : 8;
+  DevField *src, *dst[4];
+  CHK(find_field(c, src_id, &src));
+  for (int k = 0; k < n; k++) {
+    if (idx[k] < 0 || idx[k] >= npat) { qexhip_set_error("dev_dilute: idx[%d] = %d outside [0, %d)", k, idx[k], npat); return QEXHIP_ERR_ARG; }
+    if (t[k] < 0 || t[k] >= ntg) { qexhip_set_error("dev_dilute: t[%d] = %d outside [0, %d)", k, t[k], ntg); return QEXHIP_ERR_ARG; }
+    if (dst_ids[k] == src_id) { qexhip_set_error("dev_dilute: destination %d is the source field %d", k, src_id); return QEXHIP_ERR_ARG; }
+    for (int j = 0; j < k; j++)
+      if (dst_ids[j] == dst_ids[k]) { qexhip_set_error("dev_dilute: destinations %d and %d are the same field %d", j, k, dst_ids[k]); return QEXHIP_ERR_ARG; }
+    CHK(find_field(c, dst_ids[k], &dst[k]));
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return trace_dilute(c, n, dst, *src, kind, idx, t, scale);
+}
+extern "C" int qexhip_dev_trace_accum(qexhip_handle c, int cfield, int n, const int *a_ids, const int *b_ids, double coef) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!a_ids || !b_ids) { qexhip_set_error("dev_trace_accum: null argument"); return QEXHIP_ERR_ARG; }
+  if (n < 1 || n > 4) { qexhip_set_error("dev_trace_accum: n = %d, must be 1..4", n); return QEXHIP_ERR_ARG; }
+  DevCField *tr;
+  CHK(find_cfield(c, cfield, &tr));
+  DevField *a[4], *b[4];
+  for (int k = 0; k < n; k++) {
+    CHK(find_field(c, a_ids[k], &a[k]));
+    CHK(find_field(c, b_ids[k], &b[k]));
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return trace_accum(c, *tr, n, a, b, coef);
+}
+extern "C" int qexhip_dev_cfield_slices(qexhip_handle c, int cfield, double *out) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!out) { qexhip_set_error("dev_cfield_slices: null argument"); return QEXHIP_ERR_ARG; }
+  DevCField *tr;
+  CHK(find_cfield(c, cfield, &tr));
+  HIPCHK(hipSetDevice(c->device));
+  return cfield_slices(c, *tr, out);
+}
+
 // ---- link smearing ----
 extern "C" int qexhip_fat7(qexhip_handle c, const double *g, const double coef[5], double *fl, double *ll, double naik) {
   if (!c || !g || !coef || !fl) return QEXHIP_ERR_ARG;
@@ -1182,6 +1275,18 @@ extern "C" int qexhip_rng_dev_u1_vector(qexhip_handle c, qexhip_rng *rng, int fi
   DevField *f;
   CHK(find_field(c, field_id, &f));
   return rng_dev_generate(c, rng, 1, f, nullptr);
+}
+extern "C" int qexhip_rng_dev_z4_vector(qexhip_handle c, qexhip_rng *rng, int field_id) {
+  if (!c || !rng) return QEXHIP_ERR_ARG;
+  DevField *f;
+  CHK(find_field(c, field_id, &f));
+  return rng_dev_generate(c, rng, 3, f, nullptr);
+}
+extern "C" int qexhip_rng_dev_z2_vector(qexhip_handle c, qexhip_rng *rng, int field_id) {
+  if (!c || !rng) return QEXHIP_ERR_ARG;
+  DevField *f;
+  CHK(find_field(c, field_id, &f));
+  return rng_dev_generate(c, rng, 4, f, nullptr);
 }
 extern "C" int qexhip_md_refresh_momenta(qexhip_handle c, qexhip_rng *rng) {
   if (!c || !rng) return QEXHIP_ERR_ARG;

@@ -130,7 +130,9 @@ __global__ void __launch_bounds__(256) k_norm2slice(Geom g, const double2 *f0, c
   if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-// scratch of the three entry points: [partials | global table]
+}  // namespace
+
+// scratch of the table reductions (here and in trace.hip): [partials | global table]
 int meson_scratch(qexhip_ctx *c, size_t npart, size_t nout, double **part, double **out) {
   const size_t need = npart + nout;
   if (c->meson_cap < need) {
@@ -145,13 +147,17 @@ int meson_scratch(qexhip_ctx *c, size_t npart, size_t nout, double **part, doubl
   return 0;
 }
 
-int read_table(qexhip_ctx *c, const double *dev, size_t n, double *host) {
+int meson_read_table(qexhip_ctx *c, const double *dev, size_t n, double *host) {
   HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return peer_check(c);
 }
 
-}  // namespace
+int meson_bins_final(qexhip_ctx *c, const double *partials, int nbin, int nsub, int nchunk, int off, int t0, int nglob, double *out) {
+  k_bins_final<<<1, 256, 0, c->stream>>>(partials, nbin, nsub, nchunk, off, t0, nglob, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 int meson_corners(qexhip_ctx *c, int n, DevField *const *x, DevField *const *y, int t0, double *host_out) {
   const Geom &g = c->g;
@@ -170,7 +176,7 @@ int meson_corners(qexhip_ctx *c, int n, DevField *const *x, DevField *const *y, 
     HIPCHK(hipGetLastError());
   }
   if (multi_rank(c)) CHK(comm_allreduce(c, out, ntg * 8));
-  return read_table(c, out, (size_t)ntg * 8, host_out);
+  return meson_read_table(c, out, (size_t)ntg * 8, host_out);
 }
 
 int norm2slice(qexhip_ctx *c, const DevField &f, int dir, double *host_out) {
@@ -188,7 +194,7 @@ int norm2slice(qexhip_ctx *c, const DevField &f, int dir, double *host_out) {
     HIPCHK(hipGetLastError());
   }
   if (multi_rank(c)) CHK(comm_allreduce(c, out, lg));
-  return read_table(c, out, (size_t)lg, host_out);
+  return meson_read_table(c, out, (size_t)lg, host_out);
 }
 
 int sym_shift(qexhip_ctx *c, DevField &r, const DevField &x, int mu) {

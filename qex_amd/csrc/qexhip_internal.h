@@ -52,6 +52,12 @@ struct DevFieldF {  // fp32 colour vector of the mixed-precision CG: float2 v[ti
   float2 *par(int p) const { return d + (size_t)p * half; }
 };
 
+struct DevCField {  // complex site field (trace.hip): double2 d[parity][ntile*64], site c of a parity at index c; no ghost slices
+  double2 *d = nullptr;
+  size_t half = 0;  // double2 elements per parity half (= ntile*64)
+  double2 *par(int p) const { return d + (size_t)p * half; }
+};
+
 // state of the reliable-update CG (dslash_f32.hip, solver.cpp: solve_xx_sloppy_dev), resident on the device
 struct SlpScal {
   double b2, r2stop;
@@ -229,6 +235,7 @@ struct qexhip_ctx {
   std::map<int, EigBasis> bases; int next_basis = 1; // the user's eigenvector bases (qexhip_eig_new)
   void *eig = nullptr;                               // EigWork (eig.hip): Lanczos work fields, coefficient / partial / Q buffers
   int deflate_basis = 0, deflate_nev = 0;            // set around a deflated full solve: its inner solveEE calls deflate with this basis
+  std::map<int, DevCField> cfields; int next_cfield = 1;   // the user's complex site fields (qexhip_cfield_new)
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -471,6 +478,20 @@ int meson_corners(qexhip_ctx *c, int n, DevField *const *x, DevField *const *y, 
 int sym_shift(qexhip_ctx *c, DevField &r, const DevField &x, int mu);                                      // mu < 3, links set
 int norm2slice(qexhip_ctx *c, const DevField &f, int dir, double *host_out);                                // [L_dir global], rank-global
 
+int meson_scratch(qexhip_ctx *c, size_t npart, size_t nout, double **part, double **out);                      // device scratch [partials | table]
+int meson_bins_final(qexhip_ctx *c, const double *partials, int nbin, int nsub, int nchunk, int off, int t0, int nglob, double *out);
+                                                                       // k_bins_final: chunk-ordered sums into the rows of the global table
+int meson_read_table(qexhip_ctx *c, const double *dev, size_t n, double *host);
+
+// ---- trace.hip: dilution, site-wise trace accumulation and slice sums of the stochastic scalar trace ----
+int cfield_alloc(qexhip_ctx *c, DevCField &f);
+int cfield_zero(qexhip_ctx *c, DevCField &f);
+int cfield_scale(qexhip_ctx *c, DevCField &f, double s);
+int cfield_download(qexhip_ctx *c, const DevCField &f, double *host);                 // [V][2] in the site order of field_download
+int trace_dilute(qexhip_ctx *c, int n, DevField *const *dst, const DevField &src, int kind, const int *idx, const int *t, double scale);
+int trace_accum(qexhip_ctx *c, DevCField &tr, int n, DevField *const *a, DevField *const *b, double coef);
+int cfield_slices(qexhip_ctx *c, const DevCField &tr, double *host_out);              // [nt_global][2], rank-global
+
 // ---- smear.hip ----
 int smear_fat7_host(qexhip_ctx *c, const double *g_host, const double coef[5], double *fl_host, double *ll_host, double naik);
 int smear_hisq_host(qexhip_ctx *c, const double *g_host, double *fl_host, double *ll_host);
@@ -530,5 +551,6 @@ int gauge_link_trace(qexhip_ctx *c, const int *dirs, int ndirs, double *out);
 void gfix_state_free(qexhip_ctx *c);
 // ---- rng.hip (device-side generation) ----
 struct qexhip_rng;
-int rng_dev_generate(qexhip_ctx *c, qexhip_rng *R, int what, DevField *f, double2 *P);   // what: 0 gaussian vector, 1 u1 vector, 2 randomTAH -> P
+int rng_dev_generate(qexhip_ctx *c, qexhip_rng *R, int what, DevField *f, double2 *P);   // what: 0 gaussian vector, 1 u1 vector, 2 randomTAH -> P,
+                                                                                         // 3 z4 vector, 4 z2 vector
 int md_momenta_dev(qexhip_ctx *c, double2 **M);                                          // resident MD momenta (allocated on demand)

@@ -201,6 +201,28 @@ extern "C" int qexhip_rng_u1_vector(qexhip_rng *R, double *v) {
   });
   return 0;
 }
+// v.z4 r / v.z2 r (distributionUtils.nim:102-180, the non-FUELCompat branch): one uniform per colour component
+extern "C" int qexhip_rng_z4_vector(qexhip_rng *R, double *v) {
+  if (!R || !v) return QEXHIP_ERR_ARG;
+  for_sites(R->vol, [&](size_t j) {
+    for (int k = 0; k < 3; k++) {
+      const double n = R->uniform(j);
+      v[6 * j + 2 * k] = n < 0.5 ? (n < 0.25 ? 1.0 : 0.0) : (n < 0.75 ? -1.0 : 0.0);
+      v[6 * j + 2 * k + 1] = n < 0.5 ? (n < 0.25 ? 0.0 : 1.0) : (n < 0.75 ? 0.0 : -1.0);
+    }
+  });
+  return 0;
+}
+extern "C" int qexhip_rng_z2_vector(qexhip_rng *R, double *v) {
+  if (!R || !v) return QEXHIP_ERR_ARG;
+  for_sites(R->vol, [&](size_t j) {
+    for (int k = 0; k < 3; k++) {
+      v[6 * j + 2 * k] = R->uniform(j) < 0.5 ? 1.0 : -1.0;
+      v[6 * j + 2 * k + 1] = 0.0;
+    }
+  });
+  return 0;
+}
 // p.randomTAH r: gauge-shaped field [vol][4][3][3][2], direction by direction
 extern "C" int qexhip_rng_random_tah(qexhip_rng *R, double *p) {
   if (!R || !p) return QEXHIP_ERR_ARG;
@@ -279,7 +301,7 @@ __device__ __forceinline__ double milc6_gaussian(uint32_t *w) {
   const double r = sqrt(-2.0 * log(v + 9.999999999999999e-308));
   return (double)(float)(r * cos(p));
 }
-// what: 0 gaussian colour vector, 1 u1 colour vector (-> field v, one parity half after the other);
+// what: 0 gaussian, 1 u1, 3 z4, 4 z2 colour vector (-> field v, one parity half after the other);
 //       2 randomTAH (-> natural-layout matrix field P: [parity][tile][mu][9][64])
 __global__ void __launch_bounds__(256) k_rng_milc6(Geom g, uint32_t *__restrict__ state, int what, double2 *v, size_t vhalf, double2 *P) {
   const int i = blockIdx.x * 256 + threadIdx.x;          // host site index j = c + parity * Vh
@@ -309,9 +331,15 @@ __global__ void __launch_bounds__(256) k_rng_milc6(Geom g, uint32_t *__restrict_
         const double re = milc6_gaussian(w);
         const double im = milc6_gaussian(w);
         d[k * 64] = make_double2(re, im);
-      } else {
+      } else if (what == 1) {
         const double n = 2.0 * 3.14159265358979323846 * (double)milc6_uniform(w);
         d[k * 64] = make_double2(cos(n), sin(n));
+      } else if (what == 3) {
+        const float n = milc6_uniform(w);
+        d[k * 64] = n < 0.5f ? (n < 0.25f ? make_double2(1.0, 0.0) : make_double2(0.0, 1.0))
+                             : (n < 0.75f ? make_double2(-1.0, 0.0) : make_double2(0.0, -1.0));
+      } else {
+        d[k * 64] = make_double2(milc6_uniform(w) < 0.5f ? 1.0 : -1.0, 0.0);
       }
     }
   }

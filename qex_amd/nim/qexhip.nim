@@ -78,6 +78,19 @@ proc qexhip_stag_solve_batch(h: QexhipHandle; n: cint; x, b: ptr ptr cdouble; ma
 proc qexhip_dev_meson_corners(h: QexhipHandle; n: cint; xIds, yIds: ptr cint; t0: cint; o: ptr cdouble): cint {.qh.}
 proc qexhip_dev_sym_shift(h: QexhipHandle; rId, xId, mu: cint): cint {.qh.}
 proc qexhip_dev_norm2slice(h: QexhipHandle; id, dir: cint; o: ptr cdouble): cint {.qh.}
+# stochastic scalar trace on resident fields (scalarTrace.nim, dilution.nim): complex site fields, dilution, accumulation, slice sums
+proc qexhip_cfield_new(h: QexhipHandle; id: ptr cint): cint {.qh.}
+proc qexhip_cfield_free(h: QexhipHandle; id: cint): cint {.qh.}
+proc qexhip_cfield_zero(h: QexhipHandle; id: cint): cint {.qh.}
+proc qexhip_cfield_scale(h: QexhipHandle; id: cint; s: cdouble): cint {.qh.}
+proc qexhip_cfield_download(h: QexhipHandle; id: cint; host: ptr cdouble): cint {.qh.}
+proc qexhip_dev_dilute(h: QexhipHandle; n: cint; dstIds: ptr cint; srcId, kind: cint; idx, t: ptr cint; scale: cdouble): cint {.qh.}
+proc qexhip_dev_trace_accum(h: QexhipHandle; cfield, n: cint; aIds, bIds: ptr cint; coef: cdouble): cint {.qh.}
+proc qexhip_dev_cfield_slices(h: QexhipHandle; cfield: cint; o: ptr cdouble): cint {.qh.}
+proc qexhip_rng_z4_vector(r: pointer; v: ptr cdouble): cint {.qh.}
+proc qexhip_rng_z2_vector(r: pointer; v: ptr cdouble): cint {.qh.}
+proc qexhip_rng_dev_z4_vector(h: QexhipHandle; r: pointer; fieldId: cint): cint {.qh.}
+proc qexhip_rng_dev_z2_vector(h: QexhipHandle; r: pointer; fieldId: cint): cint {.qh.}
 proc qexhip_gauge_set(h: QexhipHandle; g: ptr cdouble): cint {.qh.}
 proc qexhip_gauge_get(h: QexhipHandle; g: ptr cdouble): cint {.qh.}
 proc qexhip_plaq(h: QexhipHandle; o: ptr cdouble): cint {.qh.}

@@ -46,6 +46,18 @@ class RngField:
         check(lib().qexhip_rng_u1_vector(self._h, v.ctypes.data_as(C.c_void_p)))
         return v
 
+    def z4_vector(self):
+        """v.z4 r (distributionUtils.nim:102-153): each colour component 1, i, -1 or -i by one uniform"""
+        v = self._new(3, 2)
+        check(lib().qexhip_rng_z4_vector(self._h, v.ctypes.data_as(C.c_void_p)))
+        return v
+
+    def z2_vector(self):
+        """v.z2 r (distributionUtils.nim:154-180): each colour component 1 or -1 by one uniform"""
+        v = self._new(3, 2)
+        check(lib().qexhip_rng_z2_vector(self._h, v.ctypes.data_as(C.c_void_p)))
+        return v
+
     def randomTAH(self):
         p = self._new(4, 3, 3, 2)
         check(lib().qexhip_rng_random_tah(self._h, p.ctypes.data_as(C.c_void_p)))
@@ -68,6 +80,13 @@ class RngField:
 
     def dev_u1_vector(self, ctx, field_id):
         check(lib().qexhip_rng_dev_u1_vector(ctx._h, self._h, int(field_id)))
+
+    def dev_z4_vector(self, ctx, field_id):
+        """v.z4 r into a resident colour vector: the host fill's values and generator state bit for bit"""
+        check(lib().qexhip_rng_dev_z4_vector(ctx._h, self._h, int(field_id)))
+
+    def dev_z2_vector(self, ctx, field_id):
+        check(lib().qexhip_rng_dev_z2_vector(ctx._h, self._h, int(field_id)))
 
     def dev_momenta(self, ctx):
         """p.randomTAH r into the resident MD momenta of ctx (qexhip_md_refresh_momenta)"""

@@ -337,6 +337,52 @@ class Context:
         check(lib().qexhip_dev_norm2slice(self._h, int(fid), int(dir), _p(out)))
         return out
 
+    # stochastic scalar trace (scalarTrace.nim; csrc/trace.hip): complex site fields, dilution, <a, b> accumulation, slice sums
+    def cfield_new(self):
+        """a resident complex site field (lo.Complex), zeroed; its ids are separate from the colour vectors'"""
+        cid = C.c_int(0)
+        check(lib().qexhip_cfield_new(self._h, C.byref(cid)))
+        return cid.value
+
+    def cfield_free(self, cid):
+        check(lib().qexhip_cfield_free(self._h, int(cid)))
+
+    def cfield_zero(self, cid):
+        check(lib().qexhip_cfield_zero(self._h, int(cid)))
+
+    def cfield_scale(self, cid, s):
+        check(lib().qexhip_cfield_scale(self._h, int(cid), float(s)))
+
+    def cfield_download(self, cid):
+        """(vol, 2) array of (re, im) in the site order of field_download"""
+        out = np.zeros((self.vol, 2))
+        check(lib().qexhip_cfield_download(self._h, int(cid), _p(out)))
+        return out
+
+    def dev_dilute(self, dst_ids, src_id, kind, idx, t, scale=1.0):
+        """dst_k = scale * src on the sites of GLOBAL time t[k] in pattern idx[k] of kind 0 (EO: global parity) or 1 (CORNER:
+        (x0&1) | (x1&1)<<1 | (x2&1)<<2), exact zeros elsewhere; up to four destinations in one launch"""
+        n = len(dst_ids)
+        if n != len(idx) or n != len(t):
+            raise ValueError("dst_ids, idx and t differ in length")
+        i = C.c_int * max(n, 1)
+        check(lib().qexhip_dev_dilute(self._h, n, i(*[int(v) for v in dst_ids]), int(src_id), int(kind), i(*[int(v) for v in idx]),
+                                      i(*[int(v) for v in t]), float(scale)))
+
+    def dev_trace_accum(self, cid, a_ids, b_ids, coef=1.0):
+        """trce(x) += coef * a_k(x).dot b_k(x) for up to four pairs, one after the other in ascending k"""
+        n = len(a_ids)
+        if n != len(b_ids):
+            raise ValueError("a_ids and b_ids differ in length")
+        i = C.c_int * max(n, 1)
+        check(lib().qexhip_dev_trace_accum(self._h, int(cid), n, i(*[int(v) for v in a_ids]), i(*[int(v) for v in b_ids]), float(coef)))
+
+    def dev_cfield_slices(self, cid):
+        """(nt, 2) array: Re, Im of the sum of the cfield over every global time slice, rank-global"""
+        out = np.zeros((self.lat[3] * self.rank_geom[3], 2))
+        check(lib().qexhip_dev_cfield_slices(self._h, int(cid), _p(out)))
+        return out
+
     # field algebra hooks (fieldET.nim:605-625,704-724)
     def norm2(self, x, subset="all"):
         out = C.c_double(0)
