@@ -618,6 +618,8 @@ int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped
  *                  (qexhip_stag_links_storage) if at most 1 % of their links escape it; 0: 18 reals.  Effective at the next set_links
  *   "sloppy_check" the sloppy solves post their (device-gated) reliable-update launches every this many fp32 iterations, and
  *                  at maxits (default 4; 1: in the iteration that calls for an update)
+ *   "stout_check"  inverse iterations of qexhip_stout_inverse posted between two read-backs of its device-side loop state
+ *                  (default 8); the result does not depend on it
  *   "overlap"      face exchange on the second stream beside the interior sweep: 0 never, 1 always, -1 (default) measured at
  *                  set_links when the communicator has more than one rank (qexhip_stag_sweep_info), else by interior / face
  *                  size; -2: measure on one rank too (test hook)
@@ -712,6 +714,41 @@ int qexhip_nhyp_fermion_force(qexhip_handle h, double *f, const double *const *p
 /*   the same with the pseudofermion fields already resident (field ids): nothing but scalars crosses PCIe when f == NULL */
 int qexhip_nhyp_fforce_dev(qexhip_handle h, double *f, int n, const int *phi_ids, const double *mass, const double *scale,
                            const double *r2req, int maxits, const int antiperiodic[4], const int phases[4], int *iters);
+
+/* ---------------- stout smearing (src/gauge/stoutsmear.nim) ----------------
+ * One step is fl = exp(-alpha nc TAH(g ds^+)) g with ds the derivative of the plaquette action (plaq: 1.0): one stage of the flow
+ * integrator, and it honours option "flow_exp" as the flow does.  Fields are double[vol][4][3][3][2].
+ *   smear        StoutSmear.smear (stoutsmear.nim:15-34), one step, nothing kept.  g NULL = the resident links (qexhip_gauge_set /
+ *                qexhip_md_begin); fl NULL = the result replaces the resident links; g == fl is allowed (tstoutderiv.nim:22-23).
+ *   prepare      levels 0..nlevels-1 (alphas[k]) applied in order, 1 <= nlevels <= 8, and what smearDeriv needs of every level kept
+ *                on the device: its input links and alpha nc f (the reference keeps gf, f, expaf, ds, stoutsmear.nim:5-13;
+ *                exp(a f) and ds are recomputed here).  g NULL = the resident links, fl (nullable) receives the smeared links.
+ *                The state refers to THIS g: with fl == g ("in place", level 0's input overwritten, :22) the force entry points
+ *                refuse, as smearDeriv is undefined then.
+ *   force        smearDeriv (stoutsmear.nim:148-175; gaugeForceDeriv :97-146, expDeriv = expm1Deriv with scale 20, order 4,
+ *                src/maths/matexp.nim:686-713, matrixFunctions.nim:471-481) from the last level to the first
+ *                (tstoutderiv.nim:190-192): chain = dS/dV^+ w.r.t. the smeared links, f = dS/dU^+ w.r.t. the input links.  f may
+ *                alias chain; f NULL leaves the result on the device as MD force source 1 (qexhip_md_kick).
+ *   gauge_force  smearedForce of tests/base/tstoutderiv.nim:137-143: gaugeActionDeriv on the smeared links (coefficients as
+ *                qexhip_nhyp_gauge_force), the chain, contractProjectTAH(g, f) = TAH(g f^+).  f NULL as in force.
+ *   release      drop the chain.  force / gauge_force without a prepared chain, after release, or after an in-place level 0
+ *                fail with QEXHIP_ERR_ARG and the message "call qexhip_stout_prepare first" / "smeared in place".
+ *   inverse      StoutSmear.inverse (stoutsmear.nim:36-89): g with smear(g) = fl by the fixed-point iteration of Luescher's
+ *                trivialising map (all links move at once), from g = fl.  iters = the first iteration whose rdf2 = |f_k - f_{k-1}|^2 /
+ *                |f_k|^2 < rdf2req, or maxits (not an error); rdf2 belongs to the returned field; diverging = 1 if |f_k - f_{k-1}|^2
+ *                ever grew (the reference's "df^2 increased" warning, :81-83).  iters, rdf2, diverging may be NULL.  The loop state
+ *                stays on the device; option "stout_check" (default 8) = iterations posted between two read-backs of it, and the
+ *                result does not depend on it.  g != fl.
+ * QEXHIP_ERR_ARG, before anything is launched and with nothing written: a non-finite alpha, nlevels outside 1..8, maxits < 0,
+ * g == fl in inverse.  t-sharded contexts: collective, fields are the rank's slab.  qexhip_release_workspace drops the chain and
+ * the scratch fields of smear / inverse. */
+int qexhip_stout_smear(qexhip_handle h, const double *g, double alpha, double *fl);
+int qexhip_stout_prepare(qexhip_handle h, const double *g, const double *alphas, int nlevels, double *fl);
+int qexhip_stout_force(qexhip_handle h, double *f, const double *chain);
+int qexhip_stout_gauge_force(qexhip_handle h, double *f, double cplaq, double crect, double cadjplaq);
+int qexhip_stout_release(qexhip_handle h);
+int qexhip_stout_inverse(qexhip_handle h, const double *fl, double alpha, double rdf2req, int maxits, double *g, int *iters,
+                         double *rdf2, int *diverging);
 
 /* ---------------- random number fields and configuration generation (host only, no handle) ----------------
  * newRNGField (src/rng/distributionUtils.nim:306-331): one generator per site of the LOCAL lattice, seeded with

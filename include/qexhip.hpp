@@ -329,6 +329,40 @@ inline double linkTrace(Context &c, const std::vector<int> &dirs) {
   check(qexhip_gauge_link_trace(c.h, dirs.data(), (int)dirs.size(), &r));
   return r;
 }
+// Stout smearing (src/gauge/stoutsmear.nim).  stoutSmear: ss.smear(g, fl) (:15-34), one step, nothing kept; fl may be g.
+inline void stoutSmear(Context &c, const Field &g, double alpha, Field &fl) {
+  fl.resize(g.size());
+  check(qexhip_stout_smear(c.h, g.data(), alpha, fl.data()));
+}
+// ss.inverse(gf, fl) (:36-89): returns the iterations; rdf2 / diverging (may be null) as qexhip_stout_inverse
+inline int stoutInverse(Context &c, Field &g, const Field &fl, double alpha, double rdf2req = 1e-24, int maxIter = 1000,
+                        double *rdf2 = nullptr, bool *diverging = nullptr) {
+  int its = 0, dv = 0;
+  double r2 = 0;
+  g.resize(fl.size());
+  check(qexhip_stout_inverse(c.h, fl.data(), alpha, rdf2req, maxIter, g.data(), &its, &r2, &dv));
+  if (rdf2) *rdf2 = r2;
+  if (diverging) *diverging = dv != 0;
+  return its;
+}
+// the n-level chain kept on the device: smearDeriv (:148-175) from the last level to the first, and smearedForce of
+// tests/base/tstoutderiv.nim:137-143
+class StoutSmearedForce {
+  Context &c_;
+ public:
+  StoutSmearedForce(Context &c, const Field &g, const std::vector<double> &alphas, Field *fl) : c_(c) {
+    if (fl) fl->resize(g.size());
+    check(qexhip_stout_prepare(c.h, g.data(), alphas.data(), (int)alphas.size(), fl ? fl->data() : nullptr));
+  }
+  StoutSmearedForce(Context &c, const std::vector<double> &alphas) : c_(c) {      // the links resident on the device
+    check(qexhip_stout_prepare(c.h, nullptr, alphas.data(), (int)alphas.size(), nullptr));
+  }
+  ~StoutSmearedForce() { qexhip_stout_release(c_.h); }
+  StoutSmearedForce(const StoutSmearedForce &) = delete;
+  void operator()(Field &f, const Field &chain) { check(qexhip_stout_force(c_.h, f.data(), chain.data())); }      // f may be chain
+  void gaugeForce(Field &f, double plaq, double rect = 0, double adjplaq = 0) { check(qexhip_stout_gauge_force(c_.h, f.data(), plaq, rect, adjplaq)); }
+  void gaugeForceResident(double plaq, double rect = 0, double adjplaq = 0) { check(qexhip_stout_gauge_force(c_.h, nullptr, plaq, rect, adjplaq)); }
+};
 // The complex site field `trce` of scalarTrace.nim, resident on the device, with the accumulation and slice sums on it; field
 // arguments are ids of resident colour vectors (qexhip_field_new).
 class TraceField {

@@ -12,6 +12,7 @@ from .staggered import (  # noqa: F401
     Context, device_count, Staggered, SolverParams, newStag, newStag3, link_residual_host, plaq, gaugeForce, gaugeFlow, gaugeSet, gaugeFlowResident, flowEQ, flowMeasure, gaugeAction, gaugeUpdate, reunit, wline, ploops, s4_gauge, ResidentMD, HisqCoefs, HypCoefs, makeImpLinks, fat7lDeriv, EVEN, ODD, ALL,
     SloppyNone, SloppySingle, SloppyHalf, EigBasis, EigOpts, eig_check_opts, symeig_host,
 )
+from .stout import StoutSmear, newStoutSmear, stoutSmear, stoutSmearGetForce  # noqa: F401
 from .io import loadGauge, loadGaugeSlab, saveGauge, getFileLattice, gaugeFileInfo, writeField, readField, fileMetadata  # noqa: F401
 from .rng import RngField, RngMilc6, MRG32k3a  # noqa: F401
 from .mesons import stagLocalMesons, stagMesons, norm2slice, sft, printLocalMesons, pointSource, wallSource, localMesonTables  # noqa: F401

@@ -125,6 +125,12 @@ SYMBOLS = [
     ("qexhip_nhyp_fforce", _ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _pi, _pi, _pi]),
     ("qexhip_nhyp_gauge_force", _ci, [_vp, _vp, _cd, _cd, _cd]),
     ("qexhip_nhyp_fermion_force", _ci, [_vp, _vp, _vp, _vp, _ci, _pi, _pi]),
+    ("qexhip_stout_smear", _ci, [_vp, _vp, _cd, _vp]),
+    ("qexhip_stout_prepare", _ci, [_vp, _vp, _pd, _ci, _vp]),
+    ("qexhip_stout_force", _ci, [_vp, _vp, _vp]),
+    ("qexhip_stout_gauge_force", _ci, [_vp, _vp, _cd, _cd, _cd]),
+    ("qexhip_stout_release", _ci, [_vp]),
+    ("qexhip_stout_inverse", _ci, [_vp, _vp, _cd, _cd, _ci, _vp, _pi, _pd, _pi]),
     ("qexhip_gauge_action", _ci, [_vp, _cd, _cd, _cd, _vp]),
     ("qexhip_gauge_update", _ci, [_vp, _vp, _cd]),
     ("qexhip_gauge_reunit", _ci, [_vp]),

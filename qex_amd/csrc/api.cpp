@@ -186,6 +186,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   batch_f32_state_free(c);
   msf_state_free(c);
   gfix_state_free(c);
+  stout_state_free(c);
   eig_state_free(c);
   eig_bases_free(c);
   for (auto &kv : c->cfields) (void)hipFree(kv.second.d);
@@ -764,6 +765,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   batch_f32_state_free(c);           // and the batched form's fp32 fields
   gfix_state_free(c);                // and the gauge-fixing transform with its polish scratch (qexhip_gfix_set_transform re-creates it)
   eig_state_free(c);                 // and the eigensolver's Lanczos work fields and buffers (never the user's bases)
+  stout_state_free(c);               // and the stout chain with the scratch of smear / inverse (qexhip_stout_prepare re-creates it)
   return 0;
 }
 
@@ -1114,6 +1116,10 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
     if (value < 1) { qexhip_set_error("option gfix_check: >= 1 relax iterations"); return QEXHIP_ERR_ARG; }
     c->opt_gfix_check = value;
   }
+  else if (n == "stout_check") {
+    if (value < 1) { qexhip_set_error("option stout_check: >= 1 inverse iterations"); return QEXHIP_ERR_ARG; }
+    c->opt_stout_check = value;
+  }
   else { qexhip_set_error("unknown option"); return QEXHIP_ERR_ARG; }
   return 0;
 }
@@ -1230,6 +1236,41 @@ extern "C" int qexhip_nhyp_gauge_force(qexhip_handle c, double *f, double cplaq,
   if (crect != 0.0 && cadj != 0.0) { qexhip_set_error("rect and adjplaq together are not a QEX action"); return QEXHIP_ERR_ARG; }
   HIPCHK(hipSetDevice(c->device));
   return nhyp_gauge_force(c, f, cplaq, cadj != 0.0 ? cadj : crect, cadj != 0.0 ? 1 : 0);
+}
+// ---- stout smearing (stout.hip) ----
+extern "C" int qexhip_stout_smear(qexhip_handle c, const double *g, double alpha, double *fl) {
+  if (!c) return QEXHIP_ERR_ARG;
+  return stout_smear(c, g, alpha, fl);
+}
+extern "C" int qexhip_stout_prepare(qexhip_handle c, const double *g, const double *alphas, int nlevels, double *fl) {
+  if (!c) return QEXHIP_ERR_ARG;
+  return stout_prepare(c, g, alphas, nlevels, fl);
+}
+extern "C" int qexhip_stout_force(qexhip_handle c, double *f, const double *chain) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!chain) { qexhip_set_error("stout_force: null chain"); return QEXHIP_ERR_ARG; }
+  return stout_force(c, f, chain);
+}
+extern "C" int qexhip_stout_gauge_force(qexhip_handle c, double *f, double cplaq, double crect, double cadj) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (crect != 0.0 && cadj != 0.0) { qexhip_set_error("rect and adjplaq together are not a QEX action"); return QEXHIP_ERR_ARG; }
+  if (crect != 0.0) for (int d = 0; d < 4; d++) if (c->g.X[d] < 4) { qexhip_set_error("rectangle action needs extents >= 4"); return QEXHIP_ERR_ARG; }
+  return stout_gauge_force(c, f, cplaq, cadj != 0.0 ? cadj : crect, cadj != 0.0 ? 1 : 0);
+}
+extern "C" int qexhip_stout_release(qexhip_handle c) {
+  if (!c) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  stout_chain_free(c);
+  return 0;
+}
+extern "C" int qexhip_stout_inverse(qexhip_handle c, const double *fl, double alpha, double rdf2req, int maxits, double *g, int *iters,
+                                    double *rdf2, int *diverging) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!fl || !g) { qexhip_set_error("stout_inverse: null field"); return QEXHIP_ERR_ARG; }
+  if (g == fl) { qexhip_set_error("stout_inverse: g and fl must be distinct (stoutsmear.nim:37)"); return QEXHIP_ERR_ARG; }
+  if (maxits < 0) { qexhip_set_error("stout_inverse: maxits < 0"); return QEXHIP_ERR_ARG; }
+  return stout_inverse(c, fl, alpha, rdf2req, maxits, g, iters, rdf2, diverging);
 }
 extern "C" int qexhip_nhyp_fermion_force(qexhip_handle c, double *f, const double *const *psi, const double *scale, int n,
                                          const int antiperiodic[4], const int phases[4]) {

@@ -981,23 +981,28 @@ static int gn_alloc_fp(qexhip_ctx *c) {
   if (!c->gn->P) { HIPCHK(hipMalloc((void **)&c->gn->P, bytes)); HIPCHK(hipMemsetAsync(c->gn->P, 0, bytes, c->stream)); }
   return 0;
 }
-// refresh the ghost slices of the resident links to at least `depth` (1..3); no-op unless t is sharded
-int gauge_ghosts(qexhip_ctx *c, int depth) {
+// refresh the depth-`depth` (1..3) ghost slices of any gauge-shaped device field; no-op unless t is sharded
+int gauge_field_ghosts(qexhip_ctx *c, double2 *field, int depth) {
   const Geom &g = c->g;
-  if (!g.halo || c->gn->ghost_valid >= depth) return 0;
+  if (!g.halo) return 0;
   if (g.X[3] < depth) { qexhip_set_error("local t extent %d < ghost depth %d needed by this kernel", g.X[3], depth); return -1; }
   const size_t tile2 = (size_t)4 * 576 * 2;                 // doubles per link-tile
   const size_t ft = (size_t)g.F / 64;                       // tiles per t-slice
   double *bottom[2], *top[2], *ghi[2], *glo[2];
   for (int p = 0; p < 2; p++) {
-    double *base = (double *)c->gn->U + (size_t)p * g.etile * tile2;
+    double *base = (double *)field + (size_t)p * g.etile * tile2;
     bottom[p] = base;
     top[p] = base + ((size_t)g.ntile - depth * ft) * tile2;
     ghi[p] = base + (size_t)g.ntile * tile2;
     glo[p] = base + ((size_t)g.ntile + 3 * ft + (3 - depth) * ft) * tile2;
   }
   ScopedTimer tm(c, "gauge_halo", c->stream);
-  CHK(comm_faces_exchange(c, 2, bottom, top, ghi, glo, (size_t)depth * ft * tile2));
+  return comm_faces_exchange(c, 2, bottom, top, ghi, glo, (size_t)depth * ft * tile2);
+}
+// refresh the ghost slices of the resident links to at least `depth` (1..3); no-op unless t is sharded
+int gauge_ghosts(qexhip_ctx *c, int depth) {
+  if (!c->g.halo || c->gn->ghost_valid >= depth) return 0;
+  CHK(gauge_field_ghosts(c, c->gn->U, depth));
   c->gn->ghost_valid = depth;
   return 0;
 }
@@ -1112,9 +1117,12 @@ int gauge_plaq_s4(qexhip_ctx *c, double out[8]) {
 }
 
 static int force_dev(qexhip_ctx *c, double cplaq, int flow = 0, double cf = 0, double cpm = 0, double c2 = 0, int kind = 0,
-                     double2 *Uout = nullptr) {
-  CHK(gn_alloc_fp(c));
-  CHK(gauge_ghosts(c, ghost_depth_for(c2, kind)));
+                     double2 *Uout = nullptr, double2 *Uin = nullptr, double2 *Vout = nullptr) {
+  // Uin / Vout (plaquette action only): a flow stage on any gauge-shaped device field, v into Vout; the resident fields are not touched
+  if (Uin && (!Vout || !Uout || !flow || c2 != 0.0)) { qexhip_set_error("internal: force_dev on a named field is a plaquette flow stage"); return -3; }
+  if (Uin) CHK((c->gn && Uin == c->gn->U) ? gauge_ghosts(c, 1) : gauge_field_ghosts(c, Uin, 1));
+  else { CHK(gn_alloc_fp(c)); CHK(gauge_ghosts(c, ghost_depth_for(c2, kind))); }
+  double2 *const U = Uin ? Uin : c->gn->U, *const P = Uin ? Vout : c->gn->P, *const F = Uin ? nullptr : c->gn->F;   // (a flow stage never writes F)
   ScopedTimer tm(c, "staple", c->stream);
   const int *order = nullptr; int chunk = 0;
   CHK(tile_order_table(c, &order, &chunk));
@@ -1126,22 +1134,22 @@ static int force_dev(qexhip_ctx *c, double cplaq, int flow = 0, double cf = 0, d
     if (kind == 0) {
       // rectangle action: double links once per call, then the shared-factor kernel
       if (!c->gn->D2) HIPCHK(hipMalloc((void **)&c->gn->D2, c->gn->n2 * sizeof(double2)));
-      if (c->g.halo) k_double_links<true><<<2 * c->g.etile, 256, 0, c->stream>>>(c->g, c->gn->U, c->gn->D2);
-      else k_double_links<false><<<2 * c->g.ntile, 256, 0, c->stream>>>(c->g, c->gn->U, c->gn->D2);
-      double2 *Pf = (flow || Uout) ? c->gn->P : nullptr;
-#define QX_FRECT(CL, HL) k_force_rect<CL, HL><<<nb, 256, 0, c->stream>>>(c->g, c->gn->U, c->gn->D2, c->gn->F, cplaq / 3.0, k2, Pf, cf, cpm, 0, Uout, order, chunk)
+      if (c->g.halo) k_double_links<true><<<2 * c->g.etile, 256, 0, c->stream>>>(c->g, U, c->gn->D2);
+      else k_double_links<false><<<2 * c->g.ntile, 256, 0, c->stream>>>(c->g, U, c->gn->D2);
+      double2 *Pf = (flow || Uout) ? P : nullptr;
+#define QX_FRECT(CL, HL) k_force_rect<CL, HL><<<nb, 256, 0, c->stream>>>(c->g, U, c->gn->D2, F, cplaq / 3.0, k2, Pf, cf, cpm, 0, Uout, order, chunk)
       if (closed) { if (c->g.halo) QX_FRECT(true, true); else QX_FRECT(true, false); }
       else { if (c->g.halo) QX_FRECT(false, true); else QX_FRECT(false, false); }
 #undef QX_FRECT
     } else if (closed)
-      k_force_gen<true><<<nb, 256, 0, c->stream>>>(c->g, c->gn->U, c->gn->F, cplaq / 3.0, k2, kind, c->gn->P, cf, cpm, 0, Uout, order, chunk);
+      k_force_gen<true><<<nb, 256, 0, c->stream>>>(c->g, U, F, cplaq / 3.0, k2, kind, P, cf, cpm, 0, Uout, order, chunk);
     else
-      k_force_gen<false><<<nb, 256, 0, c->stream>>>(c->g, c->gn->U, c->gn->F, cplaq / 3.0, k2, kind,
-                                                    flow ? c->gn->P : nullptr, cf, cpm, 0, Uout, order, chunk);
+      k_force_gen<false><<<nb, 256, 0, c->stream>>>(c->g, U, F, cplaq / 3.0, k2, kind,
+                                                    flow ? P : nullptr, cf, cpm, 0, Uout, order, chunk);
   } else {
     // (capping the registers for 3 or 4 waves/SIMD spills: 1460 / 2370 us against 1310 us fused at 2 waves/SIMD)
     const size_t shb = (size_t)8 * 576 * sizeof(double2);         // 72 KiB per parity of a tile position (qexhip_init checks the device offers 144)
-    double2 *Pf = (closed || flow) ? c->gn->P : nullptr;
+    double2 *Pf = (closed || flow) ? P : nullptr;
     if (c->opt_force_pair && c->tile_pairs_ok) {
       // both parities of a tile position per workgroup (k_force_lds2): 144 KiB of LDS, one workgroup of 8 wavefronts per CU
       if (!(c->lds_attr_done & 8)) {
@@ -1151,7 +1159,7 @@ static int force_dev(qexhip_ctx *c, double cplaq, int flow = 0, double cf = 0, d
         HIPCHK(hipFuncSetAttribute((const void *)k_force_lds2<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * shb)));
         c->lds_attr_done |= 8;
       }
-#define QX_FLDS2(CL, HL) k_force_lds2<CL, HL><<<nb / 2, 512, 2 * shb, c->stream>>>(c->g, c->gn->U, c->gn->F, cplaq / 3.0, Pf, cf, cpm, Uout, order, chunk)
+#define QX_FLDS2(CL, HL) k_force_lds2<CL, HL><<<nb / 2, 512, 2 * shb, c->stream>>>(c->g, U, F, cplaq / 3.0, Pf, cf, cpm, Uout, order, chunk)
       if (closed) { if (c->g.halo) QX_FLDS2(true, true); else QX_FLDS2(true, false); }
       else { if (c->g.halo) QX_FLDS2(false, true); else QX_FLDS2(false, false); }
 #undef QX_FLDS2
@@ -1164,7 +1172,7 @@ static int force_dev(qexhip_ctx *c, double cplaq, int flow = 0, double cf = 0, d
         HIPCHK(hipFuncSetAttribute((const void *)k_force_lds<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shb));
         c->lds_attr_done |= 1;
       }
-#define QX_FLDS(CL, HL) k_force_lds<CL, HL><<<nb, 256, shb, c->stream>>>(c->g, c->gn->U, c->gn->F, cplaq / 3.0, Pf, cf, cpm, Uout, order, chunk)
+#define QX_FLDS(CL, HL) k_force_lds<CL, HL><<<nb, 256, shb, c->stream>>>(c->g, U, F, cplaq / 3.0, Pf, cf, cpm, Uout, order, chunk)
       if (closed) { if (c->g.halo) QX_FLDS(true, true); else QX_FLDS(true, false); }
       else { if (c->g.halo) QX_FLDS(false, true); else QX_FLDS(false, false); }
 #undef QX_FLDS
@@ -1199,6 +1207,33 @@ int gauge_wflow(qexhip_ctx *c, int nsteps, double eps, double cplaq, double c2, 
       c->gn->ghost_valid = 0;
     }
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// One stout step (src/gauge/stoutsmear.nim:15-34) IS one RK stage of the flow with cpm = 0 and cf = -alpha nc: ds = the plaquette
+// action's derivative, f = TAH(g ds^+), fl = exp(-alpha nc f) g.  Uin == nullptr: the resident links; else any gauge-shaped device
+// field (its ghost slices are refreshed in place).  V receives a f = -alpha nc f (what the stage writes over the momenta), Uout the
+// smeared links; neither the resident links nor the resident force / momentum buffers are touched.
+int gauge_stout_stage(qexhip_ctx *c, double2 *Uin, double2 *V, double2 *Uout, double alpha) {
+  if (!Uin && !c->gn) { qexhip_set_error("gauge field not set (qexhip_gauge_set)"); return -3; }
+  return force_dev(c, 1.0, 1, -alpha * 3.0, 0.0, 0.0, 0, Uout, Uin ? Uin : c->gn->U, V);
+}
+// host [idx][mu][9] <-> any gauge-shaped device field
+int gauge_upload_nat(qexhip_ctx *c, double2 *G, const double *host) {
+  const size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
+  CHK(ensure_stage(c, bytes));
+  HIPCHK(hipMemcpyAsync(c->stage, host, bytes, hipMemcpyHostToDevice, c->stream));
+  k_gauge_to_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (const double2 *)c->stage, G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));          // the caller may reuse `host` (f aliasing chain)
+  return 0;
+}
+int gauge_download_nat(qexhip_ctx *c, const double2 *G, double *host) { return download_nat(c, G, host); }
+// the resident links become *buf, *buf the old resident buffer (both gauge-shaped); creates the resident field if there is none
+int gauge_swap_resident(qexhip_ctx *c, double2 **buf) {
+  CHK(gn_alloc(c));
+  std::swap(c->gn->U, *buf);
+  c->gn->ghost_valid = 0;
   return 0;
 }
 
@@ -1309,11 +1344,12 @@ __global__ void __launch_bounds__(256) k_links_norm2(size_t nlinks_tiles, const 
   if (threadIdx.x == 0) { partials[blockIdx.x] = r; partials[gridDim.x + blockIdx.x] = 0; partials[2 * gridDim.x + blockIdx.x] = 0; }
 }
 double2 *nhyp_force_buffer(qexhip_ctx *c);      // smear.hip: the closure's force field (null without a closure)
+double2 *stout_force_buffer(qexhip_ctx *c);     // stout.hip: the same of the stout chain
 const double2 *gauge_resident_links(qexhip_ctx *c) { return c->gn ? c->gn->U : nullptr; }
 static int md_source(qexhip_ctx *c, int source, const double2 **F) {
   *F = nullptr;
   if (source == 0) *F = c->gn ? c->gn->F : nullptr;
-  else if (source == 1) *F = nhyp_force_buffer(c);
+  else if (source == 1) *F = c->md_src1_stout ? stout_force_buffer(c) : nhyp_force_buffer(c);   // whichever closure wrote last
   if (!*F) { qexhip_set_error("md: force source %d holds nothing yet", source); return -3; }
   return 0;
 }

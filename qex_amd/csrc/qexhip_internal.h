@@ -236,6 +236,9 @@ struct qexhip_ctx {
   void *eig = nullptr;                               // EigWork (eig.hip): Lanczos work fields, coefficient / partial / Q buffers
   int deflate_basis = 0, deflate_nev = 0;            // set around a deflated full solve: its inner solveEE calls deflate with this basis
   std::map<int, DevCField> cfields; int next_cfield = 1;   // the user's complex site fields (qexhip_cfield_new)
+  void *stout = nullptr;                             // StoutState (stout.hip): the stout chain's levels, backward scratch, inverse loop state
+  int md_src1_stout = 0;                             // MD force source 1 is the stout chain's force (the closure that wrote last), else the nHYP closure's
+  int opt_stout_check = 8;                           // option "stout_check": inverse iterations posted between two read-backs of the loop state
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -549,6 +552,15 @@ int gauge_fix(qexhip_ctx *c, const int *dirs, int ndirs, double gstop, double or
 int gauge_transform(qexhip_ctx *c);
 int gauge_link_trace(qexhip_ctx *c, const int *dirs, int ndirs, double *out);
 void gfix_state_free(qexhip_ctx *c);
+// ---- stout.hip (src/gauge/stoutsmear.nim) ----
+int stout_smear(qexhip_ctx *c, const double *g_host, double alpha, double *fl_host);
+int stout_prepare(qexhip_ctx *c, const double *g_host, const double *alphas, int nlevels, double *fl_host);
+int stout_force(qexhip_ctx *c, double *f_host, const double *chain_host);
+int stout_gauge_force(qexhip_ctx *c, double *f_host, double cplaq, double c2, int kind);
+int stout_inverse(qexhip_ctx *c, const double *fl_host, double alpha, double rdf2req, int maxits, double *g_host, int *iters, double *rdf2,
+                  int *diverging);
+void stout_chain_free(qexhip_ctx *c);    // the levels of the chain (qexhip_stout_release)
+void stout_state_free(qexhip_ctx *c);    // and the scratch of smear / inverse (qexhip_release_workspace, qexhip_finalize)
 // ---- rng.hip (device-side generation) ----
 struct qexhip_rng;
 int rng_dev_generate(qexhip_ctx *c, qexhip_rng *R, int what, DevField *f, double2 *P);   // what: 0 gaussian vector, 1 u1 vector, 2 randomTAH -> P,

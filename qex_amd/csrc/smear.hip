@@ -1420,6 +1420,7 @@ __global__ void __launch_bounds__(256) k_force_projtah(size_t nlinks_tiles, doub
 }
 static int nhyp_finish(qexhip_ctx *c, NhypState *st, int adj, double *f_host) {
   CHK(nhyp_backward_dev(c, st));
+  c->md_src1_stout = 0;                                   // MD source 1 is this closure's force again
   const size_t ltiles = (size_t)2 * c->g.etile * 4;       // ghost tiles included: harmless, keeps the index linear
   k_force_projtah<<<(unsigned)((ltiles * 64 + 255) / 256), 256, 0, c->stream>>>(ltiles, st->F, st->G, adj);
   HIPCHK(hipGetLastError());

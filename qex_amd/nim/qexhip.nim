@@ -108,6 +108,14 @@ proc qexhip_nhyp_gauge_force(h: QexhipHandle; f: ptr cdouble; cplaq, crect, cadj
 proc qexhip_nhyp_fermion_force(h: QexhipHandle; f: ptr cdouble; psi: ptr ptr cdouble; scale: ptr cdouble;
                                n: cint; antiperiodic, phases: ptr cint): cint {.qh.}
 proc qexhip_nhyp_release(h: QexhipHandle): cint {.qh.}
+# stout smearing (gauge/stoutsmear.nim:15-175): g = nil is the resident field, fl = nil (smear) replaces it; alphas: nlevels steps
+proc qexhip_stout_smear(h: QexhipHandle; g: ptr cdouble; alpha: cdouble; fl: ptr cdouble): cint {.qh.}
+proc qexhip_stout_prepare(h: QexhipHandle; g, alphas: ptr cdouble; nlevels: cint; fl: ptr cdouble): cint {.qh.}
+proc qexhip_stout_force(h: QexhipHandle; f, chain: ptr cdouble): cint {.qh.}
+proc qexhip_stout_gauge_force(h: QexhipHandle; f: ptr cdouble; cplaq, crect, cadjplaq: cdouble): cint {.qh.}
+proc qexhip_stout_release(h: QexhipHandle): cint {.qh.}
+proc qexhip_stout_inverse(h: QexhipHandle; fl: ptr cdouble; alpha, rdf2req: cdouble; maxits: cint; g: ptr cdouble; iters: ptr cint;
+                          rdf2: ptr cdouble; diverging: ptr cint): cint {.qh.}
 proc qexhip_gauge_action(h: QexhipHandle; cplaq, crect, cadjplaq: cdouble; o: ptr cdouble): cint {.qh.}
 proc qexhip_gauge_update(h: QexhipHandle; p: ptr cdouble; t: cdouble): cint {.qh.}
 proc qexhip_gauge_reunit(h: QexhipHandle): cint {.qh.}
