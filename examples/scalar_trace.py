@@ -4,14 +4,17 @@ noise sources diluted in time and even/odd or the eight 3-d corners.
 
     python examples/scalar_trace.py [-inlat FILE | -lat 4 4 4 8] [-outfn output] [-mass 0.1] [-sloppy 0] [-cg_prec 1e-9]
                                     [-cg_max 100000] [-num_stoch 1] [-improved_trace 1] [-source_type Z4] [-dilute_type EO]
-                                    [-seed N] [-smear 0] [-batch 4]
+                                    [-seed N] [-smear 0] [-batch 4] [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3]
     python -m torch.distributed.run --nproc-per-node N examples/scalar_trace.py ...     # t-sharded over N ranks
 
 The parameters are the reference program's.  Without -inlat the configuration is g.random of the seed's RngMilc6 field, whose
 streams then go on into the noise, as there; -smear 1 builds the operator on nHYP(0.4, 0.5, 0.5) links (the reference always
 smears).  The noise is drawn, diluted, solved in lock-step batches of -batch patterns and contracted on the device
 (qex_amd.scalarTrace); each trace is written as one SciDAC record of 16-byte sites, read back, and its per-timeslice sums are
-printed once more, as `loadsrc` lines.  -sloppy 1 or 2 solves in mixed precision: one rank only."""
+printed once more, as `loadsrc` lines.  -sloppy 1 or 2 solves in mixed precision: one rank only.  -nev N computes the N lowest
+eigenpairs of the even/odd operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every
+batch with them, the odd-parity patterns included; the first source is then also solved without deflation and the eigensolve
+time and the iterations with / without deflation are printed."""
 import argparse
 import os
 import sys
@@ -41,6 +44,10 @@ ap.add_argument("-dilute_type", default="EO", choices=["EO", "CORNER"])
 ap.add_argument("-seed", type=int, default=int(1000 * time.time()))
 ap.add_argument("-smear", type=int, default=0, choices=[0, 1])
 ap.add_argument("-batch", type=int, default=4, choices=[1, 2, 3, 4])
+ap.add_argument("-nev", type=int, default=0, help="deflate every batch with this many low modes (0: no eigensolve)")
+ap.add_argument("-nvecs", type=int, default=0, help="size of the Lanczos basis (default max(2 nev, nev + 8))")
+ap.add_argument("-cheb", type=int, default=12, help="Chebyshev degree (0: plain Lanczos)")
+ap.add_argument("-cheb_lo", type=float, default=0.3)
 a = ap.parse_args()
 if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1:
     sys.exit("scalar_trace.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
@@ -102,11 +109,27 @@ else:
     s = q.newStag(ctx, g)
 print("links per site, storage format, max deviation:", s.links_info())
 
+defl = {}
+if a.nev > 0:
+    t0 = time.perf_counter()
+    B = s.eigs(a.nev, nvecs=a.nvecs or None, cheb_degree=a.cheb, cheb_lo=a.cheb_lo)
+    ctx.sync()
+    print("eigs: nconv %d of %d in %.3f s; %s" % (B.nconv, a.nev, time.perf_counter() - t0, B.stats))
+    defl = dict(deflate=B, nev=a.nev)
+    # the first source once more without deflation, on a copy of the generator's state: the iterations deflation saves
+    state = rng.state()
+    _, _, st0 = q.scalarTrace(s, lo, rng, a.mass, a.cg_prec * a.cg_prec, maxits=a.cg_max, num_stoch=1, source_type=a.source_type,
+                              dilute_type=a.dilute_type, improved_trace=bool(a.improved_trace), t_offset=rank * lt, sloppy=a.sloppy,
+                              batch=a.batch, out=None)
+    rng.set_state(state)
 t0 = time.perf_counter()
 traces, ests, st = q.scalarTrace(s, lo, rng, a.mass, a.cg_prec * a.cg_prec, maxits=a.cg_max, num_stoch=a.num_stoch,
                                  source_type=a.source_type, dilute_type=a.dilute_type, improved_trace=bool(a.improved_trace),
-                                 t_offset=rank * lt, sloppy=a.sloppy, batch=a.batch)
+                                 t_offset=rank * lt, sloppy=a.sloppy, batch=a.batch, **defl)
 total = time.perf_counter() - t0
+if a.nev > 0:
+    print("iterations of source 0: %d with %d modes, %d without (%.4f s of solves without)" %
+          (sum(st["iterations"][0]), a.nev, sum(st0["iterations"][0]), st0["solve_s"]))
 print("solves: %.4f s, dilution + contraction + slice sums: %.6f s (%.3f %% of the measurement, %.4f s)" %
       (st["solve_s"], st["contract_s"], 100.0 * st["contract_s"] / total, total))
 print("iterations per pattern:", st["iterations"])

@@ -3,6 +3,7 @@
 from point-source propagators.
 
     python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5] [-sloppy 0]
+                                   [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3]
     python -m torch.distributed.run --nproc-per-node N examples/stag_mesons.py ...     # t-sharded over N ranks
 
 For each colour the point source at (0,0,0,t0) and its three symmetric one-link shifts are solved in one lock-step batch of four
@@ -10,7 +11,9 @@ For each colour the point source at (0,0,0,t0) and its three symmetric one-link 
 no propagator leaves the GPU.  The tables are printed as printLocalMesons prints them: Walsh-Hadamard transform over the corner
 bits, normalisation nt / physVol.  The configuration is the library's RngMilc6 warm start (as examples/stag_prop.py), seeded by
 global site, so every partition sees the same gauge field.  -sloppy 1 runs the batches in mixed precision (fp32 iterations with
-fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only."""
+fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only.  -nev N computes the N lowest eigenpairs of the even/odd
+operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every batch with them; the
+measurement is then also run without deflation and the eigensolve time and the iterations with / without are printed."""
 import argparse
 import os
 import sys
@@ -29,6 +32,10 @@ ap.add_argument("-seed", type=int, default=987654321)
 ap.add_argument("-warm", type=float, default=0.5)
 ap.add_argument("-r2req", type=float, default=1e-16)
 ap.add_argument("-sloppy", type=int, default=0, choices=[0, 1, 2])
+ap.add_argument("-nev", type=int, default=0, help="deflate every batch with this many low modes (0: no eigensolve)")
+ap.add_argument("-nvecs", type=int, default=0, help="size of the Lanczos basis (default max(2 nev, nev + 8))")
+ap.add_argument("-cheb", type=int, default=12, help="Chebyshev degree (0: plain Lanczos)")
+ap.add_argument("-cheb_lo", type=float, default=0.3)
 a = ap.parse_args()
 if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1:
     sys.exit("stag_mesons.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
@@ -64,12 +71,23 @@ s = q.newStag(ctx, g)
 print("links per site, storage format, max deviation:", s.links_info())
 if a.sloppy:
     print("mixed-precision batches: fp32 link format, max deviation:", ctx.links_info_f32())
+defl = {}
+if a.nev > 0:
+    t = time.perf_counter()
+    B = s.eigs(a.nev, nvecs=a.nvecs or None, cheb_degree=a.cheb, cheb_lo=a.cheb_lo)
+    ctx.sync()
+    print("eigs: nconv %d of %d in %.3f s; %s" % (B.nconv, a.nev, time.perf_counter() - t, B.stats))
+    defl = dict(deflate=B, nev=a.nev)
+    _, _, st0 = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt, sloppy=a.sloppy)
 t = time.perf_counter()
 if a.sloppy:
-    cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt, sloppy=a.sloppy)
+    cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt, sloppy=a.sloppy, **defl)
 else:
-    cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt)
+    cl, cs, st = q.localMesonTables(s, lo, a.mass, a.t0, a.r2req, t_offset=rank * lt, **defl)
 total = time.perf_counter() - t
+if a.nev > 0:
+    print("iterations: %d with %d modes, %d without (%.4f s of solves without)" %
+          (int(np.sum(st["iterations"])), a.nev, int(np.sum(st0["iterations"])), st0["solve_s"]))
 print("solves: %.4f s (iterations per colour [local, x, y, z]: %s)" % (st["solve_s"], st["iterations"]))
 if a.sloppy:
     print("reliable updates per colour [local, x, y, z]: %s" % (st["updates"],))

@@ -392,7 +392,7 @@ int qexhip_dev_cfield_slices(qexhip_handle h, int cfield, double *out);
 /* ---------------- low modes of the even/odd operator and deflated solves ----------------
  * src/eigens/hisqev.nim: the lowest singular pairs (sv_i, v_i) of D_oe on the even sites (`hisqev` with EigOpts, hisqev.nim:380-560,
  * block Lanczos of src/eigens/svdLanczos.nim + Rayleigh-Ritz passes), and the deflated solveEE of its main program (:653-705).
- * Everything here lives on the EVEN sites.  The operator is H = -D_eo D_oe in this header's normalisation: qexhip_dev_op_xx(r, x, m2, 1)
+ * Everything here lives on the EVEN sites (the deflated batch below also deflates odd-parity solves, from the same even basis).  The operator is H = -D_eo D_oe in this header's normalisation: qexhip_dev_op_xx(r, x, m2, 1)
  * is 4 (m2 + H) x.  Eigenvalues are lambda_i = sv_i^2.  Whatever links the operator currently holds define H (newStag, newStag3, HISQ,
  * nHYP).
  *
@@ -406,7 +406,13 @@ int qexhip_dev_cfield_slices(qexhip_handle h, int cfield, double *out);
  *                fp64 accumulation in a fixed order (bit-identical run to run); t-sharded: ONE rank sum of 2 n doubles
  *   block_axpy   y.even += sum_j (coef[2 j] + i coef[2 j + 1]) v_{i0+j}: one pass over the n vectors, y read and written once
  *   rotate       V[:, 0:k] <- V[:, 0:m] Q in place, Q real m x k column-major (Q[j + m c]), 1 <= k <= m <= nvecs.  Vectors k .. m-1
- *                are LEFT AS THEY WERE (not zeroed, not orthogonal to the new ones): they are scratch afterwards. */
+ *                are LEFT AS THEY WERE (not zeroed, not orthogonal to the new ones): they are scratch afterwards.
+ *   block_dot_multi   out[(k n + j) 2 + re|im] = <v_{i0+j}, w_k.even> for the nrhs (1..4) fields w_ids[k] in ONE pass over the n vectors
+ *                (every basis element loaded once for all of them).  Each number is BIT FOR BIT what block_dot returns for w_k alone;
+ *                t-sharded: ONE rank sum of 2 n nrhs doubles
+ *   block_axpy_multi  y_k.even += sum_j (coef[(k n + j) 2] + i coef[(k n + j) 2 + 1]) v_{i0+j} for the nrhs distinct fields y_ids[k], one
+ *                pass; each y_k is BIT FOR BIT what block_axpy gives with its own coefficients
+ *   Bad vector ranges, nrhs outside 1..4 and repeated y_ids: QEXHIP_ERR_ARG before anything is launched. */
 #define QEXHIP_EIG_MAX_NVECS 512
 int qexhip_eig_new(qexhip_handle h, int nvecs, int *basis);
 int qexhip_eig_free(qexhip_handle h, int basis);
@@ -415,6 +421,8 @@ int qexhip_eig_set_vector(qexhip_handle h, int basis, int i, int field_id);
 int qexhip_eig_block_dot(qexhip_handle h, int basis, int i0, int n, int w_field_id, double *out);
 int qexhip_eig_block_axpy(qexhip_handle h, int basis, int i0, int n, const double *coef, int y_field_id);
 int qexhip_eig_rotate(qexhip_handle h, int basis, int m, int k, const double *Q);
+int qexhip_eig_block_dot_multi(qexhip_handle h, int basis, int i0, int n, int nrhs, const int *w_ids, double *out /* [nrhs][n][2] */);
+int qexhip_eig_block_axpy_multi(qexhip_handle h, int basis, int i0, int n, int nrhs, const double *coef /* [nrhs][n][2] */, const int *y_ids);
 /* EigOpts (src/eigens/hisqev.nim: nev, nvecs, relerr, abserr, maxup) for the thick-restart Lanczos with Chebyshev acceleration:
  *   nev, nvecs     pairs wanted / size of the Krylov basis (= vectors of the basis object used), 1 <= nev <= nvecs <= QEXHIP_EIG_MAX_NVECS
  *   relerr, abserr a pair counts as converged when its residual |H v - lambda v| <= max(abserr, relerr * lambda)
@@ -454,6 +462,31 @@ int qexhip_stag_solve_xx_deflated(qexhip_handle h, int basis, int nev, double *x
                                   int maxits, int sloppy, int *iters, double *r2_over_b2);
 int qexhip_stag_solve_deflated(qexhip_handle h, int basis, int nev, double *x, const double *b, double mass, double r2req, int maxits,
                                int sloppy, int *iters, double *r2_final);
+/* The deflated LOCK-STEP BATCH: the steps above for n (1..4) systems with their own masses, on EITHER parity, from the even basis.
+ * D is anti-Hermitian, so H_e = -D_eo D_oe = D_oe^+ D_oe and H_o = D_oe D_oe^+: an even pair (v_i, lambda_i) with lambda_i > 0 gives the
+ * odd pair (D_oe v_i / sqrt(lambda_i), lambda_i), and with A_o = 4 (m^2 + H_o) the odd projection is
+ *   x0.odd = D_oe V diag(1 / (4 lambda_i (lambda_i + m^2))) V^+ (-D_eo b.odd)
+ * (a mode with lambda_i <= 0 gets coefficient 0): two single-parity sweeps per system, no second basis.  The projections of all
+ * systems are ONE block_dot_multi and ONE block_axpy_multi, so a system's starting guess is bit for bit the single deflated solve's;
+ * a system with |b_k - A x0_k|^2 <= r2req_k |b_k|^2 is finished with 0 iterations, the others run as ONE lock-step batch CG (sloppy = 0:
+ * the fp64 batch; > 0: the mixed-precision one, refused with QEXHIP_ERR_ARG on t-sharded contexts before anything is launched) on
+ * A d_k = r0_k, then x_k = x0_k + d_k.  iters, r2_over_b2 (the TRUE residuals) and nupdates (may be NULL) are arrays of n; maxits is
+ * shared.  nev = 0 is the undeflated batch entry itself: same bits, same iteration counts.  solve_batch_deflated: n x Staggered.solve
+ * (qexhip_stag_solve_batch semantics: same ReconR / ReconL decisions, outer loop and maxits sharing) whose inner solveXX groups of BOTH
+ * parities are this batch.  dev_: resident fields, no solution aliasing a source or another solution; stag_: host fields.
+ * QEXHIP_ERR_STATE for a basis of other links.  The single-system deflated entries above are unchanged: their odd sources stay
+ * undeflated. */
+int qexhip_dev_solve_xx_batch_deflated(qexhip_handle h, int basis, int nev, int n, const int *x_ids, const int *b_ids, const double *mass,
+                                       const double *r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2,
+                                       int *nupdates);
+int qexhip_stag_solve_xx_batch_deflated(qexhip_handle h, int basis, int nev, int n, double *const *x, const double *const *b,
+                                        const double *mass, const double *r2req, int maxits, int par_even, int sloppy, int *iters,
+                                        double *r2_over_b2, int *nupdates);
+int qexhip_dev_solve_batch_deflated(qexhip_handle h, int basis, int nev, int n, const int *x_ids, const int *b_ids, const double *mass,
+                                    const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);
+int qexhip_stag_solve_batch_deflated(qexhip_handle h, int basis, int nev, int n, double *const *x, const double *const *b,
+                                     const double *mass, const double *r2req, int maxits, int sloppy, int *iters, double *r2_final,
+                                     int *nupdates);
 /* Dense real symmetric eigensolver on the host (cyclic Jacobi, no external library): what the eigensolver diagonalises at every
  * restart (the reference calls LAPACK there, src/eigens/lapack.nim).  a: n x n symmetric; w[n]: eigenvalues ascending; z (may be
  * NULL): n x n column-major, column i the unit eigenvector of w[i].  Needs no device. */

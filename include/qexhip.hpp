@@ -221,6 +221,13 @@ class Staggered {
     void blockDot(int i0, int n, int wField, double *out) const { check(qexhip_eig_block_dot(c.h, id, i0, n, wField, out)); }
     void blockAxpy(int i0, int n, const double *coef, int yField) { check(qexhip_eig_block_axpy(c.h, id, i0, n, coef, yField)); }
     void rotate(int m, int k, const double *Q) { check(qexhip_eig_rotate(c.h, id, m, k, Q)); }
+    // the two for nrhs <= 4 fields in one pass over the basis, bit for bit the single calls: out / coef [nrhs][n][2]
+    void blockDotMulti(int i0, int n, const std::vector<int> &wFields, double *out) const {
+      check(qexhip_eig_block_dot_multi(c.h, id, i0, n, (int)wFields.size(), wFields.data(), out));
+    }
+    void blockAxpyMulti(int i0, int n, const double *coef, const std::vector<int> &yFields) {
+      check(qexhip_eig_block_axpy_multi(c.h, id, i0, n, (int)yFields.size(), coef, yFields.data()));
+    }
   };
   void eigs(EigBasis &B, const qexhip_eig_opts &o) {
     B.evals.assign(o.nev > 0 ? o.nev : 0, 0.0); B.resid = B.evals;
@@ -261,6 +268,35 @@ class Staggered {
       sp.seconds += dt; sp.calls += 1; sp.iterations += its[j]; sp.iterationsMax = std::max(sp.iterationsMax, its[j]);
       sp.flops += flops(its[j]); sp.r2 = fin[j]; sp.reliableUpdates += nup[j];
     }
+  }
+  // the deflated lock-step batch (qexhip_stag_solve_batch_deflated / _xx_batch_deflated): n <= 4 systems, both parities deflated from
+  // the even basis B with its leading nev vectors; sloppy = 0, 1 or 2 is the precision of the batched CG.  solveBatch: n x solve;
+  // solveXXBatch: n x solveEE / solveOO, returning the true |b - A x|^2 / |b|^2 per system
+  std::vector<double> deflatedBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms,
+                                    std::vector<SolverParams> &sps, const EigBasis &B, int nev, int sloppy, int xxParity) {
+    const int n = (int)xs.size();
+    if (sloppy < 0 || sloppy > 2) throw std::invalid_argument("deflated batch: sloppy = 0, 1 or 2");
+    std::vector<double *> xp; std::vector<const double *> bp; std::vector<double> rq, fin(n); std::vector<int> its(n), nup(n);
+    int maxits = sps.at(0).maxits;
+    for (int j = 0; j < n; j++) { xp.push_back(xs[j].data()); bp.push_back(bs.at(j).data()); rq.push_back(sps.at(j).r2req); maxits = std::min(maxits, sps[j].maxits); }
+    auto t0 = std::chrono::steady_clock::now();
+    if (xxParity < 0) check(qexhip_stag_solve_batch_deflated(c_.h, B.id, nev, n, xp.data(), bp.data(), ms.data(), rq.data(), maxits, sloppy, its.data(), fin.data(), nup.data()));
+    else check(qexhip_stag_solve_xx_batch_deflated(c_.h, B.id, nev, n, xp.data(), bp.data(), ms.data(), rq.data(), maxits, xxParity, sloppy, its.data(), fin.data(), nup.data()));
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / n;
+    for (int j = 0; j < n; j++) {
+      SolverParams &sp = sps[j];
+      sp.seconds += dt; sp.calls += 1; sp.iterations += its[j]; sp.iterationsMax = std::max(sp.iterationsMax, its[j]);
+      sp.flops += flops(its[j]); sp.r2 = fin[j]; sp.reliableUpdates += nup[j];
+    }
+    return fin;
+  }
+  void solveBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms, std::vector<SolverParams> &sps,
+                  const EigBasis &B, int nev, int sloppy = 0) {
+    deflatedBatch(xs, bs, ms, sps, B, nev, sloppy, -1);
+  }
+  std::vector<double> solveXXBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms,
+                                   std::vector<SolverParams> &sps, const EigBasis &B, int nev, bool parEven = true, int sloppy = 0) {
+    return deflatedBatch(xs, bs, ms, sps, B, nev, sloppy, parEven ? 1 : 0);
   }
   // multi-mass Staggered.solve(xs, b, ms, sp) (stagSolve.nim:347-446).  sloppy = -1: fp64, and a sloppy SolverParams is refused (as
   // before); 0, 1, 2: the precision of the inner multi-shift CG, chosen explicitly (qexhip_stag_solve_multi_sloppy), overriding

@@ -87,6 +87,12 @@ SYMBOLS = [
     ("qexhip_dev_solve_xx_deflated", _ci, [_vp, _ci, _ci, _ci, _ci, _cd, _cd, _ci, _ci, _pi, _pd]),
     ("qexhip_stag_solve_xx_deflated", _ci, [_vp, _ci, _ci, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),
     ("qexhip_stag_solve_deflated", _ci, [_vp, _ci, _ci, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),
+    ("qexhip_eig_block_dot_multi", _ci, [_vp, _ci, _ci, _ci, _ci, _pi, _vp]),
+    ("qexhip_eig_block_axpy_multi", _ci, [_vp, _ci, _ci, _ci, _ci, _vp, _pi]),
+    ("qexhip_dev_solve_xx_batch_deflated", _ci, [_vp, _ci, _ci, _ci, _pi, _pi, _pd, _pd, _ci, _ci, _ci, _pi, _pd, _pi]),
+    ("qexhip_stag_solve_xx_batch_deflated", _ci, [_vp, _ci, _ci, _ci, _vp, _vp, _pd, _pd, _ci, _ci, _ci, _pi, _pd, _pi]),
+    ("qexhip_dev_solve_batch_deflated", _ci, [_vp, _ci, _ci, _ci, _pi, _pi, _pd, _pd, _ci, _ci, _pi, _pd, _pi]),
+    ("qexhip_stag_solve_batch_deflated", _ci, [_vp, _ci, _ci, _ci, _vp, _vp, _pd, _pd, _ci, _ci, _pi, _pd, _pi]),
     ("qexhip_symeig_host", _ci, [_pd, _ci, _pd, _pd]),   # data pointer, not a handle
     ("qexhip_dev_norm2", _ci, [_vp, _ci, _ci, _pd]),
     ("qexhip_dev_redot", _ci, [_vp, _ci, _ci, _ci, _pd]),

@@ -825,6 +825,42 @@ extern "C" int qexhip_eig_block_axpy(qexhip_handle c, int basis, int i0, int n, 
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
+// the multi-right-hand-side forms (the projections of the deflated lock-step batch): out[nrhs][n][2], coef[nrhs][n][2]
+static int eig_multi_args(qexhip_ctx *c, int basis, int i0, int n, int nrhs, const int *ids, bool distinct, const char *who, EigBasis **B, DevField **f) {
+  CHK(eig_basis_find(c, basis, B));
+  if (nrhs < 1 || nrhs > EIG_MAXRHS) { qexhip_set_error("%s: 1 <= nrhs <= %d (nrhs = %d)", who, EIG_MAXRHS, nrhs); return QEXHIP_ERR_ARG; }
+  if (i0 < 0 || n < 1 || i0 > (*B)->nvecs - n) { qexhip_set_error("%s: vectors %d..%d of a basis of %d", who, i0, i0 + n - 1, (*B)->nvecs); return QEXHIP_ERR_ARG; }
+  for (int k = 0; k < nrhs; k++) {
+    CHK(find_field(c, ids[k], &f[k]));
+    for (int q = 0; distinct && q < k; q++)
+      if (ids[q] == ids[k]) { qexhip_set_error("%s: fields %d and %d are the same (id %d)", who, q, k, ids[k]); return QEXHIP_ERR_ARG; }
+  }
+  return 0;
+}
+extern "C" int qexhip_eig_block_dot_multi(qexhip_handle c, int basis, int i0, int n, int nrhs, const int *w_ids, double *out) {
+  if (!c || !w_ids || !out) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevField *f[EIG_MAXRHS];
+  CHK(eig_multi_args(c, basis, i0, n, nrhs, w_ids, false, "eig_block_dot_multi", &B, f));
+  HIPCHK(hipSetDevice(c->device));
+  double2 *dots;
+  CHK(eig_coef_buffers(c, &dots, nullptr));
+  CHK(eig_block_dot_mrhs(c, *B, i0, n, nrhs, f, dots));
+  HIPCHK(hipMemcpyAsync(out, dots, sizeof(double) * 2 * n * nrhs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return peer_check(c);
+}
+extern "C" int qexhip_eig_block_axpy_multi(qexhip_handle c, int basis, int i0, int n, int nrhs, const double *coef, const int *y_ids) {
+  if (!c || !coef || !y_ids) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevField *f[EIG_MAXRHS];
+  CHK(eig_multi_args(c, basis, i0, n, nrhs, y_ids, true, "eig_block_axpy_multi", &B, f));
+  HIPCHK(hipSetDevice(c->device));
+  double2 *cf;
+  CHK(eig_coef_buffers(c, nullptr, &cf));
+  HIPCHK(hipMemcpyAsync(cf, coef, sizeof(double) * 2 * n * nrhs, hipMemcpyHostToDevice, c->stream));
+  CHK(eig_block_axpy_mrhs(c, *B, i0, n, nrhs, cf, 1.0, f));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
 extern "C" int qexhip_eig_rotate(qexhip_handle c, int basis, int m, int k, const double *Q) {
   if (!c || !Q) return QEXHIP_ERR_ARG;
   EigBasis *B;
@@ -1388,6 +1424,71 @@ extern "C" int qexhip_dev_solve_batch_sloppy(qexhip_handle c, int n, const int *
     CHK(find_field(c, b_ids[j], &bs[j]));
   }
   return solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates);
+}
+// ---- the deflated lock-step batch (solver.cpp: solve_xx_batch_deflated_dev; batch.hip: the full solves) ----
+// every check before anything is launched: deflate_args per mass, the batch size, the sloppy batch's one-rank condition
+static int deflate_batch_args(qexhip_ctx *c, int basis, int nev, int n, const double *mass, int sloppy, EigBasis **B) {
+  if (n < 1 || n > 4) { qexhip_set_error("batch solve: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
+  for (int k = 0; k < n; k++) CHK(deflate_args(c, basis, nev, sloppy, mass[k], B));
+  for (int k = 0; k < n; k++) if (mass[k] == 0.0) { qexhip_set_error("batch solve: mass must be non-zero"); return QEXHIP_ERR_ARG; }
+  if (sloppy) CHK(batch_sloppy_check(c, n, mass));
+  if ((*B)->gen != c->links_gen) { qexhip_set_error("deflated solve: the basis was computed on other links"); return QEXHIP_ERR_STATE; }
+  return 0;
+}
+extern "C" int qexhip_dev_solve_xx_batch_deflated(qexhip_handle c, int basis, int nev, int n, const int *x_ids, const int *b_ids,
+                                                  const double *mass, const double *r2req, int maxits, int par_even, int sloppy,
+                                                  int *iters, double *r2_over_b2, int *nupdates) {
+  if (!c || !x_ids || !b_ids || !mass || !r2req) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(deflate_batch_args(c, basis, nev, n, mass, sloppy, &B));
+  CHK(batch_alias_check(n, x_ids, b_ids));
+  DevField *xs[4], *bs[4];
+  for (int j = 0; j < n; j++) {
+    CHK(find_field(c, x_ids[j], &xs[j]));
+    CHK(find_field(c, b_ids[j], &bs[j]));
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, par_even ? 1 : 0, sloppy ? 1 : 0, iters, r2_over_b2, nupdates);
+}
+extern "C" int qexhip_dev_solve_batch_deflated(qexhip_handle c, int basis, int nev, int n, const int *x_ids, const int *b_ids,
+                                               const double *mass, const double *r2req, int maxits, int sloppy, int *iters,
+                                               double *r2_final, int *nupdates) {
+  if (!c || !x_ids || !b_ids || !mass || !r2req) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(deflate_batch_args(c, basis, nev, n, mass, sloppy, &B));
+  CHK(batch_alias_check(n, x_ids, b_ids));
+  DevField *xs[4], *bs[4];
+  for (int j = 0; j < n; j++) {
+    CHK(find_field(c, x_ids[j], &xs[j]));
+    CHK(find_field(c, b_ids[j], &bs[j]));
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2_final, nupdates);
+}
+static int solve_batch_deflated_host(qexhip_ctx *c, int basis, int nev, int n, double *const *x, const double *const *b, const double *mass,
+                                     const double *r2req, int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates) {
+  if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
+  EigBasis *B;
+  CHK(deflate_batch_args(c, basis, nev, n, mass, sloppy, &B));
+  for (int j = 0; j < n; j++) if (!x[j] || !b[j]) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  DevField *xs[4], *bs[4];
+  CHK(batch_io_fields(c, n, xs, bs));
+  for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
+  if (xx_parity >= 0) CHK(solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, xx_parity, sloppy ? 1 : 0, iters, r2, nupdates));
+  else CHK(solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2, nupdates));
+  for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
+  return 0;
+}
+extern "C" int qexhip_stag_solve_xx_batch_deflated(qexhip_handle c, int basis, int nev, int n, double *const *x, const double *const *b,
+                                                   const double *mass, const double *r2req, int maxits, int par_even, int sloppy,
+                                                   int *iters, double *r2_over_b2, int *nupdates) {
+  return solve_batch_deflated_host(c, basis, nev, n, x, b, mass, r2req, maxits, par_even ? 1 : 0, sloppy, iters, r2_over_b2, nupdates);
+}
+extern "C" int qexhip_stag_solve_batch_deflated(qexhip_handle c, int basis, int nev, int n, double *const *x, const double *const *b,
+                                                const double *mass, const double *r2req, int maxits, int sloppy, int *iters,
+                                                double *r2_final, int *nupdates) {
+  return solve_batch_deflated_host(c, basis, nev, n, x, b, mass, r2req, maxits, -1, sloppy, iters, r2_final, nupdates);
 }
 extern "C" int qexhip_nhyp_release(qexhip_handle c) {
   if (!c) return QEXHIP_ERR_ARG;

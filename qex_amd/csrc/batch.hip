@@ -549,8 +549,10 @@ int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
 }  // namespace
 
 // sloppy > 0: the inner solveXX's are the mixed-precision lock-step batch (batch_f32.hip), nupdates[j] <- system j's reliable updates
+// defl (with nev > 0): the inner solveXX groups of BOTH parities are the deflated batch (solver.cpp); the ReconL / ReconR decisions, the
+// outer loop and the sharing of maxits are the same
 static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
-                                 int maxits, int *iters, double *r2_final, int sloppy, int *nupdates) {
+                                 int maxits, int *iters, double *r2_final, int sloppy, int *nupdates, EigBasis *defl = nullptr, int nev = 0) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
   BatchState *B;
   CHK(batch_state(c, 7 * QX_MAXRHS, &B));        // 4 CG fields + r, y, d per system
@@ -605,7 +607,8 @@ static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **
         }
       if (!k) continue;
       // systems of one group share maxits: the remaining budget of the one that has used least
-      if (sloppy) CHK(solve_xx_batch_sloppy_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr, nup));
+      if (defl && nev > 0) CHK(solve_xx_batch_deflated_dev(c, *defl, nev, k, xs, bs, ms, rrs, mx, par, sloppy ? 1 : 0, its, nullptr, nup));
+      else if (sloppy) CHK(solve_xx_batch_sloppy_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr, nup));
       else CHK(solve_xx_batch_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr));
       for (int i = 0; i < k; i++) {
         S[idx[i]].n = its[i];
@@ -656,6 +659,16 @@ int solve_full_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b
   }
   CHK(batch_sloppy_check(c, n, mass));
   return solve_full_batch_impl(c, n, x, b, mass, r2req, maxits, iters, r2_final, sloppy, nupdates);
+}
+// the same with the inner batches deflated from the even basis B; nev = 0 is solve_full_batch_sloppy_dev
+int solve_full_batch_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, int n, DevField **x, DevField **b, const double *mass,
+                                  const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates) {
+  if (nev == 0) return solve_full_batch_sloppy_dev(c, n, x, b, mass, r2req, maxits, sloppy, iters, r2_final, nupdates);
+  if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
+  if (nev < 0 || nev > B.nvecs) { qexhip_set_error("deflated solve: nev = %d of a basis of %d vectors", nev, B.nvecs); return -1; }
+  if (B.gen != c->links_gen) { qexhip_set_error("deflated solve: the basis was computed on other links"); return -3; }
+  if (sloppy) CHK(batch_sloppy_check(c, n, mass));
+  return solve_full_batch_impl(c, n, x, b, mass, r2req, maxits, iters, r2_final, sloppy, nupdates, &B, nev);
 }
 
 // the first `count` (<= 4 per system) CG work fields of the batch state, for the mixed-precision batch (which leaves the fp64 CG's idle)

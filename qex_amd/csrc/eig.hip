@@ -8,6 +8,8 @@
 //   k_block_dot    c_j = <v_j, w>, j < n: a wavefront takes one 64-site tile, keeps the tile of w in registers and streams the n basis
 //                  vectors' tiles past it -- w is read once (per 128 vectors), every basis vector once
 //   k_block_axpy   y += scale * sum_j coef_j v_j: one pass over the basis, y read and written once
+//   k_block_dot_mrhs / k_block_axpy_mrhs   the two for up to four right-hand sides in one pass over the basis (the deflated lock-step batch),
+//                  every number bit for bit the single kernel's
 //   k_rotate       V[:, 0:k] <- V[:, 0:m] Q in place: a workgroup stages all m inputs of its block of rows in LDS, then writes its k outputs
 // A basis holds the body tiles of the EVEN parity only ([tile][3][64] double2 per vector: vec_off), half the memory of a field; vectors
 // are copied to / from the even half of an ordinary field when the operator has to run on them.
@@ -15,6 +17,7 @@
 #include "../../include/qexhip.h"
 #include "reduce.h"
 #include <algorithm>
+#include <cstring>
 
 #define EIG_NJ 128          // basis vectors per k_block_dot launch (its LDS accumulators: 4 waves x EIG_NJ complex)
 #define EIG_DOT_WG 1024     // at most this many workgroups (= partial sums per vector) per k_block_dot launch
@@ -24,6 +27,7 @@ struct EigWork {
   bool have[EIG_NF]{};
   double2 *dots = nullptr, *coef = nullptr;   // EIG_MAX_NVECS each
   double *parts = nullptr;                    // 2 * EIG_NJ * EIG_DOT_WG
+  double *parts_mrhs = nullptr;               // EIG_MAXRHS times as much, allocated by the first multi-right-hand-side block dot
   double *Q = nullptr;                        // EIG_MAX_NVECS^2
   int lds_attr = 0;                           // k_rotate instantiations whose dynamic LDS limit was raised
 };
@@ -32,8 +36,8 @@ static int eig_work(qexhip_ctx *c, EigWork **w) {
   if (!c->eig) {
     EigWork *e = new EigWork;
     c->eig = e;
-    HIPCHK(hipMalloc((void **)&e->dots, sizeof(double2) * EIG_MAX_NVECS));
-    HIPCHK(hipMalloc((void **)&e->coef, sizeof(double2) * EIG_MAX_NVECS));
+    HIPCHK(hipMalloc((void **)&e->dots, sizeof(double2) * EIG_MAX_NVECS * EIG_MAXRHS));    // [rhs][vector] in the multi-right-hand-side forms
+    HIPCHK(hipMalloc((void **)&e->coef, sizeof(double2) * EIG_MAX_NVECS * EIG_MAXRHS));
     HIPCHK(hipMalloc((void **)&e->parts, sizeof(double) * 2 * EIG_NJ * EIG_DOT_WG));
     HIPCHK(hipMalloc((void **)&e->Q, sizeof(double) * EIG_MAX_NVECS * EIG_MAX_NVECS));
   }
@@ -47,6 +51,7 @@ void eig_state_free(qexhip_ctx *c) {
   if (e->dots) (void)hipFree(e->dots);
   if (e->coef) (void)hipFree(e->coef);
   if (e->parts) (void)hipFree(e->parts);
+  if (e->parts_mrhs) (void)hipFree(e->parts_mrhs);
   if (e->Q) (void)hipFree(e->Q);
   delete e;
   c->eig = nullptr;
@@ -224,6 +229,99 @@ int eig_block_dot(qexhip_ctx *c, const EigBasis &B, int i0, int n, const DevFiel
   return 0;
 }
 
+// The same for nrhs (<= 4) vectors w_k at once: a wavefront keeps the three colours of ALL w_k tiles in registers (12 double2 at most)
+// and every basis element is loaded once for all of them.  Tile -> wave -> workgroup mapping, nwg, the fma chains, wave_sum and
+// every summation order are those of k_block_dot / k_block_dot_final, so the number (k, j) is bit for bit what eig_block_dot returns
+// for w_k alone.  parts[((k n + j) 2 + re|im) * nwg + workgroup]; LDS acc[4][NRHS][EIG_NJ] = 32 KiB at NRHS = 4.
+struct EigMrhsPtrs { const double2 *w[EIG_MAXRHS]; double2 *y[EIG_MAXRHS]; };
+template <int NRHS>
+__global__ void __launch_bounds__(256) k_block_dot_mrhs(const double2 *__restrict__ V, size_t n2, int n, EigMrhsPtrs P, int ntile, int Vh,
+                                                        double *__restrict__ parts) {
+  __shared__ double2 acc[4][NRHS][EIG_NJ];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < NRHS; k++)
+    for (int j = lane; j < n; j += 64) acc[wave][k][j] = make_double2(0, 0);
+  __syncthreads();
+  for (int tile = blockIdx.x * 4 + wave; tile < ntile; tile += gridDim.x * 4) {
+    const bool valid = tile * 64 + lane < Vh;
+    const size_t base = (size_t)tile * 192 + lane;
+    const double2 z = make_double2(0, 0);
+    double2 w0[NRHS], w1[NRHS], w2[NRHS];
+#pragma unroll
+    for (int k = 0; k < NRHS; k++) {
+      const double2 *w = P.w[k];
+      w0[k] = valid ? w[base] : z; w1[k] = valid ? w[base + 64] : z; w2[k] = valid ? w[base + 128] : z;
+    }
+    for (int j0 = 0; j0 < n; j0 += 4) {          // four vectors' loads in flight before the first reduction
+      double2 a[4], b[4], d[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int j = j0 + u < n ? j0 + u : n - 1;
+        const double2 *v = V + (size_t)j * n2 + base;
+        a[u] = valid ? v[0] : z; b[u] = valid ? v[64] : z; d[u] = valid ? v[128] : z;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if (j0 + u >= n) break;
+#pragma unroll
+        for (int k = 0; k < NRHS; k++) {
+          double ar = fma(a[u].x, w0[k].x, a[u].y * w0[k].y), ai = fma(a[u].x, w0[k].y, -a[u].y * w0[k].x);
+          ar = fma(b[u].x, w1[k].x, fma(b[u].y, w1[k].y, ar)); ai = fma(b[u].x, w1[k].y, fma(-b[u].y, w1[k].x, ai));
+          ar = fma(d[u].x, w2[k].x, fma(d[u].y, w2[k].y, ar)); ai = fma(d[u].x, w2[k].y, fma(-d[u].y, w2[k].x, ai));
+          ar = wave_sum(ar);
+          ai = wave_sum(ai);
+          if (lane == 0) { acc[wave][k][j0 + u].x += ar; acc[wave][k][j0 + u].y += ai; }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int nwg = gridDim.x;
+  for (int i = threadIdx.x; i < NRHS * n; i += 256) {
+    const int k = i / n, j = i - k * n;
+    parts[(size_t)(2 * i) * nwg + blockIdx.x] = (acc[0][k][j].x + acc[1][k][j].x) + (acc[2][k][j].x + acc[3][k][j].x);
+    parts[(size_t)(2 * i + 1) * nwg + blockIdx.x] = (acc[0][k][j].y + acc[1][k][j].y) + (acc[2][k][j].y + acc[3][k][j].y);
+  }
+}
+// k_block_dot_final's sum for right-hand side blockIdx.y: out[k][j0 + j] of an [nrhs][ntot] array (ntot2 = 2 ntot doubles per row)
+__global__ void __launch_bounds__(256) k_block_dot_final_mrhs(const double *__restrict__ parts, int nwg, int nj2, double *__restrict__ out, int ntot2) {
+  const double *p = parts + ((size_t)blockIdx.y * nj2 + blockIdx.x) * nwg;
+  double a = 0;
+  for (int g = threadIdx.x; g < nwg; g += 256) a += p[g];
+  const double r = block_sum_256(a);
+  if (threadIdx.x == 0) out[(size_t)blockIdx.y * ntot2 + blockIdx.x] = r;
+}
+int eig_block_dot_mrhs(qexhip_ctx *c, const EigBasis &B, int i0, int n, int nrhs, DevField *const *w, double2 *dots) {
+  CHK(basis_index_check(B, i0, n, "eig_block_dot_mrhs"));
+  CHK(basis_geom_check(c, B));
+  if (nrhs < 1 || nrhs > EIG_MAXRHS) { qexhip_set_error("eig_block_dot_mrhs: 1 <= nrhs <= %d", EIG_MAXRHS); return QEXHIP_ERR_ARG; }
+  EigWork *e;
+  CHK(eig_work(c, &e));
+  if (!e->parts_mrhs) HIPCHK(hipMalloc((void **)&e->parts_mrhs, sizeof(double) * 2 * EIG_NJ * EIG_DOT_WG * EIG_MAXRHS));
+  const int nwg = std::min(EIG_DOT_WG, (c->g.ntile + 3) / 4);
+  EigMrhsPtrs P;
+  memset(&P, 0, sizeof P);
+  for (int k = 0; k < nrhs; k++) P.w[k] = w[k]->par(0);
+  {
+    ScopedTimer tm(c, "eig_dot", c->stream);
+    for (int j0 = 0; j0 < n; j0 += EIG_NJ) {
+      const int nj = std::min(EIG_NJ, n - j0);
+      const double2 *V = B.v + (size_t)(i0 + j0) * B.n2;
+      switch (nrhs) {
+        case 1: k_block_dot_mrhs<1><<<nwg, 256, 0, c->stream>>>(V, B.n2, nj, P, c->g.ntile, c->g.Vh, e->parts_mrhs); break;
+        case 2: k_block_dot_mrhs<2><<<nwg, 256, 0, c->stream>>>(V, B.n2, nj, P, c->g.ntile, c->g.Vh, e->parts_mrhs); break;
+        case 3: k_block_dot_mrhs<3><<<nwg, 256, 0, c->stream>>>(V, B.n2, nj, P, c->g.ntile, c->g.Vh, e->parts_mrhs); break;
+        default: k_block_dot_mrhs<4><<<nwg, 256, 0, c->stream>>>(V, B.n2, nj, P, c->g.ntile, c->g.Vh, e->parts_mrhs); break;
+      }
+      k_block_dot_final_mrhs<<<dim3(2 * nj, nrhs), 256, 0, c->stream>>>(e->parts_mrhs, nwg, 2 * nj, (double *)(dots + j0), 2 * n);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  if (multi_rank(c)) CHK(comm_allreduce(c, (double *)dots, 2 * n * nrhs));      // ONE rank sum of 2 n nrhs doubles
+  return 0;
+}
+
 // ---------------- block axpy ----------------
 // y_i += scale * sum_j coef_j v_j,i: a lane owns element i, the coefficients are wave-uniform loads, eight basis loads in flight.
 __global__ void __launch_bounds__(256) k_block_axpy(const double2 *__restrict__ V, size_t n2, int n, const double2 *__restrict__ coef,
@@ -248,6 +346,59 @@ int eig_block_axpy(qexhip_ctx *c, const EigBasis &B, int i0, int n, const double
   CHK(basis_geom_check(c, B));
   ScopedTimer tm(c, "eig_axpy", c->stream);
   k_block_axpy<<<grid_for(B.n2), 256, 0, c->stream>>>(B.v + (size_t)i0 * B.n2, B.n2, n, coef, scale, y.par(0));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// y_k += scale * sum_j coef[k][j] v_j for nrhs (<= 4) fields at once: every basis element is loaded once, and the fma order over j is
+// k_block_axpy's, so each y_k is bit for bit what eig_block_axpy gives with its own coefficients.
+template <int NRHS>
+__global__ void __launch_bounds__(256) k_block_axpy_mrhs(const double2 *__restrict__ V, size_t n2, int n, const double2 *__restrict__ coef,
+                                                         double scale, EigMrhsPtrs P) {
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n2; i += (size_t)gridDim.x * 256) {
+    double sr[NRHS], si[NRHS];
+#pragma unroll
+    for (int k = 0; k < NRHS; k++) sr[k] = si[k] = 0;
+    const double2 *v = V + i;
+#pragma unroll 8
+    for (int j = 0; j < n; j++) {
+      const double2 x = v[(size_t)j * n2];
+#pragma unroll
+      for (int k = 0; k < NRHS; k++) {
+        const double2 cf = coef[k * n + j];
+        sr[k] = fma(cf.x, x.x, fma(-cf.y, x.y, sr[k]));
+        si[k] = fma(cf.x, x.y, fma(cf.y, x.x, si[k]));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NRHS; k++) {
+      double2 yv = P.y[k][i];
+      yv.x = fma(scale, sr[k], yv.x);
+      yv.y = fma(scale, si[k], yv.y);
+      P.y[k][i] = yv;
+    }
+  }
+}
+// coef: [nrhs][n] on the device; the y_k are distinct fields
+int eig_block_axpy_mrhs(qexhip_ctx *c, const EigBasis &B, int i0, int n, int nrhs, const double2 *coef, double scale, DevField *const *y) {
+  CHK(basis_index_check(B, i0, n, "eig_block_axpy_mrhs"));
+  CHK(basis_geom_check(c, B));
+  if (nrhs < 1 || nrhs > EIG_MAXRHS) { qexhip_set_error("eig_block_axpy_mrhs: 1 <= nrhs <= %d", EIG_MAXRHS); return QEXHIP_ERR_ARG; }
+  for (int k = 0; k < nrhs; k++)
+    for (int q = 0; q < k; q++)
+      if (y[k]->d == y[q]->d) { qexhip_set_error("eig_block_axpy_mrhs: outputs %d and %d are the same field", q, k); return QEXHIP_ERR_ARG; }
+  EigMrhsPtrs P;
+  memset(&P, 0, sizeof P);
+  for (int k = 0; k < nrhs; k++) P.y[k] = y[k]->par(0);
+  ScopedTimer tm(c, "eig_axpy", c->stream);
+  const double2 *V = B.v + (size_t)i0 * B.n2;
+  const int grid = grid_for(B.n2);
+  switch (nrhs) {
+    case 1: k_block_axpy_mrhs<1><<<grid, 256, 0, c->stream>>>(V, B.n2, n, coef, scale, P); break;
+    case 2: k_block_axpy_mrhs<2><<<grid, 256, 0, c->stream>>>(V, B.n2, n, coef, scale, P); break;
+    case 3: k_block_axpy_mrhs<3><<<grid, 256, 0, c->stream>>>(V, B.n2, n, coef, scale, P); break;
+    default: k_block_axpy_mrhs<4><<<grid, 256, 0, c->stream>>>(V, B.n2, n, coef, scale, P); break;
+  }
   HIPCHK(hipGetLastError());
   return 0;
 }

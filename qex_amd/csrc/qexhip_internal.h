@@ -286,6 +286,8 @@ int batch_io_fields(qexhip_ctx *c, int n, DevField **xs, DevField **bs);
 int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                          int maxits, int *iters, double *r2_final);
 int batch_work_fields(qexhip_ctx *c, int count, DevField **out);
+int solve_xx_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                       int maxits, int par_even, int *iters, double *r2_over_b2);      // n (1..4) solveXX's in lock-step, fp64
 // ---- batch_f32.hip: the mixed-precision lock-step batch (one rank, no ghost zones) ----
 void batch_f32_state_free(qexhip_ctx *c);
 int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass);     // n in 1..4, not t-sharded, no mass 0 -- before anything is launched
@@ -449,17 +451,27 @@ int pool_field(qexhip_ctx *c, int idx, DevField **f);
 
 int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevField &b, double mass, double r2req, int maxits,
                           int sloppy, int *iters, double *r2_over_b2);
+// the deflated lock-step batch: n <= 4 solveXX's of either parity deflated from the EVEN basis (solver.cpp); nev = 0 is the
+// undeflated batch entry itself.  r2_over_b2: the true residuals; nupdates (may be null): reliable updates of the sloppy batch
+int solve_xx_batch_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, int n, DevField **x, DevField **b, const double *mass,
+                                const double *r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates);
+// n x Staggered.solve whose inner solveXX groups of both parities are the deflated batch (batch.hip)
+int solve_full_batch_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, int n, DevField **x, DevField **b, const double *mass,
+                                  const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);
 
 // ---- eig.hip: basis of half-volume vectors + the three block kernels; eigsolve.cpp: thick-restart Lanczos ----
 #define EIG_MAX_NVECS 512       // the in-place rotation keeps m x R site rows in LDS with R >= 16: m <= 512 at 128 KiB
-enum { EIG_W = 0, EIG_T0, EIG_T1, EIG_AP, EIG_R0, EIG_D, EIG_NF };   // EigWork fields
+#define EIG_MAXRHS 4            // right-hand sides of the multi-right-hand-side block kernels = systems of a lock-step batch
+// EigWork fields; EIG_BR0 / EIG_BD / EIG_BZ + k: residual, correction and odd-projection work field of system k of a deflated batch
+enum { EIG_W = 0, EIG_T0, EIG_T1, EIG_AP, EIG_R0, EIG_D, EIG_BR0, EIG_BD = EIG_BR0 + EIG_MAXRHS, EIG_BZ = EIG_BD + EIG_MAXRHS,
+       EIG_NF = EIG_BZ + EIG_MAXRHS };
 int eig_basis_find(qexhip_ctx *c, int id, EigBasis **B);
 int eig_basis_new(qexhip_ctx *c, int nvecs, int *id);
 int eig_basis_free(qexhip_ctx *c, int id);
 void eig_bases_free(qexhip_ctx *c);                 // qexhip_finalize
 void eig_state_free(qexhip_ctx *c);                 // the work fields and buffers only (qexhip_release_workspace)
 int eig_field(qexhip_ctx *c, int slot, DevField **f);
-int eig_coef_buffers(qexhip_ctx *c, double2 **dots, double2 **coef);      // EIG_MAX_NVECS complex numbers each, on the device
+int eig_coef_buffers(qexhip_ctx *c, double2 **dots, double2 **coef);      // EIG_MAXRHS x EIG_MAX_NVECS complex numbers each, on the device
 int eig_get_vector(qexhip_ctx *c, const EigBasis &B, int i, DevField &f, double scale = 1.0);   // f.even := scale v_i
 int eig_set_vector(qexhip_ctx *c, EigBasis &B, int i, const DevField &f, double scale = 1.0);   // v_i := scale f.even
 int eig_move_vector(qexhip_ctx *c, EigBasis &B, int dst, int src);
@@ -467,6 +479,10 @@ int eig_move_vector(qexhip_ctx *c, EigBasis &B, int dst, int src);
 int eig_block_dot(qexhip_ctx *c, const EigBasis &B, int i0, int n, const DevField &w, double2 *dots);
 // y.even += scale * sum_j coef[j] v_{i0+j}
 int eig_block_axpy(qexhip_ctx *c, const EigBasis &B, int i0, int n, const double2 *coef, double scale, DevField &y);
+// the two for nrhs <= EIG_MAXRHS fields in one pass over the basis, every number bit for bit the single call's:
+// dots[k][j] = <v_{i0+j}, w_k.even> ([nrhs][n]);  y_k.even += scale * sum_j coef[k][j] v_{i0+j} (the y_k distinct)
+int eig_block_dot_mrhs(qexhip_ctx *c, const EigBasis &B, int i0, int n, int nrhs, DevField *const *w, double2 *dots);
+int eig_block_axpy_mrhs(qexhip_ctx *c, const EigBasis &B, int i0, int n, int nrhs, const double2 *coef, double scale, DevField *const *y);
 // V[:, 0:k] <- V[:, 0:m] Q, Q real m x k column-major on the host
 int eig_rotate(qexhip_ctx *c, EigBasis &B, int m, int k, const double *Q);
 int eig_rayleigh(qexhip_ctx *c, EigBasis &B, int n);     // fills B.evals[0..n) where missing (one operator application each)

@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
+#include <vector>
 
 
 int get_work(qexhip_ctx *c, int slot, DevField **f) {
@@ -447,6 +448,107 @@ int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevF
   }
   if (iters) *iters = its;
   if (r2_over_b2) *r2_over_b2 = b2 != 0.0 ? n[1] / b2 : 0.0;
+  return 0;
+}
+
+// ---- the deflated lock-step batch: n <= 4 solveXX's with their own masses, of either parity, from the EVEN basis ----
+// D is anti-Hermitian, so H_e = -D_eo D_oe = D_oe^+ D_oe and H_o = D_oe D_oe^+: an even pair (v_i, lambda_i), lambda_i > 0, gives the
+// odd pair (D_oe v_i / sqrt(lambda_i), lambda_i), and with A_o = 4 (m^2 + H_o)
+//   x0.odd = D_oe V diag(1 / (4 lambda_i (lambda_i + m^2))) V^+ (-D_eo b.odd)
+// -- two single-parity sweeps per system around the same block dot / block axpy, no second basis.  The steps are those of
+// solve_xx_deflated_dev; the projections of all systems are ONE multi-right-hand-side block dot and ONE block axpy (eig.hip), the
+// systems that are not finished by the projection run as ONE lock-step batch CG on A d_k = r0_k.
+int solve_xx_batch_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, int n, DevField **x, DevField **b, const double *mass,
+                                const double *r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates) {
+  if (n < 1 || n > EIG_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", EIG_MAXRHS); return QEXHIP_ERR_ARG; }
+  if (nev < 0 || nev > B.nvecs) { qexhip_set_error("deflated solve: nev = %d of a basis of %d vectors", nev, B.nvecs); return QEXHIP_ERR_ARG; }
+  if (sloppy) CHK(batch_sloppy_check(c, n, mass));
+  for (int k = 0; k < n; k++) if (mass[k] == 0.0) { qexhip_set_error("batch solve: mass must be non-zero"); return QEXHIP_ERR_ARG; }
+  if (B.gen != c->links_gen) {
+    qexhip_set_error("deflated solve: the basis was computed on other links (the operator's links changed since)");
+    return QEXHIP_ERR_STATE;
+  }
+  if (nupdates) for (int k = 0; k < n; k++) nupdates[k] = 0;
+  if (nev == 0) {
+    if (!sloppy) return solve_xx_batch_dev(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2);
+    return solve_xx_batch_sloppy_dev(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
+  }
+  const int par = par_even ? 0 : 1;
+  CHK(eig_rayleigh(c, B, nev));
+  double2 *dots, *coef;
+  CHK(eig_coef_buffers(c, &dots, &coef));
+  DevField *Ax, *r0[EIG_MAXRHS], *d[EIG_MAXRHS], *z[EIG_MAXRHS], *w[EIG_MAXRHS];
+  CHK(eig_field(c, EIG_AP, &Ax));
+  for (int k = 0; k < n; k++) {
+    CHK(eig_field(c, EIG_BR0 + k, &r0[k]));
+    CHK(eig_field(c, EIG_BD + k, &d[k]));
+    if (!par_even) CHK(eig_field(c, EIG_BZ + k, &z[k]));
+    w[k] = b[k];
+    if (!par_even) {
+      CHK(op_stagD_pub(c, *z[k], *b[k], 0, 0.0, -1.0, 0.0));      // z_k.even = -D_eo b_k.odd (the sweep's 2D halved by stagD)
+      w[k] = z[k];
+    }
+  }
+  std::vector<double2> h((size_t)n * nev);
+  CHK(eig_block_dot_mrhs(c, B, 0, nev, n, w, dots));
+  HIPCHK(hipMemcpyAsync(h.data(), dots, sizeof(double2) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < n; k++) {
+    const double m2 = mass[k] * mass[k];
+    for (int i = 0; i < nev; i++) {
+      const double lam = B.evals[i];
+      double s = 0.25 / (lam + m2);
+      if (!par_even) s = lam > 0 ? s / lam : 0.0;
+      h[(size_t)k * nev + i].x *= s; h[(size_t)k * nev + i].y *= s;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(coef, h.data(), sizeof(double2) * h.size(), hipMemcpyHostToDevice, c->stream));
+  for (int k = 0; k < n; k++) {
+    CHK(blas_zero(c, *x[k], 2));
+    if (!par_even) CHK(blas_zero(c, *z[k], 0));
+  }
+  CHK(eig_block_axpy_mrhs(c, B, 0, nev, n, coef, 1.0, par_even ? x : z));
+  HIPCHK(hipStreamSynchronize(c->stream));              // (h is read by the copy above)
+  double b2[EIG_MAXRHS], r2[EIG_MAXRHS];
+  auto resid = [&](int k) -> int {                      // r0_k = b_k - A x_k in fp64, |r0_k|^2 -> dscal[3]
+    CHK(op_xx(c, *Ax, *x[k], mass[k] * mass[k], par_even, 0, nullptr));
+    CHK(blas_axpby(c, 1.0, *b[k], -1.0, *Ax, *r0[k], par));
+    return blas_norm2(c, *r0[k], par, &c->dscal[3]);
+  };
+  for (int k = 0; k < n; k++) {
+    if (!par_even) CHK(op_stagD_pub(c, *x[k], *z[k], 1, 0.0, 1.0, 0.0));     // x_k.odd = D_oe z_k
+    CHK(blas_norm2(c, *b[k], par, &c->dscal[2]));
+    CHK(resid(k));
+    double nn[2];
+    CHK(read_scalars(c, &c->dscal[2], 2, nn));
+    b2[k] = nn[0]; r2[k] = nn[1];
+  }
+  DevField *dx[EIG_MAXRHS], *db[EIG_MAXRHS];
+  double mm[EIG_MAXRHS], rq[EIG_MAXRHS];
+  int sel[EIG_MAXRHS], its[EIG_MAXRHS] = {0, 0, 0, 0}, nup[EIG_MAXRHS] = {0, 0, 0, 0}, ns = 0;
+  for (int k = 0; k < n; k++)
+    if (b2[k] > 0 && r2[k] > r2req[k] * b2[k]) {
+      dx[ns] = d[k]; db[ns] = r0[k]; mm[ns] = mass[k]; rq[ns] = r2req[k] * b2[k] / r2[k]; sel[ns] = k;
+      ns++;
+    }
+  if (ns > 0) {
+    if (!sloppy) CHK(solve_xx_batch_dev(c, ns, dx, db, mm, rq, maxits, par_even, its, nullptr));
+    else CHK(solve_xx_batch_sloppy_dev(c, ns, dx, db, mm, rq, maxits, par_even, its, nullptr, nup));
+    for (int q = 0; q < ns; q++) {
+      const int k = sel[q];
+      CHK(blas_axpy(c, 1.0, *dx[q], *x[k], par));
+      CHK(resid(k));
+      CHK(read_scalars(c, &c->dscal[3], 1, &r2[k]));
+    }
+  }
+  for (int k = 0; k < n; k++) {
+    if (iters) iters[k] = 0;
+    if (r2_over_b2) r2_over_b2[k] = b2[k] != 0.0 ? r2[k] / b2[k] : 0.0;
+  }
+  for (int q = 0; q < ns; q++) {
+    if (iters) iters[sel[q]] = its[q];
+    if (nupdates) nupdates[sel[q]] = nup[q];
+  }
   return 0;
 }
 

@@ -115,7 +115,7 @@ def wallSource(lo, t0, v, t_offset=0):
     return r
 
 
-def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0, sloppy=0):
+def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0, sloppy=0, deflate=None, nev=None):
     """The measurement of fpvaMeas.nim's main block (:80-138) on resident fields: for each colour ic, the point source src at
     (0,0,0,t0) and its three symmetric shifts are solved in ONE lock-step batch of four, the shifted propagators are shifted back at
     the sink, and the contractions of all three colours run on the device in one launch per table:
@@ -124,8 +124,11 @@ def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0, slopp
     lo is the rank-local Layout, t_offset its first global t.  Returns (cl, [cx, cy, cz], stats) with the raw (nt, 8) tables
     (printLocalMesons transforms and scales them) and stats = {"solve_s", "contract_s", "iterations", "updates"}.
     sloppy = 1 (or 2) runs the batches in mixed precision (Context.dev_solve_batch(..., sloppy=...): one rank only); "updates" then
-    holds the reliable updates per colour and system, and zeros for the fp64 batch."""
+    holds the reliable updates per colour and system, and zeros for the fp64 batch.  deflate = an EigBasis of the operator's even
+    sites: every batch is deflated from it with its leading nev vectors (None: deflate.nconv)."""
     import time
+
+    defl = {} if deflate is None and nev is None else {"deflate": deflate, "nev": nev}
 
     ctx = stag.ctx
     keep = []
@@ -147,9 +150,9 @@ def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0, slopp
             ctx.sync()
             t = time.perf_counter()
             if sloppy:
-                its, _, nup = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits, sloppy=sloppy)
+                its, _, nup = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits, sloppy=sloppy, **defl)
             else:
-                its, _ = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits)
+                its, _ = ctx.dev_solve_batch([dest[ic]] + dests, [src] + srcs, [mass] * 4, r2req, maxits, **defl)
                 nup = [0] * 4
             stats["solve_s"] += time.perf_counter() - t
             stats["iterations"].append(its)

@@ -51,7 +51,7 @@ _NOISE = {"Z4": "dev_z4_vector", "Z2": "dev_z2_vector", "U1": "dev_u1_vector", "
 
 
 def scalarTrace(stag, lo, rng, mass, r2req, maxits=100000, num_stoch=1, source_type="Z4", dilute_type="EO", improved_trace=True,
-                t_offset=0, sloppy=0, batch=4, out=print):
+                t_offset=0, sloppy=0, batch=4, out=print, deflate=None, nev=None):
     """scalarTrace.nim:146-218 on resident fields.  stag: the operator (its context holds the links); lo: the rank-local Layout and
     t_offset its first global t; rng: the rank's RngMilc6 RngField (seeded by global site, so every partition draws the same noise).
     For each of num_stoch noise sources of source_type (Z4, Z2, U1, Gauss) the source is diluted in time and dilute_type ("EO",
@@ -61,7 +61,8 @@ def scalarTrace(stag, lo, rng, mass, r2req, maxits=100000, num_stoch=1, source_t
     site order and est[t] = Re sum_{x in slice t} trce / spatial volume over the GLOBAL t; stats = {"solve_s", "contract_s",
     "noise_s", "log_s", "iterations", "updates"} (seconds in the batched solves; in dilution, accumulation, scaling and slice sums;
     in the noise fill; in the norms of the log lines; iterations and reliable updates per pattern and source).
-    sloppy = 1 (or 2) solves in mixed precision (one rank only).  out receives the reference's log lines (None: none, and the
+    sloppy = 1 (or 2) solves in mixed precision (one rank only).  deflate = an EigBasis of the operator's even sites: every batch is
+    deflated from it with its leading nev vectors (None: deflate.nconv), the odd-parity patterns included.  out receives the reference's log lines (None: none, and the
     norms they print are not computed)."""
     ctx = stag.ctx
     if list(lo.lat) != list(ctx.lat):
@@ -71,6 +72,7 @@ def scalarTrace(stag, lo, rng, mass, r2req, maxits=100000, num_stoch=1, source_t
     dk = dilute_type if isinstance(dilute_type, DilutionKind) else parseDilution(dilute_type)
     if source_type not in _NOISE:
         raise ValueError("Invalid noise type %s." % (source_type,))
+    defl = {} if deflate is None and nev is None else {"deflate": deflate, "nev": nev}
     batch = int(batch)
     if not 1 <= batch <= 4:
         raise ValueError("batch = %d, must be 1..4" % batch)
@@ -109,9 +111,9 @@ def scalarTrace(stag, lo, rng, mass, r2req, maxits=100000, num_stoch=1, source_t
                 ctx.sync()
                 t1 = time.perf_counter()
                 if sloppy:
-                    its, _, nup = ctx.dev_solve_batch(phi[:n], tmps[:n], [mass] * n, r2req, maxits, sloppy=sloppy)
+                    its, _, nup = ctx.dev_solve_batch(phi[:n], tmps[:n], [mass] * n, r2req, maxits, sloppy=sloppy, **defl)
                 else:
-                    its, _ = ctx.dev_solve_batch(phi[:n], tmps[:n], [mass] * n, r2req, maxits)
+                    its, _ = ctx.dev_solve_batch(phi[:n], tmps[:n], [mass] * n, r2req, maxits, **defl)
                     nup = [0] * n
                 t2 = time.perf_counter()
                 if improved_trace:

@@ -254,6 +254,20 @@ class Context:
                                                  int(maxits), int(sloppy), C.byref(its), C.byref(fin)))
         return its.value, fin.value
 
+    def dev_solve_xx_batch_deflated(self, basis, nev, x_ids, b_ids, masses, r2req, maxits, par_even=True, sloppy=SloppyNone):
+        """the deflated lock-step batch on resident fields (qexhip_dev_solve_xx_batch_deflated): n <= 4 solveEE / solveOO with their
+        own masses, both parities deflated from the even EigBasis with its leading nev vectors (None: basis.nconv); returns
+        (CG iterations, true |b - A x|^2/|b|^2, reliable updates) per system"""
+        n = len(x_ids)
+        nev = _deflate_args(basis, nev, n)
+        sloppy = _batch_sloppy(sloppy)
+        rq = [float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]
+        its, fin, nup = (C.c_int * n)(), (C.c_double * n)(), (C.c_int * n)()
+        check(lib().qexhip_dev_solve_xx_batch_deflated(self._h, int(basis.id), nev, n, (C.c_int * n)(*[int(v) for v in x_ids]),
+                                                       (C.c_int * n)(*[int(v) for v in b_ids]), (C.c_double * n)(*[float(v) for v in masses]),
+                                                       (C.c_double * n)(*rq), int(maxits), 1 if par_even else 0, sloppy, its, fin, nup))
+        return list(its), list(fin), list(nup)
+
     def dev_op_xx_sloppy(self, r_id, x_id, m2, par_even=True):
         """r[par] = 4 m2 x - (2D)(2D) x with the sloppy solve's fp32 links and sweep (x rounded to fp32, the result back to fp64)"""
         check(lib().qexhip_dev_op_xx_sloppy(self._h, int(r_id), int(x_id), float(m2), 1 if par_even else 0))
@@ -270,26 +284,35 @@ class Context:
     def dev_zero(self, fid, subset="all"):
         check(lib().qexhip_dev_zero(self._h, int(fid), _SUBSET[subset]))
 
-    def dev_solve_batch(self, x_ids, b_ids, masses, r2req, maxits=1000000, sloppy=None):
+    def dev_solve_batch(self, x_ids, b_ids, masses, r2req, maxits=1000000, sloppy=None, deflate=None, nev=None):
         """n x Staggered.solve on resident fields (lock-step batches of four); returns (iterations, r2) per system.
         sloppy = 0, 1 or 2 (SloppyNone / SloppySingle / SloppyHalf) chooses the precision of the batched CG explicitly
-        (qexhip_dev_solve_batch_sloppy; mixed precision on one rank only) and returns (iterations, r2, reliable updates)."""
+        (qexhip_dev_solve_batch_sloppy; mixed precision on one rank only) and returns (iterations, r2, reliable updates).
+        deflate = an EigBasis: the inner solveEE / solveOO batches are deflated from it with its leading nev vectors (None:
+        deflate.nconv; qexhip_dev_solve_batch_deflated); the return value is that of the same call without it."""
         n = len(x_ids)
         rq = [float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]
         its, fin = (C.c_int * n)(), (C.c_double * n)()
-        if sloppy is not None:
-            sloppy = _batch_sloppy(sloppy)
+        if deflate is not None or nev is not None:
+            nev = _deflate_args(deflate, nev, None)
+        if sloppy is not None or deflate is not None:
+            sl = 0 if sloppy is None else _batch_sloppy(sloppy)
             ms = [float(v) for v in masses]
             xi, bi = [int(v) for v in x_ids], [int(v) for v in b_ids]
             nup = []
             for k0 in range(0, n, 4):           # the entry takes one lock-step batch of at most four
                 k = min(4, n - k0)
                 i4, f4, u4 = (C.c_int * k)(), (C.c_double * k)(), (C.c_int * k)()
-                check(lib().qexhip_dev_solve_batch_sloppy(self._h, k, (C.c_int * k)(*xi[k0:k0 + k]), (C.c_int * k)(*bi[k0:k0 + k]),
-                                                          (C.c_double * k)(*ms[k0:k0 + k]), (C.c_double * k)(*rq[k0:k0 + k]),
-                                                          int(maxits), sloppy, i4, f4, u4))
+                a = ((C.c_int * k)(*xi[k0:k0 + k]), (C.c_int * k)(*bi[k0:k0 + k]), (C.c_double * k)(*ms[k0:k0 + k]),
+                     (C.c_double * k)(*rq[k0:k0 + k]), int(maxits), sl, i4, f4, u4)
+                if deflate is not None:
+                    check(lib().qexhip_dev_solve_batch_deflated(self._h, int(deflate.id), nev, k, *a))
+                else:
+                    check(lib().qexhip_dev_solve_batch_sloppy(self._h, k, *a))
                 its[k0:k0 + k], fin[k0:k0 + k] = list(i4), list(f4)
                 nup += list(u4)
+            if sloppy is None:
+                return list(its), list(fin)
             return list(its), list(fin), nup
         check(lib().qexhip_dev_solve_batch(self._h, n, (C.c_int * n)(*[int(v) for v in x_ids]), (C.c_int * n)(*[int(v) for v in b_ids]),
                                            (C.c_double * n)(*[float(v) for v in masses]), (C.c_double * n)(*rq), int(maxits), its, fin))
@@ -481,6 +504,25 @@ class EigBasis:
         buf = np.ascontiguousarray(np.stack([cf.real, cf.imag], axis=-1))
         check(lib().qexhip_eig_block_axpy(self.ctx._h, self.id, int(i0), len(cf), buf.ctypes.data, int(y_id)))
 
+    def block_dot_multi(self, i0, n, w_ids):
+        """[[<v_j, w_k.even> for j in i0 .. i0+n-1] for k] in one pass over the basis: complex array (nrhs, n), each number bit for
+        bit block_dot's for w_k alone"""
+        k = len(w_ids)
+        out = np.zeros((k, n, 2))
+        check(lib().qexhip_eig_block_dot_multi(self.ctx._h, self.id, int(i0), int(n), k, (C.c_int * max(k, 1))(*[int(v) for v in w_ids]),
+                                               out.ctypes.data))
+        return out[..., 0] + 1j * out[..., 1]
+
+    def block_axpy_multi(self, i0, coef, y_ids):
+        """y_k.even += sum_j coef[k][j] v_{i0+j} for the distinct resident fields y_ids, one pass over the basis"""
+        cf = np.atleast_2d(np.asarray(coef, dtype=np.complex128))
+        k = len(y_ids)
+        if cf.shape[0] != k:
+            raise ValueError("block_axpy_multi: one row of coefficients per field")
+        buf = np.ascontiguousarray(np.stack([cf.real, cf.imag], axis=-1))
+        check(lib().qexhip_eig_block_axpy_multi(self.ctx._h, self.id, int(i0), cf.shape[1], k, buf.ctypes.data,
+                                                (C.c_int * max(k, 1))(*[int(v) for v in y_ids])))
+
     def rotate(self, Q):
         """V[:, 0:k] <- V[:, 0:m] Q in place, Q real (m, k); vectors k .. m-1 are scratch afterwards"""
         Q = np.asarray(Q, dtype=np.float64)
@@ -649,8 +691,23 @@ class Staggered:
     def solveEE(self, r, x, m, sp, histcap=0, deflate=None, nev=None):
         self.solveXX(r, x, m, sp, True, histcap, deflate=deflate, nev=nev)
 
-    def solveOO(self, r, x, m, sp, histcap=0):
-        self.solveXX(r, x, m, sp, False, histcap)
+    def solveOO(self, r, x, m, sp, histcap=0, deflate=None, nev=None):
+        """deflate = an EigBasis (of the EVEN sites): the odd solve deflated from it, through the deflated batch with one system"""
+        if deflate is None and nev is None:
+            return self.solveXX(r, x, m, sp, False, histcap)
+        t0 = time.time()
+        its, fin, nup = self._batch("xx", [r], [x], [m], sp.r2req, sp.maxits, False, int(getattr(sp, "sloppySolve", SloppyNone)),
+                                    deflate=deflate, nev=nev)
+        sp.calls += 1
+        sp.iterations += its[0]
+        sp.iterationsMax = max(sp.iterationsMax, its[0])
+        sp.seconds += time.time() - t0
+        sp.flops += self._flops(its[0])
+        sp.reliableUpdates += nup[0]
+        sp.r2 = fin[0]
+        sp.r2hist = None
+        if sp.verbosity > 1:
+            print("solveOO(HIP): " + sp.getStats())
 
     def solve(self, x, b, m, sp, sloppy=None, deflate=None, nev=None):
         """Staggered.solve: x (array or list of arrays) <- D(m)^-1 b  (stagSolve.nim:224-294,347-446).
@@ -721,17 +778,30 @@ class Staggered:
         if sp.verbosity > 1:
             print("stagSolve(HIP): " + sp.getStats())
 
-    def _batch(self, fn_name, xs, bs, ms, r2req, maxits, parEven=None, sloppy=None):
+    def _batch(self, fn_name, xs, bs, ms, r2req, maxits, parEven=None, sloppy=None, deflate=None, nev=None):
         if sloppy is not None:
             sloppy = _batch_sloppy(sloppy)
         n = len(xs)
         if not (1 <= n <= 4 and len(bs) == n and len(ms) == n):
             raise ValueError("batch solve: 1..4 systems, one source and one mass each")
+        if deflate is not None or nev is not None:
+            nev = _deflate_args(deflate, nev, n)
         rq = [float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]
         xp = (C.c_void_p * n)(*[_p(a).value for a in xs])
         bp = (C.c_void_p * n)(*[_p(a).value for a in bs])
         mv, rv = (C.c_double * n)(*[float(v) for v in ms]), (C.c_double * n)(*rq)
         its, fin = (C.c_int * n)(), (C.c_double * n)()
+        if deflate is not None:
+            nup = (C.c_int * n)()
+            sl = 0 if sloppy is None else sloppy
+            if parEven is None:
+                check(lib().qexhip_stag_solve_batch_deflated(self.ctx._h, int(deflate.id), nev, n, xp, bp, mv, rv, int(maxits), sl, its, fin, nup))
+            else:
+                check(lib().qexhip_stag_solve_xx_batch_deflated(self.ctx._h, int(deflate.id), nev, n, xp, bp, mv, rv, int(maxits),
+                                                                1 if parEven else 0, sl, its, fin, nup))
+            if sloppy is None:
+                return list(its), list(fin)
+            return list(its), list(fin), list(nup)
         if sloppy is not None:
             nup = (C.c_int * n)()
             if parEven is None:
@@ -746,13 +816,14 @@ class Staggered:
             check(lib().qexhip_stag_solve_xx_batch(self.ctx._h, n, xp, bp, mv, rv, int(maxits), 1 if parEven else 0, its, fin))
         return list(its), list(fin)
 
-    def solve_batch(self, xs, bs, ms, sps, sloppy=None):
+    def solve_batch(self, xs, bs, ms, sps, sloppy=None, deflate=None, nev=None):
         """n (<= 4) x Staggered.solve on these links in lock-step: the links are streamed once per sweep for
         all systems.  sps: one SolverParams (shared r2req / maxits) or one per system; each gets the
         statistics of its own system, exactly as n calls of solve would record them.
         sloppy: None = fp64, and a SolverParams that asks for a sloppy solve is refused; 0, 1 or 2 (SloppyNone / SloppySingle /
         SloppyHalf) = the precision of the batched CG, chosen explicitly whatever sps say (mixed precision: one rank only; every
-        system comes out bit for bit as its own sloppy solve does; sp.reliableUpdates gets each system's updates)."""
+        system comes out bit for bit as its own sloppy solve does; sp.reliableUpdates gets each system's updates).
+        deflate = an EigBasis: the inner solveEE / solveOO batches are deflated from it (leading nev vectors; None: deflate.nconv)."""
         sl = [sps] * len(xs) if isinstance(sps, SolverParams) else list(sps)
         if sloppy is not None:
             sloppy = _batch_sloppy(sloppy)
@@ -763,9 +834,10 @@ class Staggered:
         t0 = time.time()
         nup = [0] * len(xs)
         if sloppy is None:
-            its, fin = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl))
+            its, fin = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl), deflate=deflate, nev=nev)
         else:
-            its, fin, nup = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl), sloppy=sloppy)
+            its, fin, nup = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl), sloppy=sloppy,
+                                        deflate=deflate, nev=nev)
         dt = (time.time() - t0) / len(xs)
         for sp, u in zip(sl, nup):
             sp.reliableUpdates += u
@@ -778,10 +850,12 @@ class Staggered:
             sp.r2 = f
         return its
 
-    def solveXX_batch(self, xs, bs, ms, r2req, maxits, parEven=True, sloppy=None):
+    def solveXX_batch(self, xs, bs, ms, r2req, maxits, parEven=True, sloppy=None, deflate=None, nev=None):
         """n (<= 4) x solveEE / solveOO in lock-step; returns (iterations, r2/b2) per system.  sloppy = 0, 1 or 2 chooses the
-        precision explicitly (as in solve_batch) and returns (fp32 iterations, true r2/b2, reliable updates) per system."""
-        return self._batch("xx", xs, bs, ms, r2req, maxits, parEven, sloppy)
+        precision explicitly (as in solve_batch) and returns (fp32 iterations, true r2/b2, reliable updates) per system.
+        deflate = an EigBasis of the even sites: BOTH parities are deflated from it with its leading nev vectors (None:
+        deflate.nconv); r2/b2 is then the true residual."""
+        return self._batch("xx", xs, bs, ms, r2req, maxits, parEven, sloppy, deflate=deflate, nev=nev)
 
     def solveXX_multi(self, xs, b, shifts, sp, parEven=True, histcap=0, sloppy=None):
         """Staggered.solveXX(xs, b, ms, sp, subset) (stagSolve.nim:296-345): shifts[0] = base mass.
@@ -819,6 +893,18 @@ class Staggered:
                                                int(sp.maxits), 1 if parEven else 0, C.byref(its), _p(hist), histcap))
         sp.iterations += its.value
         sp.r2hist = hist[: min(histcap, its.value + 1)] if histcap else None
+
+
+def _deflate_args(deflate, nev, n):
+    """the keywords deflate= / nev= of the batched solves, checked before any library call; returns nev (None -> deflate.nconv)"""
+    if not isinstance(deflate, EigBasis):
+        raise ValueError("deflate = %r: an EigBasis (Staggered.eigs); nev= needs deflate=" % (deflate,))
+    if n is not None and not 1 <= n <= 4:
+        raise ValueError("deflated batch: 1..4 systems (n = %d)" % n)
+    nev = int(deflate.nconv) if nev is None else nev
+    if isinstance(nev, bool) or not isinstance(nev, (int, np.integer)) or not 0 <= int(nev) <= deflate.nvecs:
+        raise ValueError("nev = %r: 0 .. %d (the vectors of the basis)" % (nev, deflate.nvecs))
+    return int(nev)
 
 
 def _batch_sloppy(sloppy):
