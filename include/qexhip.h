@@ -27,6 +27,7 @@
 #define QEXHIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -220,7 +221,14 @@ int qexhip_stag_solve_prev(qexhip_handle h, double *x, const double *b, double m
  *   sloppy = 1 (SloppySingle) CG iterations in fp32 (fp32 links and fields, fp32 Dslash sweeps, reductions in double), with
  *                             reliable updates: x, b and the true residual b - A x in fp64 whenever |r_s|^2 has fallen by
  *                             delta^2 = 0.01 since the last one, when the fp32 residual says converged, and at maxits
- *   sloppy = 2 (SloppyHalf)   runs single: there is no half-precision format
+ *   sloppy = 2 (SloppyHalf)   with option "half" = 0 (the default) runs single, bit for bit.  With "half" = 1 the single-system
+ *                             entries below, qexhip_dev_solve_xx_sloppy and the single-system deflated entries iterate on 16-bit
+ *                             storage: r_s, p_s, Ap_s as six int16 + one fp32 norm per site (qexhip_half_pack_host), the links
+ *                             as int16 (qexhip_stag_links_info_half), fp32 arithmetic, the increment of x in fp32, the same
+ *                             reliable updates and the same stop on the true fp64 residual.  If "half_stall" reliable updates in
+ *                             a row do not lower the true residual the solve finishes in fp32 (qexhip_stag_sloppy_last says so;
+ *                             iters and nupdates are then the sums).  Lock-step batches, multi-shift solves and t-sharded
+ *                             contexts (or ghost zones forced on one rank) run single for sloppy = 2 whatever the option says
  * The solve stops on the TRUE (fp64) residual: r2_over_b2 is |b - A x|^2/|b|^2 of the returned x (solveXX); iters counts fp32
  * iterations; nupdates (may be NULL) receives the number of reliable updates, the last one that confirmed convergence included
  * (0 for sloppy = 0).  iters == maxits is not an error.  QEXHIP_ERR_ARG for sloppy outside 0..2.
@@ -234,6 +242,16 @@ int qexhip_stag_solve_xx_sloppy(qexhip_handle h, double *x, const double *b, dou
                                 int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates);
 int qexhip_stag_solve_sloppy(qexhip_handle h, double *x, const double *b, double mass, double r2req, int maxits,
                              int use_prev, int sloppy, int *iters, double *r2_final, int *nupdates);
+/* What the last single-system sloppy solve (the two entries above, qexhip_dev_solve_xx_sloppy, the single-system deflated entries)
+ * ran: precision = 1 single, 2 16-bit storage (0: none yet); the iterations it spent on 16-bit storage and in fp32, summed over the
+ * inner solves of a full solve (half_iters + f32_iters = iters); fell_back = 1 if the stall guard of a 16-bit solve handed over
+ * to fp32.  Any pointer may be NULL. */
+int qexhip_stag_sloppy_last(qexhip_handle h, int *precision, int *half_iters, int *f32_iters, int *fell_back);
+/* The 16-bit vector format on the host, for nsites sites of 6 doubles (re, im of three colours): norm[i] = fp32 of the largest
+ * |component| of site i, q[6 i + k] = rint(v 32767 / norm[i]) formed in double; a site whose norm is below the smallest normal
+ * fp32 number is all zeros.  unpack: v = q norm / 32767.  Needs no device.  QEXHIP_ERR_ARG for a site that is not finite in fp32. */
+int qexhip_half_pack_host(const double *v, size_t nsites, int16_t *q, float *norm);
+int qexhip_half_unpack_host(const int16_t *q, const float *norm, size_t nsites, double *v);
 
 /* multi-shift solveXX (src/physics/stagSolve.nim:296-345 + src/solvers/cgm.nim:84-315).
  * shifts[0] = base mass, shifts[k>0] = sigma_k added to the base operator 4 m0^2 - (2D)(2D) (i.e. shift k is that operator at
@@ -307,6 +325,14 @@ int qexhip_dev_op_xx_sloppy(qexhip_handle h, int r_id, int x_id, double m2, int 
  * the largest deviation of a stored row 2 from the sign-format rebuild (0 when the sign format is capped off by "recon" = 0); t-sharded:
  * the maximum over the ranks, and collective when the copy is rebuilt */
 int qexhip_stag_links_info_f32(qexhip_handle h, int *format, double *max_dev);
+/* the 16-bit counterpart of qexhip_dev_op_xx_sloppy: x[par] rounded to the 16-bit vector format, the two 16-bit sweeps (their
+ * intermediate and result stored in the format), the result back in fp64.  One rank without ghost zones */
+int qexhip_dev_op_xx_half(qexhip_handle h, int r_id, int x_id, double m2, int par_even);
+/* the 16-bit link copy (building it if stale, behind the fp32 copy whose format decision it shares): format 1 = rows 0,1 as int16
+ * of u 32767 (clamped) + the fp32 copy's sign masks, 48 B per forward/backward pair; format 0 = 18 reals as int16 of u 32767 / s,
+ * 72 B per pair, s = *s_fat for the one-hop links and *s_long for the Naik links: the largest |entry| of each kind (reported in
+ * either format; 0 without Naik links).  max_dev as qexhip_stag_links_info_f32 */
+int qexhip_stag_links_info_half(qexhip_handle h, int *format, double *s_fat, double *s_long, double *max_dev);
 /* Re-entry of the CG on the state the last qexhip_dev_solve_xx (or re-entry) on x_id left behind -- CgState.solve called
  * again with b2 >= 0 (src/solvers/cg.nim:21-27,85,133,155-161,256-261): no set-up, r / p / rzold kept, the stopping
  * criterion comes from the new r2req / maxits, `iters` goes on counting from where the last call stopped (maxits is the
@@ -651,6 +677,10 @@ int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped
  *                  (qexhip_stag_links_storage) if at most 1 % of their links escape it; 0: 18 reals.  Effective at the next set_links
  *   "sloppy_check" the sloppy solves post their (device-gated) reliable-update launches every this many fp32 iterations, and
  *                  at maxits (default 4; 1: in the iteration that calls for an update)
+ *   "half"         1: sloppy = 2 (SloppyHalf) iterates on 16-bit storage in the single-system solves of a one-rank context;
+ *                  0 (default): it runs single.  Other values are refused
+ *   "half_stall"   successive reliable updates of a 16-bit solve that may fail to lower the true residual before the solve
+ *                  finishes in fp32 (default 2; 0: hand over at the first update, a test hook)
  *   "stout_check"  inverse iterations of qexhip_stout_inverse posted between two read-backs of its device-side loop state
  *                  (default 8); the result does not depend on it
  *   "overlap"      face exchange on the second stream beside the interior sweep: 0 never, 1 always, -1 (default) measured at

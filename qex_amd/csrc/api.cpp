@@ -195,6 +195,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   comm_destroy(c);
   if (c->W) (void)hipFree(c->W);
   f32_state_free(c);
+  half_state_free(c);
   if (c->outer_F) (void)hipFree(c->outer_F);
   if (c->obs_table) (void)hipFree(c->obs_table);
   if (c->tile_order) (void)hipFree(c->tile_order);
@@ -446,6 +447,16 @@ static int sloppy_check(qexhip_ctx *c, int sloppy) {
   }
   return 0;
 }
+// the single-system sloppy entries start a new report for qexhip_stag_sloppy_last
+static void sloppy_last_reset(qexhip_ctx *c) { c->slp_last.precision = 0; c->slp_last.half_iters = 0; c->slp_last.f32_iters = 0; c->slp_last.fell_back = 0; }
+extern "C" int qexhip_stag_sloppy_last(qexhip_handle c, int *precision, int *half_iters, int *f32_iters, int *fell_back) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (precision) *precision = c->slp_last.precision;
+  if (half_iters) *half_iters = c->slp_last.half_iters;
+  if (f32_iters) *f32_iters = c->slp_last.f32_iters;
+  if (fell_back) *fell_back = c->slp_last.fell_back;
+  return 0;
+}
 
 extern "C" int qexhip_stag_solve_xx_sloppy(qexhip_handle c, double *x, const double *b, double mass, double r2req, int maxits,
                                            int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates) {
@@ -457,7 +468,8 @@ extern "C" int qexhip_stag_solve_xx_sloppy(qexhip_handle c, double *x, const dou
   DevField *fb, *fx;
   CHK(host_in(c, WK_IN, b, &fb));
   CHK(get_work(c, WK_OUT, &fx));
-  CHK(solve_xx_sloppy_dev(c, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates));
+  sloppy_last_reset(c);
+  CHK(solve_xx_sloppy_any(c, sloppy, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates));
   return field_download(c, *fx, x);
 }
 
@@ -472,6 +484,7 @@ extern "C" int qexhip_stag_solve_sloppy(qexhip_handle c, double *x, const double
   CHK(host_in(c, WK_IN, b, &fb));
   if (use_prev) CHK(host_in(c, WK_OUT, x, &fx));
   else CHK(get_work(c, WK_OUT, &fx));
+  sloppy_last_reset(c);
   CHK(solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, use_prev, sloppy, nupdates));
   return field_download(c, *fx, x);
 }
@@ -671,7 +684,8 @@ extern "C" int qexhip_dev_solve_xx_sloppy(qexhip_handle c, int x_id, int b_id, d
   CHK(find_field(c, x_id, &fx));
   CHK(find_field(c, b_id, &fb));
   if (x_id == b_id) { qexhip_set_error("dev_solve_xx_sloppy: the solution field is the source field"); return QEXHIP_ERR_ARG; }
-  return solve_xx_sloppy_dev(c, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
+  sloppy_last_reset(c);
+  return solve_xx_sloppy_any(c, sloppy, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
 }
 extern "C" int qexhip_dev_op_xx_sloppy(qexhip_handle c, int r_id, int x_id, double m2, int par_even) {
   if (!c) return QEXHIP_ERR_ARG;
@@ -687,6 +701,29 @@ extern "C" int qexhip_dev_op_xx_sloppy(qexhip_handle c, int r_id, int x_id, doub
   CHK(f32_from_f64(c, *xi, *fx, px, 1.0));
   CHK(f32_op_xx(c, *ro, *xi, m2, par_even, 0, nullptr, nullptr));
   return f32_to_f64(c, *fr, *ro, px, 1.0, 0);
+}
+// the 16-bit counterpart of qexhip_dev_op_xx_sloppy: x rounded to the 16-bit format, two 16-bit sweeps, the result back in fp64
+extern "C" int qexhip_dev_op_xx_half(qexhip_handle c, int r_id, int x_id, double m2, int par_even) {
+  if (!c) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fr, *fx;
+  CHK(find_field(c, r_id, &fr));
+  CHK(find_field(c, x_id, &fx));
+  return half_op_xx_probe(c, *fr, *fx, m2, par_even);
+}
+extern "C" int qexhip_stag_links_info_half(qexhip_handle c, int *format, double *s_fat, double *s_long, double *max_dev) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (c->nranks > 1 || c->g.halo) { qexhip_set_error("the 16-bit links exist on one rank without ghost zones"); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  return half_links(c, format, s_fat, s_long, max_dev);
+}
+extern "C" int qexhip_half_pack_host(const double *v, size_t nsites, int16_t *q, float *norm) {
+  if (!v || !q || !norm) return QEXHIP_ERR_ARG;
+  return half_pack_host(v, nsites, q, norm);
+}
+extern "C" int qexhip_half_unpack_host(const int16_t *q, const float *norm, size_t nsites, double *v) {
+  if (!v || !q || !norm) return QEXHIP_ERR_ARG;
+  return half_unpack_host(q, norm, nsites, v);
 }
 extern "C" int qexhip_stag_links_info_f32(qexhip_handle c, int *format, double *max_dev) {
   if (!c) return QEXHIP_ERR_ARG;
@@ -761,6 +798,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   }
   gauge_release_scratch(c);
   f32_state_free(c);                 // the mixed-precision CG's fp32 links and fields: rebuilt by the next sloppy solve
+  half_state_free(c);                // and its 16-bit links and fields
   msf_state_free(c);                 // and the mixed multi-shift CG's fp32 search directions / increments
   batch_f32_state_free(c);           // and the batched form's fp32 fields
   gfix_state_free(c);                // and the gauge-fixing transform with its polish scratch (qexhip_gfix_set_transform re-creates it)
@@ -907,7 +945,8 @@ extern "C" int qexhip_dev_solve_xx_deflated(qexhip_handle c, int basis, int nev,
   CHK(find_field(c, b_id, &fb));
   if (x_id == b_id) { qexhip_set_error("dev_solve_xx_deflated: the solution field is the source field"); return QEXHIP_ERR_ARG; }
   HIPCHK(hipSetDevice(c->device));
-  return solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2_over_b2);
+  sloppy_last_reset(c);
+  return solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy, iters, r2_over_b2);
 }
 extern "C" int qexhip_stag_solve_xx_deflated(qexhip_handle c, int basis, int nev, double *x, const double *b, double mass, double r2req,
                                              int maxits, int sloppy, int *iters, double *r2_over_b2) {
@@ -918,7 +957,8 @@ extern "C" int qexhip_stag_solve_xx_deflated(qexhip_handle c, int basis, int nev
   DevField *fb, *fx;
   CHK(host_in(c, WK_IN, b, &fb));
   CHK(get_work(c, WK_OUT, &fx));
-  CHK(solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2_over_b2));
+  sloppy_last_reset(c);
+  CHK(solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy, iters, r2_over_b2));
   return field_download(c, *fx, x);
 }
 extern "C" int qexhip_stag_solve_deflated(qexhip_handle c, int basis, int nev, double *x, const double *b, double mass, double r2req,
@@ -932,7 +972,8 @@ extern "C" int qexhip_stag_solve_deflated(qexhip_handle c, int basis, int nev, d
   CHK(host_in(c, WK_IN, b, &fb));
   CHK(get_work(c, WK_OUT, &fx));
   c->deflate_basis = basis; c->deflate_nev = nev;
-  const int rc = solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, 0, sloppy ? 1 : 0, nullptr);
+  sloppy_last_reset(c);
+  const int rc = solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, 0, sloppy, nullptr);
   c->deflate_basis = 0; c->deflate_nev = 0;
   CHK(rc);
   return field_download(c, *fx, x);
@@ -1147,6 +1188,14 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
   else if (n == "sloppy_check") {
     if (value < 1) { qexhip_set_error("option sloppy_check: >= 1 fp32 iterations"); return QEXHIP_ERR_ARG; }
     c->opt_sloppy_check = value;
+  }
+  else if (n == "half") {
+    if (value != 0 && value != 1) { qexhip_set_error("option half: 0 (SloppyHalf runs single) or 1 (16-bit storage)"); return QEXHIP_ERR_ARG; }
+    c->opt_half = value;
+  }
+  else if (n == "half_stall") {
+    if (value < 0) { qexhip_set_error("option half_stall: >= 0 failed reliable updates"); return QEXHIP_ERR_ARG; }
+    c->opt_half_stall = value;
   }
   else if (n == "gfix_check") {
     if (value < 1) { qexhip_set_error("option gfix_check: >= 1 relax iterations"); return QEXHIP_ERR_ARG; }

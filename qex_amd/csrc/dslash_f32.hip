@@ -570,6 +570,12 @@ int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const De
   HIPCHK(hipGetLastError());
   return 0;
 }
+// the close of an iteration whose update kernel is another file's (dslash_half.hip): one rank, nparts |r_s|^2 partials in r2p
+int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts) {
+  k_slp_close<<<1, 256, 0, c->stream>>>(s, r2p, nparts, SLP_DELTA * SLP_DELTA);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity) {
   const size_t n = body2(c);
   k_slp_flush<<<grid_for(n), 256, 0, c->stream>>>(x.par(parity), xs.par(parity), n, s);

@@ -239,6 +239,10 @@ struct qexhip_ctx {
   void *stout = nullptr;                             // StoutState (stout.hip): the stout chain's levels, backward scratch, inverse loop state
   int md_src1_stout = 0;                             // MD force source 1 is the stout chain's force (the closure that wrote last), else the nHYP closure's
   int opt_stout_check = 8;                           // option "stout_check": inverse iterations posted between two read-backs of the loop state
+  void *half = nullptr;                              // HalfState (dslash_half.hip): 16-bit links + fields + stall guard of the SloppyHalf CG
+  int opt_half = 0;                                  // option "half": 1 = sloppy = 2 runs the 16-bit path (single-system solves on one rank)
+  int opt_half_stall = 2;                            // option "half_stall": failed reliable updates in a row before the 16-bit solve finishes in fp32
+  struct { int precision = 0, half_iters = 0, f32_iters = 0, fell_back = 0; } slp_last;   // the last sloppy solve (qexhip_stag_sloppy_last)
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -392,6 +396,19 @@ int slp_xpay(qexhip_ctx *c, SlpScal *s, DevFieldF &p, DevFieldF &rs, const DevFi
 int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const DevFieldF &p, const DevFieldF &Ap, int parity, int ndot);
 int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity);
 int slp_resid(qexhip_ctx *c, SlpScal *s, DevField &r, const DevField &b, const DevField &Ax, int parity);
+int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts);     // k_slp_close alone (one rank)
+
+// ---- dslash_half.hip (16-bit storage for the sloppy CG: one rank, no ghost zones, one system) ----
+enum { HALF_T = 0, HALF_R, HALF_P, HALF_AP, HALF_IN, HALF_NF };   // 16-bit work fields
+int half_pack_host(const double *v, size_t nsites, int16_t *q, float *norm);       // the vector format on the host
+int half_unpack_host(const int16_t *q, const float *norm, size_t nsites, double *v);
+int half_links(qexhip_ctx *c, int *fmt, double *s_fat, double *s_long, double *dev);   // the 16-bit copy of the links, rebuilt when links_gen moved
+int half_op_xx_probe(qexhip_ctx *c, DevField &fr, const DevField &fx, double m2, int par_even);
+int slph_begin(qexhip_ctx *c, SlpScal *s);               // links + the stall guard's state, behind slp_init
+int slph_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, const DevField &r, double m2, int par_even);   // one 16-bit iteration
+int slph_stall(qexhip_ctx *c, SlpScal *s, int limit);    // behind a gated reliable update: the stall guard
+int slph_stalled(qexhip_ctx *c, int *stalled);           // (stream synchronised)
+void half_state_free(qexhip_ctx *c);
 
 // ---- multishift_f32.hip: the fp32 iteration of the mixed-precision multi-shift CG ----
 #define CGM_MAXM 32                                      // shifts per multi-shift solve (fp64 and mixed)
@@ -435,6 +452,12 @@ int solve_xx_continue_dev(qexhip_ctx *c, DevField &x, double r2req, int maxits, 
 int solve_full_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits,
                    int *iters, double *r2_final, int use_prev = 0, int sloppy = 0, int *nupdates = nullptr);
 int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                        int *iters, double *r2_over_b2, int *nupdates);
+// the 16-bit solve (option "half"), and the single-system sloppy solve of either storage: sloppy = 2 takes the 16-bit one where
+// the option is set and the context is one rank without ghost zones.  Both add what they ran to c->slp_last.
+int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                      int *iters, double *r2_over_b2, int *nupdates);
+int solve_xx_sloppy_any(qexhip_ctx *c, int sloppy, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                         int *iters, double *r2_over_b2, int *nupdates);
 int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts,
                        int nmass, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);

@@ -261,6 +261,94 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
   return 0;
 }
 
+// ---- SloppyHalf with option "half": the same loop on 16-bit vectors and links (dslash_half.hip) ----
+// r_s, p_s, Ap_s are stored in the 16-bit format, the increment x_s stays fp32; the update gating, the chunks and the stop on the
+// true fp64 residual are solve_xx_sloppy_dev's, and its fp64 kernels (slp_flush, op_xx, slp_resid) run unchanged.  Stall guard: at a
+// light mass cond(A) 2^-15 reaches 1 and the 16-bit recursion can stop improving the true residual; when opt_half_stall reliable
+// updates in a row have not lowered it (0: at the first update) the device ends the 16-bit iteration and the solve finishes in
+// fp32 -- A e = r with solve_xx_sloppy_dev to r2req |b|^2 / |r|^2, x += e, and the true residual recomputed once.  iters and
+// nupdates are the sums.  One rank without ghost zones (solve_xx_sloppy_any sends everything else to the fp32 solve).
+int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                      int *iters, double *r2_over_b2, int *nupdates) {
+  const int par = par_even ? 0 : 1;
+  if (c->nranks > 1 || c->g.halo) { qexhip_set_error("16-bit sloppy solve: one rank without ghost zones only"); return -1; }
+  const double m2 = mass * mass;
+  if (m2 == 0.0) { qexhip_set_error("sloppy solve: mass 0 unsupported (op_xx's <p,Ap> needs 4 m^2 > 0)"); return -1; }
+  DevField *r, *Ax;
+  CHK(get_work(c, WK_R, &r));
+  CHK(get_work(c, WK_AP, &Ax));
+  DevFieldF *xs;
+  CHK(f32_field(c, F32_X, &xs));
+  SlpScal *s;
+  CHK(slp_alloc(c, &s));
+  CHK(blas_zero(c, x, 2));                       // (as solve_xx_dev)
+  CHK(blas_norm2(c, b, par, &c->dscal[0]));
+  CHK(blas_copy(c, *r, b, par));
+  HIPCHK(hipMemsetAsync(xs->par(par), 0, xs->half * sizeof(float2), c->stream));
+  CHK(slp_init(c, s, r2req, maxits));
+  CHK(slph_begin(c, s));
+  SlpScal h;
+  HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  memcpy(&h, c->pinned, sizeof(SlpScal));
+  const int every = std::max(1, c->opt_sloppy_check);
+  const int chunk = 32;
+  int k = 0;
+  while (!h.done && k < maxits) {
+    const int n = std::min(chunk, maxits - k);
+    for (int i = 0; i < n; i++, k++) {
+      CHK(slph_iterate(c, s, *xs, *r, m2, par_even));
+      if ((k + 1) % every == 0 || k + 1 >= maxits) {
+        CHK(slp_flush(c, s, x, *xs, par));
+        CHK(op_xx(c, *Ax, x, m2, par_even, 0, &s->noupd));
+        CHK(slp_resid(c, s, *r, b, *Ax, par));
+        CHK(slph_stall(c, s, c->opt_half_stall));
+      }
+    }
+    HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(&h, c->pinned, sizeof(SlpScal));
+  }
+  int its = h.k, nupd = h.nupd, stalled = 0, its32 = 0;
+  double r2t = h.r2t;
+  CHK(slph_stalled(c, &stalled));
+  if (stalled && r2t > h.r2stop && its < maxits) {
+    // (x holds every increment: the update that tripped the guard flushed x_s; r is its true residual)
+    DevField *e, *rc;
+    CHK(pool_field(c, POOL_REF, &e));
+    CHK(pool_field(c, POOL_REF + 4, &rc));
+    CHK(blas_copy(c, *rc, *r, par));
+    int nu32 = 0;
+    CHK(solve_xx_sloppy_dev(c, *e, *rc, mass, h.r2stop / r2t, maxits - its, par_even, &its32, nullptr, &nu32));
+    CHK(blas_axpy(c, 1.0, *e, x, par));
+    CHK(op_xx(c, *Ax, x, m2, par_even, 0, nullptr));
+    CHK(blas_axpby(c, 1.0, b, -1.0, *Ax, *rc, par));
+    CHK(blas_norm2(c, *rc, par, &c->dscal[1]));
+    CHK(read_scalars(c, &c->dscal[1], 1, &r2t));
+    nupd += nu32;
+    c->slp_last.fell_back = 1;
+  }
+  c->slp_last.precision = 2;
+  c->slp_last.half_iters += its;
+  c->slp_last.f32_iters += its32;
+  if (iters) *iters = its + its32;
+  if (r2_over_b2) *r2_over_b2 = (h.b2 != 0.0) ? r2t / h.b2 : 0.0;
+  if (nupdates) *nupdates = nupd;
+  return 0;
+}
+
+int solve_xx_sloppy_any(qexhip_ctx *c, int sloppy, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                        int *iters, double *r2_over_b2, int *nupdates) {
+  if (sloppy == 2 && c->opt_half && c->nranks == 1 && !c->g.halo)
+    return solve_xx_half_dev(c, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
+  int its = 0;
+  CHK(solve_xx_sloppy_dev(c, x, b, mass, r2req, maxits, par_even, &its, r2_over_b2, nupdates));
+  if (c->slp_last.precision == 0) c->slp_last.precision = 1;
+  c->slp_last.f32_iters += its;
+  if (iters) *iters = its;
+  return 0;
+}
+
 // ---- mixed-precision multi-shift solveXX (QUDA's scheme: fp32 multi-shift iterations, then per-shift refinement) ----
 // Phase 1: the multi-shift CG of solve_xx_multi_dev with every iterated vector in fp32 (multishift_f32.hip) and reliable updates on the
 // BASE system: gated on device flags and posted every opt_sloppy_check-th iteration and at maxits like the single solve's; one launch
@@ -406,7 +494,7 @@ int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevF
   }
   if (nev == 0) {
     if (!sloppy) return solve_xx_dev(c, x, b, mass, r2req, maxits, 1, iters, r2_over_b2, nullptr, 0);
-    return solve_xx_sloppy_dev(c, x, b, mass, r2req, maxits, 1, iters, r2_over_b2, nullptr);
+    return solve_xx_sloppy_any(c, sloppy, x, b, mass, r2req, maxits, 1, iters, r2_over_b2, nullptr);
   }
   const double m2 = mass * mass;
   CHK(eig_rayleigh(c, B, nev));
@@ -439,7 +527,7 @@ int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevF
   if (b2 > 0 && n[1] > r2req * b2) {
     const double rq = r2req * b2 / n[1];
     if (!sloppy) CHK(solve_xx_dev(c, *d, *r0, mass, rq, maxits, 1, &its, nullptr, nullptr, 0));
-    else CHK(solve_xx_sloppy_dev(c, *d, *r0, mass, rq, maxits, 1, &its, nullptr, nullptr));
+    else CHK(solve_xx_sloppy_any(c, sloppy, *d, *r0, mass, rq, maxits, 1, &its, nullptr, nullptr));
     CHK(blas_axpy(c, 1.0, *d, x, 0));
     CHK(op_xx(c, *Ax, x, m2, 1, 0, nullptr));
     CHK(blas_axpby(c, 1.0, b, -1.0, *Ax, *r0, 0));
@@ -559,11 +647,11 @@ static int inner_xx(qexhip_ctx *c, DevField &x, DevField &b, double m, double r2
   if (par_even && c->deflate_nev > 0) {
     EigBasis *B;
     CHK(eig_basis_find(c, c->deflate_basis, &B));
-    return solve_xx_deflated_dev(c, *B, c->deflate_nev, x, b, m, r2req, maxits, sloppy ? 1 : 0, its, nullptr);
+    return solve_xx_deflated_dev(c, *B, c->deflate_nev, x, b, m, r2req, maxits, sloppy, its, nullptr);
   }
   if (!sloppy) return solve_xx_dev(c, x, b, m, r2req, maxits, par_even, its, nullptr, nullptr, 0);
   int nu = 0;
-  CHK(solve_xx_sloppy_dev(c, x, b, m, r2req, maxits, par_even, its, nullptr, &nu));
+  CHK(solve_xx_sloppy_any(c, sloppy, x, b, m, r2req, maxits, par_even, its, nullptr, &nu));
   *nupd += nu;
   return 0;
 }

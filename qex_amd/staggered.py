@@ -22,7 +22,8 @@ from . import _lib
 from ._lib import check, lib
 
 EVEN, ODD, ALL = 0, 1, 2
-# SolverParams.sloppySolve (solverBase.nim:8-15): SloppyHalf runs single precision -- there is no half-precision format
+# SolverParams.sloppySolve (solverBase.nim:8-15): SloppyHalf runs single precision unless the context's option "half" is 1, which
+# gives the single-system solves of a one-rank context 16-bit storage (Context.set_option("half", 1); half_pack_host is the format)
 SloppyNone, SloppySingle, SloppyHalf = 0, 1, 2
 _SUBSET = {"even": EVEN, "odd": ODD, "all": ALL}
 
@@ -277,6 +278,25 @@ class Context:
         f, dev = C.c_int(0), C.c_double(0)
         check(lib().qexhip_stag_links_info_f32(self._h, C.byref(f), C.byref(dev)))
         return f.value, dev.value
+
+    def dev_op_xx_half(self, r_id, x_id, m2, par_even=True):
+        """r[par] = 4 m2 x - (2D)(2D) x with the 16-bit links, vectors and sweep of SloppyHalf under option "half" = 1 (x rounded to
+        the 16-bit format, the intermediate and the result stored in it, the result back to fp64)"""
+        check(lib().qexhip_dev_op_xx_half(self._h, int(r_id), int(x_id), float(m2), 1 if par_even else 0))
+
+    def links_info_half(self):
+        """(format, s_fat, s_long, max deviation) of the 16-bit link copy: format 0 = 18 reals scaled by the largest |entry| of the
+        link kind (s_fat, s_long), 1 = rows 0,1 + the fp32 copy's sign masks (scale 1)"""
+        f, sf, sl, dev = C.c_int(0), C.c_double(0), C.c_double(0), C.c_double(0)
+        check(lib().qexhip_stag_links_info_half(self._h, C.byref(f), C.byref(sf), C.byref(sl), C.byref(dev)))
+        return f.value, sf.value, sl.value, dev.value
+
+    def sloppy_last(self):
+        """what the last single-system sloppy solve ran (qexhip_stag_sloppy_last): dict with precision (1 single, 2 16-bit storage),
+        half_iters, f32_iters and fell_back (the 16-bit solve's stall guard handed over to fp32)"""
+        v = [C.c_int(0) for _ in range(4)]
+        check(lib().qexhip_stag_sloppy_last(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("precision", "half_iters", "f32_iters", "fell_back"), (x.value for x in v)))
 
     def release_workspace(self):
         check(lib().qexhip_release_workspace(self._h))
@@ -934,6 +954,33 @@ def link_residual_host(links):
     row2 = np.zeros((n, 3, 2), dtype=np.float64)
     check(lib().qexhip_link_residual_host(a.ctypes.data, n, esc.ctypes.data, row2.ctypes.data))
     return esc.astype(bool), row2
+
+
+def half_pack_host(v):
+    """The 16-bit vector format of the SloppyHalf solves on the host (no device needed).  v: (..., 3, 2) real or (..., 3) complex
+    sites.  Returns (q: int16 (n, 6), norm: float32 (n,)): norm = the site's largest |component|, q = rint(v 32767 / norm)."""
+    a = np.asarray(v)
+    if np.iscomplexobj(a):
+        a = np.stack([a.real, a.imag], axis=-1)
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 6)
+    n = a.shape[0]
+    q = np.zeros((n, 6), dtype=np.int16)
+    norm = np.zeros(n, dtype=np.float32)
+    check(lib().qexhip_half_pack_host(a.ctypes.data_as(C.POINTER(C.c_double)), n, q.ctypes.data_as(C.POINTER(C.c_int16)),
+                                      norm.ctypes.data_as(C.POINTER(C.c_float))))
+    return q, norm
+
+
+def half_unpack_host(q, norm):
+    """the sites (n, 3, 2) that half_pack_host's (q, norm) stand for: q norm / 32767"""
+    q = np.ascontiguousarray(q, dtype=np.int16).reshape(-1, 6)
+    norm = np.ascontiguousarray(norm, dtype=np.float32).reshape(-1)
+    if norm.shape[0] != q.shape[0]:
+        raise ValueError("half_unpack_host: one norm per site")
+    v = np.zeros((q.shape[0], 3, 2), dtype=np.float64)
+    check(lib().qexhip_half_unpack_host(q.ctypes.data_as(C.POINTER(C.c_int16)), norm.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0],
+                                        v.ctypes.data_as(C.POINTER(C.c_double))))
+    return v
 
 
 # ---- gauge observables / Wilson flow (src/gauge/gaugeUtils.nim:213-282, src/gauge/wflow.nim:21-67) ----
