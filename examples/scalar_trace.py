@@ -2,7 +2,7 @@
 """src/observables/scalarTrace.nim through libqexhip: the stochastic scalar-density trace Tr (D+m)^-1(x,x) (disconnected pbp) from
 noise sources diluted in time and even/odd or the eight 3-d corners.
 
-    python examples/scalar_trace.py [-inlat FILE | -lat 4 4 4 8] [-outfn output] [-mass 0.1] [-sloppy 0] [-cg_prec 1e-9]
+    python examples/scalar_trace.py [-inlat FILE | -lat 4 4 4 8] [-outfn output] [-mass 0.1] [-sloppy 0] [-half 0] [-cg_prec 1e-9]
                                     [-cg_max 100000] [-num_stoch 1] [-improved_trace 1] [-source_type Z4] [-dilute_type EO]
                                     [-seed N] [-smear 0] [-batch 4] [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3]
     python -m torch.distributed.run --nproc-per-node N examples/scalar_trace.py ...     # t-sharded over N ranks
@@ -11,7 +11,8 @@ The parameters are the reference program's.  Without -inlat the configuration is
 streams then go on into the noise, as there; -smear 1 builds the operator on nHYP(0.4, 0.5, 0.5) links (the reference always
 smears).  The noise is drawn, diluted, solved in lock-step batches of -batch patterns and contracted on the device
 (qex_amd.scalarTrace); each trace is written as one SciDAC record of 16-byte sites, read back, and its per-timeslice sums are
-printed once more, as `loadsrc` lines.  -sloppy 1 or 2 solves in mixed precision: one rank only.  -nev N computes the N lowest
+printed once more, as `loadsrc` lines.  -sloppy 1 or 2 solves in mixed precision: one rank only; -half 1 lets -sloppy 2 iterate on
+16-bit storage (the context options "half" and "half_batch"; default 0: it runs single).  -nev N computes the N lowest
 eigenpairs of the even/odd operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every
 batch with them, the odd-parity patterns included; the first source is then also solved without deflation and the eigensolve
 time and the iterations with / without deflation are printed."""
@@ -35,6 +36,7 @@ ap.add_argument("-lat", type=int, nargs=4, default=[4, 4, 4, 8])
 ap.add_argument("-outfn", default="output")
 ap.add_argument("-mass", type=float, default=0.1)
 ap.add_argument("-sloppy", type=int, default=0, choices=[0, 1, 2])
+ap.add_argument("-half", type=int, default=0, choices=[0, 1], help="1: -sloppy 2 iterates on 16-bit storage (options half, half_batch)")
 ap.add_argument("-cg_prec", type=float, default=1e-9)
 ap.add_argument("-cg_max", type=int, default=100000)
 ap.add_argument("-num_stoch", type=int, default=1)
@@ -77,6 +79,9 @@ if world > 1:
     rng = q.RngField(lat, q.RngMilc6, a.seed, glat=glat, t_offset=rank * lt)
 else:
     ctx = q.Context(lat)
+    if a.half:
+        ctx.set_option("half", 1)
+        ctx.set_option("half_batch", 1)
     rng = q.RngField(lat, q.RngMilc6, a.seed)
 if rank != 0:
     sys.stdout = open(os.devnull, "w")            # one log, rank 0's

@@ -2,7 +2,7 @@
 """src/observables/fpvaMeas.nim through libqexhip: local and one-link (symmetric spatial shift) staggered meson correlators
 from point-source propagators.
 
-    python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5] [-sloppy 0]
+    python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5] [-sloppy 0] [-half 0]
                                    [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3]
     python -m torch.distributed.run --nproc-per-node N examples/stag_mesons.py ...     # t-sharded over N ranks
 
@@ -11,7 +11,8 @@ For each colour the point source at (0,0,0,t0) and its three symmetric one-link 
 no propagator leaves the GPU.  The tables are printed as printLocalMesons prints them: Walsh-Hadamard transform over the corner
 bits, normalisation nt / physVol.  The configuration is the library's RngMilc6 warm start (as examples/stag_prop.py), seeded by
 global site, so every partition sees the same gauge field.  -sloppy 1 runs the batches in mixed precision (fp32 iterations with
-fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only.  -nev N computes the N lowest eigenpairs of the even/odd
+fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only; -half 1 lets
+-sloppy 2 iterate on 16-bit storage (the context options "half" and "half_batch"; default 0: it runs single).  -nev N computes the N lowest eigenpairs of the even/odd
 operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every batch with them; the
 measurement is then also run without deflation and the eigensolve time and the iterations with / without are printed."""
 import argparse
@@ -32,6 +33,7 @@ ap.add_argument("-seed", type=int, default=987654321)
 ap.add_argument("-warm", type=float, default=0.5)
 ap.add_argument("-r2req", type=float, default=1e-16)
 ap.add_argument("-sloppy", type=int, default=0, choices=[0, 1, 2])
+ap.add_argument("-half", type=int, default=0, choices=[0, 1], help="1: -sloppy 2 iterates on 16-bit storage (options half, half_batch)")
 ap.add_argument("-nev", type=int, default=0, help="deflate every batch with this many low modes (0: no eigensolve)")
 ap.add_argument("-nvecs", type=int, default=0, help="size of the Lanczos basis (default max(2 nev, nev + 8))")
 ap.add_argument("-cheb", type=int, default=12, help="Chebyshev degree (0: plain Lanczos)")
@@ -61,6 +63,9 @@ if world > 1:
     rng = q.RngField(lat, q.RngMilc6, a.seed, glat=glat, t_offset=rank * lt)
 else:
     ctx = q.Context(lat)
+    if a.half:
+        ctx.set_option("half", 1)
+        ctx.set_option("half_batch", 1)
     rng = q.RngField(lat, q.RngMilc6, a.seed)
 if rank != 0:
     sys.stdout = open(os.devnull, "w")            # one log, rank 0's

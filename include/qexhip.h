@@ -227,8 +227,14 @@ int qexhip_stag_solve_prev(qexhip_handle h, double *x, const double *b, double m
  *                             as int16 (qexhip_stag_links_info_half), fp32 arithmetic, the increment of x in fp32, the same
  *                             reliable updates and the same stop on the true fp64 residual.  If "half_stall" reliable updates in
  *                             a row do not lower the true residual the solve finishes in fp32 (qexhip_stag_sloppy_last says so;
- *                             iters and nupdates are then the sums).  Lock-step batches, multi-shift solves and t-sharded
- *                             contexts (or ghost zones forced on one rank) run single for sloppy = 2 whatever the option says
+ *                             iters and nupdates are then the sums).  With option "half_batch" = 1 (default 0, independent of
+ *                             "half") the lock-step batched entries -- qexhip_stag_solve_xx_batch_sloppy,
+ *                             qexhip_stag_solve_batch_sloppy, qexhip_dev_solve_batch_sloppy and the deflated batches -- run the
+ *                             same 16-bit solve for up to four systems in lock-step on one stream of the int16 links: every
+ *                             system returns the bits of its single-system 16-bit solve, stall guard and fp32 finish included
+ *                             (qexhip_stag_sloppy_last_batch).  With "half_batch" = 0 the batches run single for sloppy = 2;
+ *                             multi-shift solves and t-sharded contexts (or ghost zones forced on one rank) run single for
+ *                             sloppy = 2 whatever the options say
  * The solve stops on the TRUE (fp64) residual: r2_over_b2 is |b - A x|^2/|b|^2 of the returned x (solveXX); iters counts fp32
  * iterations; nupdates (may be NULL) receives the number of reliable updates, the last one that confirmed convergence included
  * (0 for sloppy = 0).  iters == maxits is not an error.  QEXHIP_ERR_ARG for sloppy outside 0..2.
@@ -247,6 +253,11 @@ int qexhip_stag_solve_sloppy(qexhip_handle h, double *x, const double *b, double
  * inner solves of a full solve (half_iters + f32_iters = iters); fell_back = 1 if the stall guard of a 16-bit solve handed over
  * to fp32.  Any pointer may be NULL. */
 int qexhip_stag_sloppy_last(qexhip_handle h, int *precision, int *half_iters, int *f32_iters, int *fell_back);
+/* The same per system for the last BATCHED sloppy call (the lock-step batched entries with sloppy > 0, the deflated batches): *n <- the
+ * number of systems of that call; the arrays hold n_max entries, of which the first min(*n, n_max) are written; sums over the inner
+ * batches of a full solve.  precision[j] = 0: system j ran no sloppy iteration (finished by the start or by the deflation).  The
+ * batched entries do not touch qexhip_stag_sloppy_last's report, nor the single-system entries this one.  Any pointer may be NULL. */
+int qexhip_stag_sloppy_last_batch(qexhip_handle h, int n_max, int *n, int *precision, int *half_iters, int *f32_iters, int *fell_back);
 /* The 16-bit vector format on the host, for nsites sites of 6 doubles (re, im of three colours): norm[i] = fp32 of the largest
  * |component| of site i, q[6 i + k] = rint(v 32767 / norm[i]) formed in double; a site whose norm is below the smallest normal
  * fp32 number is all zeros.  unpack: v = q norm / 32767.  Needs no device.  QEXHIP_ERR_ARG for a site that is not finite in fp32. */
@@ -328,6 +339,9 @@ int qexhip_stag_links_info_f32(qexhip_handle h, int *format, double *max_dev);
 /* the 16-bit counterpart of qexhip_dev_op_xx_sloppy: x[par] rounded to the 16-bit vector format, the two 16-bit sweeps (their
  * intermediate and result stored in the format), the result back in fp64.  One rank without ghost zones */
 int qexhip_dev_op_xx_half(qexhip_handle h, int r_id, int x_id, double m2, int par_even);
+/* the batched form: n <= 4 fields x_ids[j][par] rounded to the format, ONE batched operator (two multi-right-hand-side 16-bit sweeps that
+ * stream the links once for all systems) at m2[j], the results back in fp64 in r_ids[j][par]; per system the bits of qexhip_dev_op_xx_half */
+int qexhip_dev_op_xx_half_batch(qexhip_handle h, int n, const int *r_ids, const int *x_ids, const double *m2, int par_even);
 /* the 16-bit link copy (building it if stale, behind the fp32 copy whose format decision it shares): format 1 = rows 0,1 as int16
  * of u 32767 (clamped) + the fp32 copy's sign masks, 48 B per forward/backward pair; format 0 = 18 reals as int16 of u 32767 / s,
  * 72 B per pair, s = *s_fat for the one-hop links and *s_long for the Naik links: the largest |entry| of each kind (reported in
@@ -679,6 +693,9 @@ int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped
  *                  at maxits (default 4; 1: in the iteration that calls for an update)
  *   "half"         1: sloppy = 2 (SloppyHalf) iterates on 16-bit storage in the single-system solves of a one-rank context;
  *                  0 (default): it runs single.  Other values are refused
+ *   "half_batch"   1: sloppy = 2 on the lock-step batched entries (the deflated batches included) iterates on 16-bit storage, up to
+ *                  four systems per stream of the int16 links, on a one-rank context without ghost zones; 0 (default): those
+ *                  batches run single.  Independent of "half".  Other values are refused
  *   "half_stall"   successive reliable updates of a 16-bit solve that may fail to lower the true residual before the solve
  *                  finishes in fp32 (default 2; 0: hand over at the first update, a test hook)
  *   "stout_check"  inverse iterations of qexhip_stout_inverse posted between two read-backs of its device-side loop state

@@ -124,6 +124,20 @@ class Context {
     return ci;
   }
   void setOption(const char *name, int value) { check(qexhip_set_option(h, name, value)); }   // e.g. "flow_exp", 0
+  // per system what the last batched sloppy call ran (qexhip_stag_sloppy_last_batch)
+  struct SloppyLast { int precision = 0, halfIters = 0, f32Iters = 0, fellBack = 0; };
+  std::vector<SloppyLast> sloppyLastBatch() const {
+    int n = 0, p[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0}, fi[4] = {0, 0, 0, 0}, fb[4] = {0, 0, 0, 0};
+    check(qexhip_stag_sloppy_last_batch(h, 4, &n, p, hi, fi, fb));
+    std::vector<SloppyLast> out(n < 4 ? n : 4);
+    for (size_t j = 0; j < out.size(); j++) out[j] = SloppyLast{p[j], hi[j], fi[j], fb[j]};
+    return out;
+  }
+  // the batched 16-bit operator probe on resident fields (qexhip_dev_op_xx_half_batch)
+  void devOpXXHalfBatch(const std::vector<int> &rIds, const std::vector<int> &xIds, const std::vector<double> &m2, bool parEven = true) {
+    if (rIds.size() != xIds.size() || rIds.size() != m2.size()) throw std::invalid_argument("devOpXXHalfBatch: sizes differ");
+    check(qexhip_dev_op_xx_half_batch(h, (int)rIds.size(), rIds.data(), xIds.data(), m2.data(), parEven ? 1 : 0));
+  }
   static int deviceCount() { int n = 0; check(qexhip_device_count(&n)); return n; }
 };
 

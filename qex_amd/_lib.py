@@ -56,6 +56,8 @@ SYMBOLS = [
     ("qexhip_dev_op_xx_half", _ci, [_vp, _ci, _ci, _cd, _ci]),
     ("qexhip_stag_links_info_half", _ci, [_vp, _pi, _pd, _pd, _pd]),
     ("qexhip_stag_sloppy_last", _ci, [_vp, _pi, _pi, _pi, _pi]),
+    ("qexhip_dev_op_xx_half_batch", _ci, [_vp, _ci, _pi, _pi, _pd, _ci]),
+    ("qexhip_stag_sloppy_last_batch", _ci, [_vp, _ci, _pi, _pi, _pi, _pi, _pi]),
     ("qexhip_half_pack_host", _ci, [_pd, C.c_size_t, C.POINTER(C.c_int16), C.POINTER(C.c_float)]),
     ("qexhip_half_unpack_host", _ci, [C.POINTER(C.c_int16), C.POINTER(C.c_float), C.c_size_t, _pd]),
     ("qexhip_stag_solve_prev", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _ci, _pi, _pd]),

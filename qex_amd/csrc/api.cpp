@@ -184,6 +184,7 @@ extern "C" int qexhip_finalize(qexhip_handle c) {
   hisq_state_free(c);
   batch_state_free(c);
   batch_f32_state_free(c);
+  batch_half_state_free(c);
   msf_state_free(c);
   gfix_state_free(c);
   stout_state_free(c);
@@ -711,6 +712,33 @@ extern "C" int qexhip_dev_op_xx_half(qexhip_handle c, int r_id, int x_id, double
   CHK(find_field(c, x_id, &fx));
   return half_op_xx_probe(c, *fr, *fx, m2, par_even);
 }
+// the batched form of qexhip_dev_op_xx_half: n <= 4 fields rounded to the 16-bit format, ONE batched op_xx (two multi-RHS 16-bit sweeps),
+// the results back in fp64
+extern "C" int qexhip_dev_op_xx_half_batch(qexhip_handle c, int n, const int *r_ids, const int *x_ids, const double *m2, int par_even) {
+  if (!c || !r_ids || !x_ids || !m2) return QEXHIP_ERR_ARG;
+  if (n < 1 || n > 4) { qexhip_set_error("dev_op_xx_half_batch: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fr[4], *fx[4];
+  for (int j = 0; j < n; j++) {
+    CHK(find_field(c, r_ids[j], &fr[j]));
+    CHK(find_field(c, x_ids[j], &fx[j]));
+  }
+  return half_op_xx_batch_probe(c, n, fr, fx, m2, par_even);
+}
+// what the last batched sloppy call ran per system: n <- its systems; arrays of n_max entries, the first min(n, n_max) filled
+extern "C" int qexhip_stag_sloppy_last_batch(qexhip_handle c, int n_max, int *n, int *precision, int *half_iters, int *f32_iters,
+                                             int *fell_back) {
+  if (!c || n_max < 0) return QEXHIP_ERR_ARG;
+  const auto &l = c->slpb_last;
+  if (n) *n = l.n;
+  for (int j = 0; j < l.n && j < n_max; j++) {
+    if (precision) precision[j] = l.precision[j];
+    if (half_iters) half_iters[j] = l.half_iters[j];
+    if (f32_iters) f32_iters[j] = l.f32_iters[j];
+    if (fell_back) fell_back[j] = l.fell_back[j];
+  }
+  return 0;
+}
 extern "C" int qexhip_stag_links_info_half(qexhip_handle c, int *format, double *s_fat, double *s_long, double *max_dev) {
   if (!c) return QEXHIP_ERR_ARG;
   if (c->nranks > 1 || c->g.halo) { qexhip_set_error("the 16-bit links exist on one rank without ghost zones"); return QEXHIP_ERR_ARG; }
@@ -801,6 +829,7 @@ extern "C" int qexhip_release_workspace(qexhip_handle c) {
   half_state_free(c);                // and its 16-bit links and fields
   msf_state_free(c);                 // and the mixed multi-shift CG's fp32 search directions / increments
   batch_f32_state_free(c);           // and the batched form's fp32 fields
+  batch_half_state_free(c);          // and its 16-bit fields
   gfix_state_free(c);                // and the gauge-fixing transform with its polish scratch (qexhip_gfix_set_transform re-creates it)
   eig_state_free(c);                 // and the eigensolver's Lanczos work fields and buffers (never the user's bases)
   stout_state_free(c);               // and the stout chain with the scratch of smear / inverse (qexhip_stout_prepare re-creates it)
@@ -1193,6 +1222,10 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
     if (value != 0 && value != 1) { qexhip_set_error("option half: 0 (SloppyHalf runs single) or 1 (16-bit storage)"); return QEXHIP_ERR_ARG; }
     c->opt_half = value;
   }
+  else if (n == "half_batch") {
+    if (value != 0 && value != 1) { qexhip_set_error("option half_batch: 0 (SloppyHalf batches run single) or 1 (16-bit batches)"); return QEXHIP_ERR_ARG; }
+    c->opt_half_batch = value;
+  }
   else if (n == "half_stall") {
     if (value < 0) { qexhip_set_error("option half_stall: >= 0 failed reliable updates"); return QEXHIP_ERR_ARG; }
     c->opt_half_stall = value;
@@ -1472,6 +1505,7 @@ extern "C" int qexhip_dev_solve_batch_sloppy(qexhip_handle c, int n, const int *
     CHK(find_field(c, x_ids[j], &xs[j]));
     CHK(find_field(c, b_ids[j], &bs[j]));
   }
+  slpb_last_reset(c, n);
   return solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates);
 }
 // ---- the deflated lock-step batch (solver.cpp: solve_xx_batch_deflated_dev; batch.hip: the full solves) ----
@@ -1497,7 +1531,8 @@ extern "C" int qexhip_dev_solve_xx_batch_deflated(qexhip_handle c, int basis, in
     CHK(find_field(c, b_ids[j], &bs[j]));
   }
   HIPCHK(hipSetDevice(c->device));
-  return solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, par_even ? 1 : 0, sloppy ? 1 : 0, iters, r2_over_b2, nupdates);
+  slpb_last_reset(c, n);
+  return solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, par_even ? 1 : 0, sloppy, iters, r2_over_b2, nupdates);
 }
 extern "C" int qexhip_dev_solve_batch_deflated(qexhip_handle c, int basis, int nev, int n, const int *x_ids, const int *b_ids,
                                                const double *mass, const double *r2req, int maxits, int sloppy, int *iters,
@@ -1512,7 +1547,8 @@ extern "C" int qexhip_dev_solve_batch_deflated(qexhip_handle c, int basis, int n
     CHK(find_field(c, b_ids[j], &bs[j]));
   }
   HIPCHK(hipSetDevice(c->device));
-  return solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2_final, nupdates);
+  slpb_last_reset(c, n);
+  return solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2_final, nupdates);
 }
 static int solve_batch_deflated_host(qexhip_ctx *c, int basis, int nev, int n, double *const *x, const double *const *b, const double *mass,
                                      const double *r2req, int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates) {
@@ -1524,8 +1560,9 @@ static int solve_batch_deflated_host(qexhip_ctx *c, int basis, int nev, int n, d
   DevField *xs[4], *bs[4];
   CHK(batch_io_fields(c, n, xs, bs));
   for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
-  if (xx_parity >= 0) CHK(solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, xx_parity, sloppy ? 1 : 0, iters, r2, nupdates));
-  else CHK(solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy ? 1 : 0, iters, r2, nupdates));
+  slpb_last_reset(c, n);
+  if (xx_parity >= 0) CHK(solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, xx_parity, sloppy, iters, r2, nupdates));
+  else CHK(solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
   for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
   return 0;
 }

@@ -607,9 +607,16 @@ static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **
         }
       if (!k) continue;
       // systems of one group share maxits: the remaining budget of the one that has used least
-      if (defl && nev > 0) CHK(solve_xx_batch_deflated_dev(c, *defl, nev, k, xs, bs, ms, rrs, mx, par, sloppy ? 1 : 0, its, nullptr, nup));
-      else if (sloppy) CHK(solve_xx_batch_sloppy_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr, nup));
-      else CHK(solve_xx_batch_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr));
+      // (the sloppy batches report per system through c->slpb_last.map: system of this call <- system of the inner batch)
+      int outer[QX_MAXRHS];
+      for (int i = 0; i < QX_MAXRHS; i++) outer[i] = c->slpb_last.map[i];
+      for (int i = 0; i < k; i++) c->slpb_last.map[i] = outer[idx[i]];
+      int rc = 0;
+      if (defl && nev > 0) rc = solve_xx_batch_deflated_dev(c, *defl, nev, k, xs, bs, ms, rrs, mx, par, sloppy, its, nullptr, nup);
+      else if (sloppy) rc = solve_xx_batch_sloppy_any(c, sloppy, k, xs, bs, ms, rrs, mx, par, its, nullptr, nup);
+      else rc = solve_xx_batch_dev(c, k, xs, bs, ms, rrs, mx, par, its, nullptr);
+      for (int i = 0; i < QX_MAXRHS; i++) c->slpb_last.map[i] = outer[i];
+      CHK(rc);
       for (int i = 0; i < k; i++) {
         S[idx[i]].n = its[i];
         if (nupdates) nupdates[idx[i]] += nup[i];

@@ -112,14 +112,6 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_f32(MrhsF32Args A) {
 
 // ---- the reliable-update CG's BLAS and bookkeeping kernels (dslash_f32.hip: k_slp_*) for n systems: system = blockIdx.y, each with
 // the single-system kernel's grid in x, so the workgroup partials group as they do there ----
-struct SlpBatch {
-  double2 *x[QX_MAXRHS], *r[QX_MAXRHS];          // fp64: solution, true residual
-  const double2 *b[QX_MAXRHS], *Ax[QX_MAXRHS];   // fp64: source, A x of the reliable update
-  float2 *rs[QX_MAXRHS], *ps[QX_MAXRHS], *xs[QX_MAXRHS];
-  const float2 *aps[QX_MAXRHS];
-  double *dotp[QX_MAXRHS], *r2p[QX_MAXRHS];      // <p,Ap> partials of the second sweep; |r_s|^2 / |b - A x|^2 partials
-  SlpScal *s;
-};
 
 __global__ void __launch_bounds__(256) k_slpb_xpay(SlpBatch B, size_t n) {
   const int j = blockIdx.y;
@@ -238,6 +230,24 @@ __global__ void __launch_bounds__(256) k_slpb_rclose(SlpBatch B, int nparts) {
       if (!(s->r2s_old > 0)) s->first = 1;
     }
   }
+}
+
+// the bookkeeping launches for another file's iteration kernels (batch_half.hip): one rank
+int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts) {
+  k_slpb_close<<<n, 256, 0, c->stream>>>(L, nparts, SLP_DELTA * SLP_DELTA);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int slpb_flush(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb) {
+  k_slpb_flush<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb) {
+  k_slpb_resid<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
+  k_slpb_rclose<<<n, 256, 0, c->stream>>>(L, nbb);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -398,7 +408,8 @@ int solve_batch_sloppy_host(qexhip_ctx *c, int n, double *const *x, const double
   DevField *xs[QX_MAXRHS], *bs[QX_MAXRHS];
   CHK(batch_io_fields(c, n, xs, bs));
   for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
-  if (xx_parity >= 0) CHK(solve_xx_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2, nupdates));
+  slpb_last_reset(c, n);
+  if (xx_parity >= 0) CHK(solve_xx_batch_sloppy_any(c, sloppy, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2, nupdates));
   else CHK(solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
   for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
   return 0;

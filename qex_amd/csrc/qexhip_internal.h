@@ -243,6 +243,11 @@ struct qexhip_ctx {
   int opt_half = 0;                                  // option "half": 1 = sloppy = 2 runs the 16-bit path (single-system solves on one rank)
   int opt_half_stall = 2;                            // option "half_stall": failed reliable updates in a row before the 16-bit solve finishes in fp32
   struct { int precision = 0, half_iters = 0, f32_iters = 0, fell_back = 0; } slp_last;   // the last sloppy solve (qexhip_stag_sloppy_last)
+  void *batch_half = nullptr;                        // BatchHalfState (batch_half.hip): 16-bit fields, x_s, SlpScal[4] and stall guards of the 16-bit lock-step batch
+  int opt_half_batch = 0;                            // option "half_batch": 1 = sloppy = 2 on the batched entries runs the 16-bit batch (one rank, no ghost zones)
+  // the last batched sloppy call per system (qexhip_stag_sloppy_last_batch); map: system of the entry <- system of the inner batch
+  struct { int n = 0, precision[4] = {0, 0, 0, 0}, half_iters[4] = {0, 0, 0, 0}, f32_iters[4] = {0, 0, 0, 0}, fell_back[4] = {0, 0, 0, 0},
+           map[4] = {0, 1, 2, 3}; } slpb_last;
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -299,6 +304,30 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
                               int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
 int solve_full_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                                 int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);     // (batch.hip)
+#define QX_MAXRHS 4
+struct SlpBatch {
+  double2 *x[QX_MAXRHS], *r[QX_MAXRHS];          // fp64: solution, true residual
+  const double2 *b[QX_MAXRHS], *Ax[QX_MAXRHS];   // fp64: source, A x of the reliable update
+  float2 *rs[QX_MAXRHS], *ps[QX_MAXRHS], *xs[QX_MAXRHS];
+  const float2 *aps[QX_MAXRHS];
+  double *dotp[QX_MAXRHS], *r2p[QX_MAXRHS];      // <p,Ap> partials of the second sweep; |r_s|^2 / |b - A x|^2 partials
+  SlpScal *s;
+};
+// k_slpb_close / k_slpb_flush / k_slpb_resid + k_slpb_rclose for n systems, for the 16-bit batch (nvec, nbb: the fp32 batch's BLAS size and grid)
+int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts);
+int slpb_flush(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb);
+int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb);
+
+// ---- batch_half.hip: the 16-bit lock-step batch (option "half_batch") ----
+void batch_half_state_free(qexhip_ctx *c);
+int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                            int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
+// the batched sloppy solveXX of either storage: sloppy = 2 takes the 16-bit batch where option "half_batch" is set (one rank, no
+// ghost zones), everything else the fp32 batch; both add what they ran to c->slpb_last through its map
+int solve_xx_batch_sloppy_any(qexhip_ctx *c, int sloppy, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
+                              int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
+void slpb_last_reset(qexhip_ctx *c, int n);             // the batched entries start a new report
+int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even);
 int solve_batch_sloppy_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass, const double *r2req,
                             int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates);
 int nhyp_fforce(qexhip_ctx *c, double *f_host, int n, const double *const *phi, const double *mass, const double *scale,
@@ -457,6 +486,10 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
 // the option is set and the context is one rank without ghost zones.  Both add what they ran to c->slp_last.
 int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                       int *iters, double *r2_over_b2, int *nupdates);
+// the fp32 finish of a 16-bit solve whose stall guard tripped (single and batched): A e = r to r2stop / *r2t with solve_xx_sloppy_dev,
+// x += e, the true residual recomputed once into *r2t (Ax: scratch).  Uses POOL_REF, POOL_REF + 4 and the single sloppy solve's fields.
+int half_finish_f32(qexhip_ctx *c, DevField &x, DevField &b, const DevField &r, DevField &Ax, double mass, double r2stop, int maxits,
+                    int par_even, double *r2t, int *its32, int *nupd32);
 int solve_xx_sloppy_any(qexhip_ctx *c, int sloppy, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                         int *iters, double *r2_over_b2, int *nupdates);
 int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts,

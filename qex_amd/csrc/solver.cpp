@@ -314,17 +314,8 @@ int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, doub
   CHK(slph_stalled(c, &stalled));
   if (stalled && r2t > h.r2stop && its < maxits) {
     // (x holds every increment: the update that tripped the guard flushed x_s; r is its true residual)
-    DevField *e, *rc;
-    CHK(pool_field(c, POOL_REF, &e));
-    CHK(pool_field(c, POOL_REF + 4, &rc));
-    CHK(blas_copy(c, *rc, *r, par));
     int nu32 = 0;
-    CHK(solve_xx_sloppy_dev(c, *e, *rc, mass, h.r2stop / r2t, maxits - its, par_even, &its32, nullptr, &nu32));
-    CHK(blas_axpy(c, 1.0, *e, x, par));
-    CHK(op_xx(c, *Ax, x, m2, par_even, 0, nullptr));
-    CHK(blas_axpby(c, 1.0, b, -1.0, *Ax, *rc, par));
-    CHK(blas_norm2(c, *rc, par, &c->dscal[1]));
-    CHK(read_scalars(c, &c->dscal[1], 1, &r2t));
+    CHK(half_finish_f32(c, x, b, *r, *Ax, mass, h.r2stop, maxits - its, par_even, &r2t, &its32, &nu32));
     nupd += nu32;
     c->slp_last.fell_back = 1;
   }
@@ -335,6 +326,23 @@ int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, doub
   if (r2_over_b2) *r2_over_b2 = (h.b2 != 0.0) ? r2t / h.b2 : 0.0;
   if (nupdates) *nupdates = nupd;
   return 0;
+}
+
+// the fp32 finish of a 16-bit solve whose stall guard tripped, for solve_xx_half_dev above and for every stalled system of the 16-bit batch
+// (batch_half.hip): r is the true residual of x; A e = r with solve_xx_sloppy_dev to r2stop / *r2t, x += e, *r2t recomputed once
+int half_finish_f32(qexhip_ctx *c, DevField &x, DevField &b, const DevField &r, DevField &Ax, double mass, double r2stop, int maxits,
+                    int par_even, double *r2t, int *its32, int *nupd32) {
+  const int par = par_even ? 0 : 1;
+  DevField *e, *rc;
+  CHK(pool_field(c, POOL_REF, &e));
+  CHK(pool_field(c, POOL_REF + 4, &rc));
+  CHK(blas_copy(c, *rc, r, par));
+  CHK(solve_xx_sloppy_dev(c, *e, *rc, mass, r2stop / *r2t, maxits, par_even, its32, nullptr, nupd32));
+  CHK(blas_axpy(c, 1.0, *e, x, par));
+  CHK(op_xx(c, Ax, x, mass * mass, par_even, 0, nullptr));
+  CHK(blas_axpby(c, 1.0, b, -1.0, Ax, *rc, par));
+  CHK(blas_norm2(c, *rc, par, &c->dscal[1]));
+  return read_scalars(c, &c->dscal[1], 1, r2t);
 }
 
 int solve_xx_sloppy_any(qexhip_ctx *c, int sloppy, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
@@ -559,7 +567,7 @@ int solve_xx_batch_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, int n, DevF
   if (nupdates) for (int k = 0; k < n; k++) nupdates[k] = 0;
   if (nev == 0) {
     if (!sloppy) return solve_xx_batch_dev(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2);
-    return solve_xx_batch_sloppy_dev(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
+    return solve_xx_batch_sloppy_any(c, sloppy, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
   }
   const int par = par_even ? 0 : 1;
   CHK(eig_rayleigh(c, B, nev));
@@ -621,7 +629,14 @@ int solve_xx_batch_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, int n, DevF
     }
   if (ns > 0) {
     if (!sloppy) CHK(solve_xx_batch_dev(c, ns, dx, db, mm, rq, maxits, par_even, its, nullptr));
-    else CHK(solve_xx_batch_sloppy_dev(c, ns, dx, db, mm, rq, maxits, par_even, its, nullptr, nup));
+    else {
+      int outer[EIG_MAXRHS];
+      for (int q = 0; q < EIG_MAXRHS; q++) outer[q] = c->slpb_last.map[q];
+      for (int q = 0; q < ns; q++) c->slpb_last.map[q] = outer[sel[q]];
+      const int rc = solve_xx_batch_sloppy_any(c, sloppy, ns, dx, db, mm, rq, maxits, par_even, its, nullptr, nup);
+      for (int q = 0; q < EIG_MAXRHS; q++) c->slpb_last.map[q] = outer[q];
+      CHK(rc);
+    }
     for (int q = 0; q < ns; q++) {
       const int k = sel[q];
       CHK(blas_axpy(c, 1.0, *dx[q], *x[k], par));

@@ -298,6 +298,24 @@ class Context:
         check(lib().qexhip_stag_sloppy_last(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("precision", "half_iters", "f32_iters", "fell_back"), (x.value for x in v)))
 
+    def dev_op_xx_half_batch(self, r_ids, x_ids, m2s, par_even=True):
+        """the batched form of dev_op_xx_half (qexhip_dev_op_xx_half_batch): n <= 4 fields rounded to the 16-bit format, one batched
+        operator with its own m2 per system (the links streamed once for all of them), the results back in fp64"""
+        n = len(x_ids)
+        if len(r_ids) != n or len(m2s) != n:
+            raise ValueError("dev_op_xx_half_batch: r_ids, x_ids and m2s differ in length")
+        check(lib().qexhip_dev_op_xx_half_batch(self._h, n, (C.c_int * max(n, 1))(*[int(v) for v in r_ids]),
+                                                (C.c_int * max(n, 1))(*[int(v) for v in x_ids]),
+                                                (C.c_double * max(n, 1))(*[float(v) for v in m2s]), 1 if par_even else 0))
+
+    def sloppy_last_batch(self):
+        """what the last batched sloppy call ran per system (qexhip_stag_sloppy_last_batch): a list of dicts as sloppy_last()'s"""
+        n = C.c_int(0)
+        v = [(C.c_int * 4)() for _ in range(4)]
+        check(lib().qexhip_stag_sloppy_last_batch(self._h, 4, C.byref(n), *v))
+        keys = ("precision", "half_iters", "f32_iters", "fell_back")
+        return [dict(zip(keys, (a[j] for a in v))) for j in range(min(n.value, 4))]
+
     def release_workspace(self):
         check(lib().qexhip_release_workspace(self._h))
 
