@@ -70,14 +70,30 @@ __device__ __forceinline__ void recon_row2_res(double2 U[9], const double2 *row,
   for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
 }
 
-// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3: lossless (link_residual.h)
+// packed lossless format (RECON 4, link_residual.h): the whole link from the slots in U[0..5] and the row's extra word; an escaped
+// lane reads all 18 reals from W (arguments as above)
+__device__ __forceinline__ void recon_packed(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
+                                             size_t fr, int lane) {
+  const uint32_t extra = __builtin_nontemporal_load((const uint32_t *)(row + LP_EXTRA) + lane);
+  uint64_t s[12];
+#pragma unroll
+  for (int k = 0; k < 6; k++) { s[2 * k] = lr_bits(U[k].x); s[2 * k + 1] = lr_bits(U[k].y); }
+  lp_decode(s, extra, (m[0] >> lane) & 1ull, U);
+  if ((m[1] >> lane) & 1ull) {
+    const double2 *wf = (const double2 *)(uintptr_t)hdr[0] + fr;
+#pragma unroll
+    for (int k = 0; k < 9; k++) U[k] = wf[k * 64];
+  }
+}
+
+// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3: lossless (link_residual.h), 4: its packed form
 template <int RECON> struct LinkFormat {
-  static constexpr int NLOAD = (RECON == 1 || RECON == 3) ? 6 : (RECON == 2 ? 7 : 9);      // double2 loaded per lane and link
-  static constexpr int LROW = RECON == 3 ? LR_ROW : NLOAD * 64;                             // double2 per (tile, direction) row
+  static constexpr int NLOAD = (RECON == 1 || RECON >= 3) ? 6 : (RECON == 2 ? 7 : 9);      // double2 loaded per lane and link
+  static constexpr int LROW = RECON == 3 ? LR_ROW : (RECON == 4 ? LP_ROW : NLOAD * 64);     // double2 per (tile, direction) row
 };
 
 // The links of one output site as a sweep reads them: built once per site from the parity's link base W, its mask base S (RECON 1:
-// sign masks [tile][dir], bit = lane; 3: [tile][dir][sign, escape], S[-2] = this parity's 18-real W) and the site c.
+// sign masks [tile][dir], bit = lane; 3, 4: [tile][dir][sign, escape], S[-2] = this parity's 18-real W) and the site c.
 // fetch(pr, ..) gives the forward link of hop pair pr (direction 2 pr; fat links: pairs 0..3, 3-hop links: 4..7) in U and the backward
 // link (direction 2 pr + 1) in Wb, rebuilt to 3x3.  The batched sweep (batch.hip) calls it; dslash_body (dslash.hip) takes the cursor's
 // rows and masks but spells the same statements out in place, because through the call its RECON 1 / 2 kernels change registers
@@ -86,13 +102,13 @@ template <int NDIR, int RECON>
 struct LinkCursor {
   static constexpr int NLOAD = LinkFormat<RECON>::NLOAD, LROW = LinkFormat<RECON>::LROW;
   const double2 *w;                  // this lane's element of the site's first (tile, direction) row
-  const unsigned long long *sm;      // the tile's mask row (RECON 1, 3)
-  const unsigned long long *hdr;     // RECON 3: header of the parity's mask block
+  const unsigned long long *sm;      // the tile's mask row (RECON 1, 3, 4)
+  const unsigned long long *hdr;     // RECON 3, 4: header of the parity's mask block
   int tile, lane;
   __device__ __forceinline__ LinkCursor(const double2 *W, const unsigned long long *S, const int c)
       : w(W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63)),
-        sm(RECON == 1 ? S + (size_t)(c >> 6) * NDIR : (RECON == 3 ? S + (size_t)(c >> 6) * NDIR * 2 : nullptr)),
-        hdr(RECON == 3 ? S - 2 : nullptr), tile(c >> 6), lane(c & 63) {}
+        sm(RECON == 1 ? S + (size_t)(c >> 6) * NDIR : (RECON >= 3 ? S + (size_t)(c >> 6) * NDIR * 2 : nullptr)),
+        hdr(RECON >= 3 ? S - 2 : nullptr), tile(c >> 6), lane(c & 63) {}
   // do_f / do_b: which of the pair's two links this call takes (literally true on the fast paths)
   __device__ __forceinline__ void fetch(const int pr, const bool do_f, const bool do_b, double2 U[9], double2 Wb[9]) const {
     const double2 *wp = w + (size_t)pr * (2 * LROW);
@@ -121,6 +137,10 @@ struct LinkCursor {
       const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
       if (do_f) recon_row2_res(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
       if (do_b) recon_row2_res(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
+    } else if (RECON == 4) {
+      const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
+      if (do_f) recon_packed(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
+      if (do_b) recon_packed(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
     } else if (RECON == 2) {
       if (do_f) recon_row2<2>(U, false);
       if (do_b) recon_row2<2>(Wb, false);
@@ -132,7 +152,7 @@ struct LinkCursor {
 // (RECON 0: 9 double2) or Wc (RECON 1: rows 0,1; RECON 2: rows 0,1 + det), `sm` at the row's sign mask (RECON 1 only)
 template <int RECON>
 __device__ __forceinline__ void load_link(double2 U[9], const double2 *w, const unsigned long long *sm, int lane) {
-  static_assert(RECON != 3, "the lossless rows are read through LinkCursor only");
+  static_assert(RECON < 3, "the lossless rows are read through LinkCursor only");
 #pragma unroll
   for (int k = 0; k < LinkFormat<RECON>::NLOAD; k++) U[k] = w[k * 64];
   if (RECON == 1) recon_row2<1>(U, (*sm >> lane) & 1ull);

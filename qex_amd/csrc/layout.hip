@@ -259,6 +259,35 @@ __global__ void __launch_bounds__(256) k_links_residual(size_t nrows, size_t pro
   }
 }
 
+// The packed form of the same (link_residual.h, RECON 4): slots and extra into Wc (row stride LP_ROW), the masks as above.  Lanes
+// beyond the parity's last site (Vh) hold no link: never read, never escaped.
+__global__ void __launch_bounds__(256) k_links_packed(size_t nrows, size_t prows, int Vh, const double2 *__restrict__ W, double2 *Wc,
+                                                      unsigned long long *Wm, unsigned int *nesc) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // (row = (parity, tile, dir), lane)
+  const size_t row = j >> 6;
+  if (row >= nrows) return;
+  const int l = j & 63;
+  const double2 *w = W + row * 576 + l;
+  double2 u[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) u[k] = w[k * 64];
+  bool neg;
+  uint64_t s[12];
+  uint32_t extra;
+  const bool ok = lp_encode(u, &neg, s, &extra) || (long long)((row % prows) / 8 * 64 + l) >= Vh;
+  ulonglong2 *o = (ulonglong2 *)(Wc + row * LP_ROW) + l;
+#pragma unroll
+  for (int k = 0; k < 6; k++) o[k * 64] = make_ulonglong2(s[2 * k], s[2 * k + 1]);
+  ((uint32_t *)(Wc + row * LP_ROW + LP_EXTRA))[l] = extra;
+  const unsigned long long sgn = __ballot(neg), esc = __ballot(!ok);
+  if (l == 0) {
+    unsigned long long *m = Wm + 2 * (row + row / prows + 1);
+    m[0] = sgn;
+    m[1] = esc;
+    if (esc) atomicAdd(nesc, (unsigned int)__popcll(esc));
+  }
+}
+
 // The same encoder and decoder on the host (qexhip_link_residual_host): n links of 9 double2 each
 int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2 *row2) {
   for (long i = 0; i < n; i++) {
@@ -268,6 +297,18 @@ int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2
     const bool ok = lr_encode(u + 9 * i, &neg, &lo, &hi);
     if (escaped) escaped[i] = !ok;
     if (row2) lr_decode(u + 9 * i, neg, lo, hi, row2 + 3 * i);
+  }
+  return 0;
+}
+// ... and of the packed form (qexhip_link_packed_host): the whole link as decoded
+int link_packed_host(const double2 *u, long n, unsigned char *escaped, double2 *dec) {
+  for (long i = 0; i < n; i++) {
+    bool neg;
+    uint64_t s[12];
+    uint32_t extra;
+    const bool ok = lp_encode(u + 9 * i, &neg, s, &extra);
+    if (escaped) escaped[i] = !ok;
+    if (dec) lp_decode(s, extra, neg, dec + 9 * i);
   }
   return 0;
 }
@@ -302,8 +343,9 @@ int links_compress(qexhip_ctx *c) {
     if (fmt == 1 || dev <= 5e-14f) c->recon_dev = dev;
     if (dev <= 5e-14f) { c->recon = fmt; break; }
   }
-  // neither format holds: the residual format when at most 1 % of the links escape it (8-link operators; it stores the same
-  // operator bit for bit, so qexhip_stag_links_info keeps reporting format 0)
+  // neither format holds: a lossless form when at most 1 % of the links escape it (8-link operators; it stores the same operator
+  // bit for bit, so qexhip_stag_links_info keeps reporting format 0).  Option lossless = 2: the packed 100-byte form first, then
+  // the 108-byte residual form under its own rule; 1: the residual form only
   if (!c->recon && c->opt_lossless && c->ndir == 8) {
     if (!c->Wm || c->Wm_rows < nrows) {
       if (c->Wm) HIPCHK(hipFree(c->Wm));
@@ -312,16 +354,19 @@ int links_compress(qexhip_ctx *c) {
       c->Wm_rows = nrows;
     }
     const size_t prows = nrows / 2;
-    HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
-    k_links_residual<<<nblk, 256, 0, c->stream>>>(nrows, prows, c->W, c->Wc, c->Wm, flag);
-    HIPCHK(hipGetLastError());
-    unsigned int nesc = 0;
-    HIPCHK(hipMemcpyAsync(&nesc, flag, sizeof(nesc), hipMemcpyDeviceToHost, c->stream));
     const unsigned long long hdr[2][2] = {{(unsigned long long)(uintptr_t)c->W, 0}, {(unsigned long long)(uintptr_t)(c->W + prows * 576), 0}};
-    for (int p = 0; p < 2; p++) HIPCHK(hipMemcpyAsync(c->Wm + p * 2 * (prows + 1), hdr[p], sizeof hdr[p], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->lres_esc = nesc;
-    if ((double)nesc <= 0.01 * (double)(nrows * 64)) c->lres = 1;
+    for (int form = c->opt_lossless >= 2 ? 2 : 1; form >= 1 && !c->lres; form--) {
+      HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
+      if (form == 2) k_links_packed<<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
+      else k_links_residual<<<nblk, 256, 0, c->stream>>>(nrows, prows, c->W, c->Wc, c->Wm, flag);
+      HIPCHK(hipGetLastError());
+      unsigned int nesc = 0;
+      HIPCHK(hipMemcpyAsync(&nesc, flag, sizeof(nesc), hipMemcpyDeviceToHost, c->stream));
+      for (int p = 0; p < 2; p++) HIPCHK(hipMemcpyAsync(c->Wm + p * 2 * (prows + 1), hdr[p], sizeof hdr[p], hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      c->lres_esc = nesc;
+      if ((double)nesc <= 0.01 * (double)(nrows * 64)) c->lres = form;
+    }
   }
   return 0;
 }

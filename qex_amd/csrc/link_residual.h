@@ -90,3 +90,77 @@ __host__ __device__ __forceinline__ bool lr_encode(const double2 u[9], bool *neg
   *hi = (uint32_t)(uint16_t)k[4] | (uint32_t)(uint16_t)k[5] << 16;
   return ok;
 }
+
+// ---- the packed form (RECON 4): 100 B per link -------------------------------------------------------------------------------
+// Every real of a near-unitary matrix lies in (-2, 2) and almost every one above 2^-15: bits 62..56 of such a double (the top
+// seven exponent bits) are 0111111 and carry nothing, 84 constant bits in rows 0,1.  The residuals of row 2 live there, 19 bits
+// wide (fewer escapes than int16).  Per (parity, tile, dir) row:
+//   u64     slot[6][64][2]    rows 0,1 in the order of the rows above (slot 2i = the real, 2i+1 = the imaginary part of element i,
+//                             one 16-byte load): the IEEE bits with bits 62..56 replaced by 7 payload bits; the real is
+//                             (slot & ~(0x7F << 56)) | (0x3F << 56)
+//   u32     extra[64]         at double2 offset 384
+// = 400 double2 = 100 B per link.  Residual k_j (signed, |k| <= 262143): bits 0..6 = payload of slot 2j, 7..13 = payload of slot
+// 2j+1, 14..18 = extra bits [5j, 5j+5); extra bits 30, 31 are zero.  Row 2 is lr_apply(rec_j, k_j) on the rebuild lr_rebuild of
+// the decoded rows 0,1: the residual format's bits.  Masks and header as above (one lossless form is live per context); an
+// escaped lane reads the WHOLE link from the 18 reals.
+#define LP_ROW 400          // double2 per (tile, dir) row
+#define LP_EXTRA 384        // double2 offset of extra in a row
+#define LP_KMAX 262143
+#define LP_PAY (0x7Full << 56)
+#define LP_EXP (0x3Full << 56)
+
+// the real a slot holds / whether a real fits a slot: 2^-15 <= |v| < 2
+__host__ __device__ __forceinline__ double lp_real(uint64_t slot) { return lr_double((slot & ~LP_PAY) | LP_EXP); }
+__host__ __device__ __forceinline__ bool lp_fits(double v) { return (lr_bits(v) & LP_PAY) == LP_EXP; }
+
+// slots + extra + sign -> the link u[9]
+__host__ __device__ __forceinline__ void lp_decode(const uint64_t s[12], uint32_t extra, bool neg, double2 u[9]) {
+  int k[6];
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const uint32_t v = (uint32_t)(s[2 * j] >> 56 & 0x7f) | (uint32_t)(s[2 * j + 1] >> 56 & 0x7f) << 7 | (extra >> (5 * j) & 31u) << 14;
+    k[j] = (int)(v << 13) >> 13;                      // sign-extend 19 bits
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) u[j] = make_double2(lp_real(s[2 * j]), lp_real(s[2 * j + 1]));
+  double rec[6];
+  lr_rebuild(u, neg, rec);
+#pragma unroll
+  for (int j = 0; j < 3; j++) u[6 + j] = make_double2(lr_apply(rec[2 * j], k[2 * j]), lr_apply(rec[2 * j + 1], k[2 * j + 1]));
+}
+
+// A full link u[9] -> sign, slots and extra.  Returns true when the link decodes back to u bit for bit in all 18 reals; false
+// (escaped) otherwise: a real of rows 0,1 outside the window, |k| > 262143, or anything lr_encode escapes.  Sign rule of lr_encode.
+__host__ __device__ __forceinline__ bool lp_encode(const double2 u[9], bool *neg, uint64_t s[12], uint32_t *extra) {
+  double rec[6];
+  lr_rebuild(u, false, rec);
+  double px = 0;
+#pragma unroll
+  for (int j = 0; j < 3; j++) px += u[6 + j].x * rec[2 * j] + u[6 + j].y * rec[2 * j + 1];
+  const bool ng = px < 0;
+  if (ng) {
+#pragma unroll
+    for (int j = 0; j < 6; j++) rec[j] = -rec[j];
+  }
+  const double row2[6] = {u[6].x, u[6].y, u[7].x, u[7].y, u[8].x, u[8].y};
+  bool ok = true;
+  uint32_t ex = 0;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    ok = ok && lp_fits(u[j].x) && lp_fits(u[j].y);
+    const double sc = lr_double(lr_bits(rec[j]) & 0x7ff0000000000000ull) * 0x1p-52;
+    const double q = sc > 0 ? (row2[j] - rec[j]) / sc : 0.0;
+    const int k = fabs(q) <= (double)LP_KMAX ? (int)rint(q) : 0;  // (false for a NaN q too)
+    const uint32_t v = (uint32_t)k & 0x7ffffu;
+    s[2 * j] = (lr_bits(u[j].x) & ~LP_PAY) | (uint64_t)(v & 0x7f) << 56;
+    s[2 * j + 1] = (lr_bits(u[j].y) & ~LP_PAY) | (uint64_t)(v >> 7 & 0x7f) << 56;
+    ex |= (v >> 14) << (5 * j);
+  }
+  double2 d[9];
+  lp_decode(s, ex, ng, d);
+#pragma unroll
+  for (int j = 0; j < 9; j++) ok = ok && lr_bits(d[j].x) == lr_bits(u[j].x) && lr_bits(d[j].y) == lr_bits(u[j].y);
+  *neg = ng;
+  *extra = ex;
+  return ok;
+}
