@@ -3,7 +3,15 @@ eigenpairs of Staggered.eigs against the dense spectrum of the oracle's operator
 dense matrix.  tests/eig_ref.py builds the inputs and the dense references once per lattice.
 
 Lattices: 4.4.4.6 (576 dimensions on the even sites, exactly 3 wavefront tiles), 4.6.4.6 (864 dimensions, 4.5 tiles: a ragged last
-tile), 4.4.8.8 (1536 dimensions).  Observed values are printed (pytest -s)."""
+tile), 4.4.8.8 (1536 dimensions).  Observed values are printed (pytest -s).
+
+Sizes.  The block-kernel tests of this module stop at n = 17 vectors per call and rotations of m <= 40; the sizes the eigensolver
+and the deflated solves use them at -- more than 128 vectors (the 128-vector chunks of the block dot), m in 64 .. 512 (all three
+instantiations of k_rotate, with and without the large-LDS opt-in) and every grid-stride loop wrapped (30.30.30.22, 14.14.14.34)
+-- are held to numpy in test_gpu_eig_blocks.py: integer data exactly, Gaussian data within the bound of the kernel's own
+summation (observed worst ratios to the bound: rotation 0.016, block axpy 0.007, block dot 0.009).  Here one eigensolve with
+nev = 48 of nvecs = 210 on 4.6.4.6 (k_rotate<32> from 210 to 129 vectors, orthogonalisation in two chunks) and the deflated solves
+with the 129 vectors it leaves (144 -> 47 iterations) run those paths inside the solvers."""
 import ctypes as C
 
 import numpy as np
@@ -179,6 +187,79 @@ def test_eigenpairs_of_a_hisq_operator():
     finally:
         B.free()
         ctx.close()
+
+
+# ---------------------------------------------------------------- more than 128 vectors
+# nev = 48 of nvecs = 210 on 4.6.4.6: every restart rotates m = 210 vectors down to k = 48 + (210 - 48) / 2 = 129 with k_rotate<32>
+# (five passes of its column loop), and the orthogonalisation of steps 128 .. 209 runs the block dot in two chunks.  The 48th
+# eigenvalue is 0.199 < cheb_lo.  The 129 Ritz vectors the last restart keeps are orthonormal (48 converged pairs, 81 further Ritz
+# vectors of the same Lanczos space), which is all the projection x0 = sum_i v_i <v_i, b> / (4 (rho_i + m^2)) with their Rayleigh
+# quotients rho_i needs: the deflated solves below take nev = 129 of them.
+WLAT, WNEV, WNVECS, WDEFL = (4, 6, 4, 6), 48, 210, 129
+
+
+@pytest.fixture(scope="module")
+def wide():
+    import time
+
+    import qex_amd as q
+    from oracle import oracle as o
+
+    lo, g, _, b = R.inputs(WLAT)
+    ctx = q.Context(list(WLAT), device=0)
+    s = q.newStag(ctx, g)
+    t0 = time.time()
+    B = s.eigs(WNEV, nvecs=WNVECS, relerr=0.0, abserr=1e-9, **CHEB)
+    print("eigs nev = %d nvecs = %d on %s: %.2f s" % (WNEV, WNVECS, WLAT, time.time() - t0))
+    rf = o.RngField(lo, o.RNG_MILC6, 4242)
+    bs = [np.ascontiguousarray(b)] + [o.vector_gaussian(lo, rf) for _ in range(3)]
+    yield dict(ctx=ctx, s=s, B=B, bs=bs, lo=lo, g=g, vh=lo.vol // 2)
+    B.free()
+    ctx.close()
+
+
+def test_eigenpairs_with_more_than_128_vectors(wide):
+    assert WNVECS > 128 and WNEV + (WNVECS - WNEV) // 2 == WDEFL > 128
+    _check_pairs(WLAT, False, wide["B"], WNEV)
+
+
+def test_deflated_solves_with_more_than_128_vectors(wide):
+    """what test_deflated_solve_against_numpy_cg and test_even_batch_against_the_single_deflated_solve (test_gpu_defl_batch.py)
+    assert at nev = 16, at nev = 129: block dot and block axpy in two chunks, single and for four right-hand sides"""
+    from oracle import oracle as o
+
+    ctx, B, bs, vh = wide["ctx"], wide["B"], wide["bs"], wide["vh"]
+    V = np.stack([R.cvec(B.vector(i), vh) for i in range(WDEFL)], axis=1)
+    orth = np.abs(V.conj().T @ V - np.eye(WDEFL)).max()
+    print("the %d leading vectors: |V^+ V - 1| %.2e" % (WDEFL, orth))
+    assert orth <= 1e-12
+    bid, xid = [ctx.field_new(v) for v in bs], [ctx.field_new() for _ in bs]
+    one = ctx.field_new()
+    its0, _, _ = ctx.dev_solve_xx(one, bid[0], MASS, R2REQ, 5000)
+    its1, r1 = ctx.dev_solve_xx_deflated(B, WDEFL, one, bid[0], MASS, R2REQ, 5000)
+    xf = ctx.field_download(one)
+    rr = R.cvec(bs[0], vh) - R.cvec(o.stagD2xx(wide["lo"], wide["g"], None, xf, MASS * MASS, True), vh)
+    r2o = np.vdot(rr, rr).real / np.vdot(R.cvec(bs[0], vh), R.cvec(bs[0], vh)).real
+    print("plain %d its, deflated with %d vectors %d its, ratio %.3f; r2/b2 %.6e (oracle %.6e)" % (its0, WDEFL, its1, its1 / its0, r1, r2o))
+    assert its1 <= 0.75 * its0
+    assert r1 <= R2REQ * (1 + 1e-3)
+    assert abs(r2o / r1 - 1) <= 1e-6
+    ms = [0.01, 0.01, 0.02, 0.05]
+    its, r2, nup = ctx.dev_solve_xx_batch_deflated(B, WDEFL, xid, bid, ms, R2REQ, 5000)
+    for k in range(4):
+        xk = ctx.field_download(xid[k])
+        i1, rk = ctx.dev_solve_xx_deflated(B, WDEFL, one, bid[k], ms[k], R2REQ, 5000)
+        x1 = ctx.field_download(one)
+        eq = np.array_equal(xk, x1)
+        rel = np.linalg.norm(xk - x1) / np.linalg.norm(x1)
+        print("system %d (m = %g): batch %d its r2/b2 %.4e, single %d its r2/b2 %.4e, x %s" %
+              (k, ms[k], its[k], r2[k], i1, rk, "bit-identical" if eq else "relerr %.2e" % rel))
+        assert eq or rel < 1e-13
+        assert abs(its[k] - i1) <= 1
+        assert r2[k] <= R2REQ * (1 + 1e-3)
+    assert nup == [0, 0, 0, 0]
+    for f in bid + xid + [one]:
+        ctx.field_free(f)
 
 
 # ---------------------------------------------------------------- deflated solve
