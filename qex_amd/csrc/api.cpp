@@ -406,39 +406,34 @@ extern "C" int qexhip_stag_outer(qexhip_handle c, double *f, const double *x, do
 }
 
 // ---- solvers ----
+// Host staging of the single-system entries: b into WK_IN; the solution is WK_OUT, holding the caller's x where the solve starts from it
+static int stage_in(qexhip_ctx *c, double *x, const double *b, int use_prev, DevField **fx, DevField **fb) {
+  if (!c || !x || !b) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  CHK(host_in(c, WK_IN, b, fb));
+  return use_prev ? host_in(c, WK_OUT, x, fx) : get_work(c, WK_OUT, fx);
+}
+
 extern "C" int qexhip_stag_solve_xx(qexhip_handle c, double *x, const double *b, double mass, double r2req,
                                     int maxits, int par_even, int *iters, double *r2_over_b2, double *hist,
                                     int histcap) {
-  if (!c || !x || !b) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
   DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  CHK(get_work(c, WK_OUT, &fx));
+  CHK(stage_in(c, x, b, 0, &fx, &fb));
   CHK(solve_xx_dev(c, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, hist, histcap));
-  return field_download(c, *fx, x);
-}
-
-extern "C" int qexhip_stag_solve(qexhip_handle c, double *x, const double *b, double mass, double r2req,
-                                 int maxits, int *iters, double *r2_final) {
-  if (!c || !x || !b) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  CHK(get_work(c, WK_OUT, &fx));
-  CHK(solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final));
   return field_download(c, *fx, x);
 }
 
 extern "C" int qexhip_stag_solve_prev(qexhip_handle c, double *x, const double *b, double mass, double r2req,
                                       int maxits, int use_prev, int *iters, double *r2_final) {
-  if (!c || !x || !b) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
   DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  if (use_prev) CHK(host_in(c, WK_OUT, x, &fx));
-  else CHK(get_work(c, WK_OUT, &fx));
+  CHK(stage_in(c, x, b, use_prev, &fx, &fb));
   CHK(solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, use_prev));
   return field_download(c, *fx, x);
+}
+
+extern "C" int qexhip_stag_solve(qexhip_handle c, double *x, const double *b, double mass, double r2req,
+                                 int maxits, int *iters, double *r2_final) {
+  return qexhip_stag_solve_prev(c, x, b, mass, r2req, maxits, 0, iters, r2_final);
 }
 
 static int sloppy_check(qexhip_ctx *c, int sloppy) {
@@ -465,10 +460,8 @@ extern "C" int qexhip_stag_solve_xx_sloppy(qexhip_handle c, double *x, const dou
   CHK(sloppy_check(c, sloppy));
   if (nupdates) *nupdates = 0;
   if (!sloppy) return qexhip_stag_solve_xx(c, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nullptr, 0);
-  HIPCHK(hipSetDevice(c->device));
   DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  CHK(get_work(c, WK_OUT, &fx));
+  CHK(stage_in(c, x, b, 0, &fx, &fb));
   sloppy_last_reset(c);
   CHK(solve_xx_sloppy_any(c, sloppy, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates));
   return field_download(c, *fx, x);
@@ -480,27 +473,28 @@ extern "C" int qexhip_stag_solve_sloppy(qexhip_handle c, double *x, const double
   CHK(sloppy_check(c, sloppy));
   if (nupdates) *nupdates = 0;
   if (!sloppy) return qexhip_stag_solve_prev(c, x, b, mass, r2req, maxits, use_prev, iters, r2_final);
-  HIPCHK(hipSetDevice(c->device));
   DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  if (use_prev) CHK(host_in(c, WK_OUT, x, &fx));
-  else CHK(get_work(c, WK_OUT, &fx));
+  CHK(stage_in(c, x, b, use_prev, &fx, &fb));
   sloppy_last_reset(c);
   CHK(solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, use_prev, sloppy, nupdates));
   return field_download(c, *fx, x);
 }
 
-static int multi_common(qexhip_ctx *c, double *const *xs, const double *b, const double *vals, int nmass,
-                        double r2req, int maxits, int par_even, int full, int *iters, double *out, double *hist,
-                        int histcap) {
+// Host staging of the multi-shift entries: b into WK_IN, the solutions in the persistent pool (nothing to free on any path), one of
+// the three solvers -- full: Staggered.solve(xs, ...), out = r2_final; else solveXX on one parity, in fp64 (hist) or mixed precision
+// (out = r2_over_b2[nmass], refine_iters) -- and the solutions down
+static int multi_host(qexhip_ctx *c, double *const *xs, const double *b, const double *vals, int nmass, double r2req, int maxits,
+                      int par_even, int full, int sloppy, int *iters, double *out, double *hist, int histcap, int *nupdates,
+                      int *refine_iters) {
   if (!c || !xs || !b || !vals || nmass < 1) return QEXHIP_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
   DevField *fb;
   CHK(host_in(c, WK_IN, b, &fb));
   if (nmass > 32) { qexhip_set_error("multishift: nmass <= 32"); return QEXHIP_ERR_ARG; }
   std::vector<DevField *> xp(nmass);
-  for (int k = 0; k < nmass; k++) CHK(pool_field(c, POOL_XS + k, &xp[k]));   // persistent: nothing to free on any path
-  if (full) CHK(solve_multi_dev(c, xp, *fb, vals, nmass, r2req, maxits, iters, out));
+  for (int k = 0; k < nmass; k++) CHK(pool_field(c, POOL_XS + k, &xp[k]));
+  if (full) CHK(solve_multi_dev(c, xp, *fb, vals, nmass, r2req, maxits, iters, out, sloppy, nupdates));
+  else if (sloppy) CHK(solve_xx_multi_sloppy_dev(c, xp, *fb, vals, nmass, r2req, maxits, par_even, iters, out, nupdates, refine_iters));
   else CHK(solve_xx_multi_dev(c, xp, *fb, vals, nmass, r2req, maxits, par_even, iters, hist, histcap));
   for (int k = 0; k < nmass; k++) CHK(field_download(c, *xp[k], xs[k]));
   return 0;
@@ -509,11 +503,11 @@ static int multi_common(qexhip_ctx *c, double *const *xs, const double *b, const
 extern "C" int qexhip_stag_solve_xx_multi(qexhip_handle c, double *const *xs, const double *b, const double *shifts,
                                           int nmass, double r2req, int maxits, int par_even, int *iters,
                                           double *hist, int histcap) {
-  return multi_common(c, xs, b, shifts, nmass, r2req, maxits, par_even, 0, iters, nullptr, hist, histcap);
+  return multi_host(c, xs, b, shifts, nmass, r2req, maxits, par_even, 0, 0, iters, nullptr, hist, histcap, nullptr, nullptr);
 }
 extern "C" int qexhip_stag_solve_multi(qexhip_handle c, double *const *xs, const double *b, const double *masses,
                                        int nmass, double r2req, int maxits, int *iters, double *r2_final) {
-  return multi_common(c, xs, b, masses, nmass, r2req, maxits, 1, 1, iters, r2_final, nullptr, 0);
+  return multi_host(c, xs, b, masses, nmass, r2req, maxits, 1, 1, 0, iters, r2_final, nullptr, 0, nullptr, nullptr);
 }
 
 // Mixed-precision multi-shift solves.  sloppy = 0 IS the fp64 entry (nupdates = 0, refine_iters all 0); r2_over_b2[k] then is not
@@ -525,33 +519,15 @@ extern "C" int qexhip_stag_solve_xx_multi_sloppy(qexhip_handle c, double *const 
   CHK(multi_sloppy_check(c, sloppy, shifts, nmass));
   if (nupdates) *nupdates = 0;
   if (refine_iters) for (int k = 0; k < nmass; k++) refine_iters[k] = 0;
-  if (!sloppy) {
-    if (r2_over_b2) for (int k = 0; k < nmass; k++) r2_over_b2[k] = -1.0;
-    return qexhip_stag_solve_xx_multi(c, xs, b, shifts, nmass, r2req, maxits, par_even, iters, nullptr, 0);
-  }
-  HIPCHK(hipSetDevice(c->device));
-  DevField *fb;
-  CHK(host_in(c, WK_IN, b, &fb));
-  std::vector<DevField *> xp(nmass);
-  for (int k = 0; k < nmass; k++) CHK(pool_field(c, POOL_XS + k, &xp[k]));
-  CHK(solve_xx_multi_sloppy_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, r2_over_b2, nupdates, refine_iters));
-  for (int k = 0; k < nmass; k++) CHK(field_download(c, *xp[k], xs[k]));
-  return 0;
+  if (!sloppy && r2_over_b2) for (int k = 0; k < nmass; k++) r2_over_b2[k] = -1.0;
+  return multi_host(c, xs, b, shifts, nmass, r2req, maxits, par_even, 0, sloppy, iters, r2_over_b2, nullptr, 0, nupdates, refine_iters);
 }
 extern "C" int qexhip_stag_solve_multi_sloppy(qexhip_handle c, double *const *xs, const double *b, const double *masses, int nmass,
                                               double r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates) {
   if (!c || !xs || !b || !masses) return QEXHIP_ERR_ARG;
   CHK(multi_sloppy_check(c, sloppy, masses, nmass));
   if (nupdates) *nupdates = 0;
-  if (!sloppy) return qexhip_stag_solve_multi(c, xs, b, masses, nmass, r2req, maxits, iters, r2_final);
-  HIPCHK(hipSetDevice(c->device));
-  DevField *fb;
-  CHK(host_in(c, WK_IN, b, &fb));
-  std::vector<DevField *> xp(nmass);
-  for (int k = 0; k < nmass; k++) CHK(pool_field(c, POOL_XS + k, &xp[k]));
-  CHK(solve_multi_dev(c, xp, *fb, masses, nmass, r2req, maxits, iters, r2_final, sloppy, nupdates));
-  for (int k = 0; k < nmass; k++) CHK(field_download(c, *xp[k], xs[k]));
-  return 0;
+  return multi_host(c, xs, b, masses, nmass, r2req, maxits, 1, 1, sloppy, iters, r2_final, nullptr, 0, nupdates, nullptr);
 }
 
 // ---- field algebra hooks ----
@@ -605,6 +581,40 @@ static int find_field(qexhip_ctx *c, int id, DevField **f) {
   auto it = c->fields.find(id);
   if (id <= 0 || it == c->fields.end()) { qexhip_set_error("unknown field id %d", id); return QEXHIP_ERR_ARG; }
   *f = &it->second;
+  return 0;
+}
+// The resident fields of one solve: the solutions x_ids[0..n), then the source.  The solvers zero every solution before they form
+// |b|^2, so a solution that is the source, or another solution, would silently give b2 = 0 / one field holding the last shift
+// only: refused under the entry's name `who` (by_index: the multi-shift entries, whose messages name the position in x_ids)
+static int find_solve_fields(qexhip_ctx *c, const char *who, bool by_index, int n, const int *x_ids, int b_id, DevField **fx, DevField **fb) {
+  for (int k = 0; k < n; k++) CHK(find_field(c, x_ids[k], &fx[k]));
+  CHK(find_field(c, b_id, fb));
+  for (int k = 0; k < n; k++) {
+    if (x_ids[k] == b_id) {
+      if (by_index) qexhip_set_error("%s: x_ids[%d] is the source field", who, k);
+      else qexhip_set_error("%s: the solution field is the source field", who);
+      return QEXHIP_ERR_ARG;
+    }
+    for (int j = 0; j < k; j++)
+      if (x_ids[j] == x_ids[k]) { qexhip_set_error("%s: x_ids[%d] == x_ids[%d]", who, j, k); return QEXHIP_ERR_ARG; }
+  }
+  return 0;
+}
+// The resident fields of a call of lock-step batches.  Every solution is zeroed while its system is set up, in order: a solution
+// field that is also a source (of ANY system of the call) or another system's solution would be destroyed silently -- such aliases
+// are refused for the whole call
+static int find_batch_fields(qexhip_ctx *c, int n, const int *x_ids, const int *b_ids, DevField **xs, DevField **bs) {
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++)
+      if (x_ids[i] == b_ids[j] || (i != j && x_ids[i] == x_ids[j])) {
+        qexhip_set_error("dev_solve_batch: solution field %d (system %d) aliases %s of system %d", x_ids[i], i,
+                         x_ids[i] == b_ids[j] ? "the source" : "the solution", j);
+        return QEXHIP_ERR_ARG;
+      }
+  for (int j = 0; j < n; j++) {
+    CHK(find_field(c, x_ids[j], &xs[j]));
+    CHK(find_field(c, b_ids[j], &bs[j]));
+  }
   return 0;
 }
 extern "C" int qexhip_field_new(qexhip_handle c, int *id) {
@@ -682,9 +692,7 @@ extern "C" int qexhip_dev_solve_xx_sloppy(qexhip_handle c, int x_id, int b_id, d
   if (!sloppy) return qexhip_dev_solve_xx(c, x_id, b_id, mass, r2req, maxits, par_even, iters, r2_over_b2, nullptr, 0);
   HIPCHK(hipSetDevice(c->device));
   DevField *fx, *fb;
-  CHK(find_field(c, x_id, &fx));
-  CHK(find_field(c, b_id, &fb));
-  if (x_id == b_id) { qexhip_set_error("dev_solve_xx_sloppy: the solution field is the source field"); return QEXHIP_ERR_ARG; }
+  CHK(find_solve_fields(c, "dev_solve_xx_sloppy", false, 1, &x_id, b_id, &fx, &fb));
   sloppy_last_reset(c);
   return solve_xx_sloppy_any(c, sloppy, *fx, *fb, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
 }
@@ -772,16 +780,8 @@ extern "C" int qexhip_dev_solve_xx_multi(qexhip_handle c, const int *x_ids, int 
                                          double r2req, int maxits, int par_even, int *iters, double *hist, int histcap) {
   if (!c || !x_ids || !shifts || nmass < 1 || nmass > 32) return QEXHIP_ERR_ARG;
   DevField *fb;
-  CHK(find_field(c, b_id, &fb));
   std::vector<DevField *> xp(nmass);
-  for (int k = 0; k < nmass; k++) {
-    CHK(find_field(c, x_ids[k], &xp[k]));
-    // the solver zeroes every xs[k] before it forms |b|^2: a solution field that is the source, or another solution, would
-    // silently give b2 = 0 / one field holding the last shift only
-    if (x_ids[k] == b_id) { qexhip_set_error("dev_solve_xx_multi: x_ids[%d] is the source field", k); return QEXHIP_ERR_ARG; }
-    for (int j = 0; j < k; j++)
-      if (x_ids[j] == x_ids[k]) { qexhip_set_error("dev_solve_xx_multi: x_ids[%d] == x_ids[%d]", j, k); return QEXHIP_ERR_ARG; }
-  }
+  CHK(find_solve_fields(c, "dev_solve_xx_multi", true, nmass, x_ids, b_id, xp.data(), &fb));
   return solve_xx_multi_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, hist, histcap);
 }
 // qexhip_stag_solve_xx_multi_sloppy on resident fields
@@ -798,14 +798,8 @@ extern "C" int qexhip_dev_solve_xx_multi_sloppy(qexhip_handle c, const int *x_id
   }
   HIPCHK(hipSetDevice(c->device));
   DevField *fb;
-  CHK(find_field(c, b_id, &fb));
   std::vector<DevField *> xp(nmass);
-  for (int k = 0; k < nmass; k++) {
-    CHK(find_field(c, x_ids[k], &xp[k]));
-    if (x_ids[k] == b_id) { qexhip_set_error("dev_solve_xx_multi_sloppy: x_ids[%d] is the source field", k); return QEXHIP_ERR_ARG; }
-    for (int j = 0; j < k; j++)
-      if (x_ids[j] == x_ids[k]) { qexhip_set_error("dev_solve_xx_multi_sloppy: x_ids[%d] == x_ids[%d]", j, k); return QEXHIP_ERR_ARG; }
-  }
+  CHK(find_solve_fields(c, "dev_solve_xx_multi_sloppy", true, nmass, x_ids, b_id, xp.data(), &fb));
   return solve_xx_multi_sloppy_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, r2_over_b2, nupdates, refine_iters);
 }
 
@@ -970,9 +964,7 @@ extern "C" int qexhip_dev_solve_xx_deflated(qexhip_handle c, int basis, int nev,
   EigBasis *B;
   CHK(deflate_args(c, basis, nev, sloppy, mass, &B));
   DevField *fx, *fb;
-  CHK(find_field(c, x_id, &fx));
-  CHK(find_field(c, b_id, &fb));
-  if (x_id == b_id) { qexhip_set_error("dev_solve_xx_deflated: the solution field is the source field"); return QEXHIP_ERR_ARG; }
+  CHK(find_solve_fields(c, "dev_solve_xx_deflated", false, 1, &x_id, b_id, &fx, &fb));
   HIPCHK(hipSetDevice(c->device));
   sloppy_last_reset(c);
   return solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy, iters, r2_over_b2);
@@ -982,10 +974,8 @@ extern "C" int qexhip_stag_solve_xx_deflated(qexhip_handle c, int basis, int nev
   if (!c || !x || !b) return QEXHIP_ERR_ARG;
   EigBasis *B;
   CHK(deflate_args(c, basis, nev, sloppy, mass, &B));
-  HIPCHK(hipSetDevice(c->device));
   DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  CHK(get_work(c, WK_OUT, &fx));
+  CHK(stage_in(c, x, b, 0, &fx, &fb));
   sloppy_last_reset(c);
   CHK(solve_xx_deflated_dev(c, *B, nev, *fx, *fb, mass, r2req, maxits, sloppy, iters, r2_over_b2));
   return field_download(c, *fx, x);
@@ -996,10 +986,8 @@ extern "C" int qexhip_stag_solve_deflated(qexhip_handle c, int basis, int nev, d
   EigBasis *B;
   CHK(deflate_args(c, basis, nev, sloppy, mass, &B));
   if (B->gen != c->links_gen) { qexhip_set_error("deflated solve: the basis was computed on other links"); return QEXHIP_ERR_STATE; }
-  HIPCHK(hipSetDevice(c->device));
   DevField *fb, *fx;
-  CHK(host_in(c, WK_IN, b, &fb));
-  CHK(get_work(c, WK_OUT, &fx));
+  CHK(stage_in(c, x, b, 0, &fx, &fb));
   c->deflate_basis = basis; c->deflate_nev = nev;
   sloppy_last_reset(c);
   const int rc = solve_full_dev(c, *fx, *fb, mass, r2req, maxits, iters, r2_final, 0, sloppy, nullptr);
@@ -1241,17 +1229,34 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
   else { qexhip_set_error("unknown option"); return QEXHIP_ERR_ARG; }
   return 0;
 }
+// Host staging of the lock-step batches, after the entry's own checks: the sources up into the batch state's io fields, ONE batch --
+// xx_parity >= 0: solveXX on that parity, else the full solve; in fp64, mixed precision (sloppy > 0) or deflated from basis B (either
+// precision) -- and the solutions down.  The sloppy and the deflated entries start a new report for qexhip_stag_sloppy_last_batch.
+static int solve_batch_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass, const double *r2req,
+                            int maxits, int xx_parity, int sloppy, EigBasis *B, int nev, int *iters, double *r2, int *nupdates) {
+  HIPCHK(hipSetDevice(c->device));
+  if (sloppy && !B) CHK(batch_sloppy_check(c, n, mass));     // (deflate_batch_args has made it for a deflated batch)
+  DevField *xs[QX_MAXRHS], *bs[QX_MAXRHS];
+  CHK(batch_io_fields(c, n, xs, bs));
+  for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
+  if (sloppy || B) slpb_last_reset(c, n);
+  if (B && xx_parity >= 0) CHK(solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, xx_parity, sloppy, iters, r2, nupdates));
+  else if (B) CHK(solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
+  else if (xx_parity < 0) CHK(solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
+  else if (sloppy) CHK(solve_xx_batch_sloppy_any(c, sloppy, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2, nupdates));
+  else CHK(solve_xx_batch_dev(c, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2));
+  for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
+  return 0;
+}
 extern "C" int qexhip_stag_solve_xx_batch(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
                                           const double *r2req, int maxits, int par_even, int *iters, double *r2_over_b2) {
   if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  return solve_batch_host(c, n, x, b, mass, r2req, maxits, par_even ? 1 : 0, iters, r2_over_b2);
+  return solve_batch_host(c, n, x, b, mass, r2req, maxits, par_even ? 1 : 0, 0, nullptr, 0, iters, r2_over_b2, nullptr);
 }
 extern "C" int qexhip_stag_solve_batch(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
                                        const double *r2req, int maxits, int *iters, double *r2_over_b2) {
   if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  return solve_batch_host(c, n, x, b, mass, r2req, maxits, -1, iters, r2_over_b2);
+  return solve_batch_host(c, n, x, b, mass, r2req, maxits, -1, 0, nullptr, 0, iters, r2_over_b2, nullptr);
 }
 // Mixed-precision lock-step batches.  sloppy = 0 IS the fp64 entry; the batched fp32 form is one-rank only (batch_sloppy_check).
 extern "C" int qexhip_stag_solve_xx_batch_sloppy(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
@@ -1261,9 +1266,7 @@ extern "C" int qexhip_stag_solve_xx_batch_sloppy(qexhip_handle c, int n, double 
   CHK(sloppy_check(c, sloppy));
   if (n < 1 || n > 4) { qexhip_set_error("batch solve: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
   if (nupdates) for (int j = 0; j < n; j++) nupdates[j] = 0;
-  if (!sloppy) return qexhip_stag_solve_xx_batch(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2);
-  HIPCHK(hipSetDevice(c->device));
-  return solve_batch_sloppy_host(c, n, x, b, mass, r2req, maxits, par_even ? 1 : 0, sloppy, iters, r2_over_b2, nupdates);
+  return solve_batch_host(c, n, x, b, mass, r2req, maxits, par_even ? 1 : 0, sloppy, nullptr, 0, iters, r2_over_b2, nupdates);
 }
 extern "C" int qexhip_stag_solve_batch_sloppy(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
                                               const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates) {
@@ -1271,9 +1274,7 @@ extern "C" int qexhip_stag_solve_batch_sloppy(qexhip_handle c, int n, double *co
   CHK(sloppy_check(c, sloppy));
   if (n < 1 || n > 4) { qexhip_set_error("batch solve: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
   if (nupdates) for (int j = 0; j < n; j++) nupdates[j] = 0;
-  if (!sloppy) return qexhip_stag_solve_batch(c, n, x, b, mass, r2req, maxits, iters, r2_final);
-  HIPCHK(hipSetDevice(c->device));
-  return solve_batch_sloppy_host(c, n, x, b, mass, r2req, maxits, -1, sloppy, iters, r2_final, nupdates);
+  return solve_batch_host(c, n, x, b, mass, r2req, maxits, -1, sloppy, nullptr, 0, iters, r2_final, nupdates);
 }
 extern "C" int qexhip_stag_links_info(qexhip_handle c, int *nlinks, int *compressed, double *max_dev) {
   if (!c) return QEXHIP_ERR_ARG;
@@ -1465,32 +1466,15 @@ extern "C" int qexhip_dev_zero(qexhip_handle c, int id, int parity) {
   CHK(find_field(c, id, &f));
   return blas_zero(c, *f, parity);
 }
-// every solution is zeroed while its system is set up, in order: a solution field that is also a source (of ANY system of
-// the call) or another system's solution would be destroyed silently -- refuse such aliases for the whole call
-static int batch_alias_check(int n, const int *x_ids, const int *b_ids) {
-  for (int i = 0; i < n; i++)
-    for (int j = 0; j < n; j++)
-      if (x_ids[i] == b_ids[j] || (i != j && x_ids[i] == x_ids[j])) {
-        qexhip_set_error("dev_solve_batch: solution field %d (system %d) aliases %s of system %d", x_ids[i], i,
-                         x_ids[i] == b_ids[j] ? "the source" : "the solution", j);
-        return QEXHIP_ERR_ARG;
-      }
-  return 0;
-}
 extern "C" int qexhip_dev_solve_batch(qexhip_handle c, int n, const int *x_ids, const int *b_ids, const double *mass,
                                       const double *r2req, int maxits, int *iters, double *r2) {
   if (!c || !x_ids || !b_ids || !mass || !r2req || n < 1 || n > 64) return QEXHIP_ERR_ARG;
   HIPCHK(hipSetDevice(c->device));
-  CHK(batch_alias_check(n, x_ids, b_ids));
-  for (int k0 = 0; k0 < n; k0 += 4) {          // lock-step batches of four, as qexhip_stag_solve_batch
-    const int k = std::min(4, n - k0);
-    DevField *xs[4], *bs[4];
-    for (int j = 0; j < k; j++) {
-      CHK(find_field(c, x_ids[k0 + j], &xs[j]));
-      CHK(find_field(c, b_ids[k0 + j], &bs[j]));
-    }
-    CHK(solve_full_batch_dev(c, k, xs, bs, mass + k0, r2req + k0, maxits, iters ? iters + k0 : nullptr, r2 ? r2 + k0 : nullptr));
-  }
+  DevField *xs[64], *bs[64];
+  CHK(find_batch_fields(c, n, x_ids, b_ids, xs, bs));
+  for (int k0 = 0; k0 < n; k0 += 4)            // lock-step batches of four, as qexhip_stag_solve_batch
+    CHK(solve_full_batch_dev(c, std::min(4, n - k0), xs + k0, bs + k0, mass + k0, r2req + k0, maxits, iters ? iters + k0 : nullptr,
+                             r2 ? r2 + k0 : nullptr));
   return 0;
 }
 // qexhip_stag_solve_batch_sloppy on resident fields: ONE lock-step batch (n <= 4)
@@ -1503,12 +1487,8 @@ extern "C" int qexhip_dev_solve_batch_sloppy(qexhip_handle c, int n, const int *
   if (!sloppy) return qexhip_dev_solve_batch(c, n, x_ids, b_ids, mass, r2req, maxits, iters, r2);
   HIPCHK(hipSetDevice(c->device));
   CHK(batch_sloppy_check(c, n, mass));
-  CHK(batch_alias_check(n, x_ids, b_ids));
   DevField *xs[4], *bs[4];
-  for (int j = 0; j < n; j++) {
-    CHK(find_field(c, x_ids[j], &xs[j]));
-    CHK(find_field(c, b_ids[j], &bs[j]));
-  }
+  CHK(find_batch_fields(c, n, x_ids, b_ids, xs, bs));
   slpb_last_reset(c, n);
   return solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates);
 }
@@ -1528,12 +1508,8 @@ extern "C" int qexhip_dev_solve_xx_batch_deflated(qexhip_handle c, int basis, in
   if (!c || !x_ids || !b_ids || !mass || !r2req) return QEXHIP_ERR_ARG;
   EigBasis *B;
   CHK(deflate_batch_args(c, basis, nev, n, mass, sloppy, &B));
-  CHK(batch_alias_check(n, x_ids, b_ids));
   DevField *xs[4], *bs[4];
-  for (int j = 0; j < n; j++) {
-    CHK(find_field(c, x_ids[j], &xs[j]));
-    CHK(find_field(c, b_ids[j], &bs[j]));
-  }
+  CHK(find_batch_fields(c, n, x_ids, b_ids, xs, bs));
   HIPCHK(hipSetDevice(c->device));
   slpb_last_reset(c, n);
   return solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, par_even ? 1 : 0, sloppy, iters, r2_over_b2, nupdates);
@@ -1544,31 +1520,20 @@ extern "C" int qexhip_dev_solve_batch_deflated(qexhip_handle c, int basis, int n
   if (!c || !x_ids || !b_ids || !mass || !r2req) return QEXHIP_ERR_ARG;
   EigBasis *B;
   CHK(deflate_batch_args(c, basis, nev, n, mass, sloppy, &B));
-  CHK(batch_alias_check(n, x_ids, b_ids));
   DevField *xs[4], *bs[4];
-  for (int j = 0; j < n; j++) {
-    CHK(find_field(c, x_ids[j], &xs[j]));
-    CHK(find_field(c, b_ids[j], &bs[j]));
-  }
+  CHK(find_batch_fields(c, n, x_ids, b_ids, xs, bs));
   HIPCHK(hipSetDevice(c->device));
   slpb_last_reset(c, n);
   return solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2_final, nupdates);
 }
+// the host-field forms: every check of the resident ones, and no null field, before the first upload
 static int solve_batch_deflated_host(qexhip_ctx *c, int basis, int nev, int n, double *const *x, const double *const *b, const double *mass,
                                      const double *r2req, int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates) {
   if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
   EigBasis *B;
   CHK(deflate_batch_args(c, basis, nev, n, mass, sloppy, &B));
   for (int j = 0; j < n; j++) if (!x[j] || !b[j]) return QEXHIP_ERR_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  DevField *xs[4], *bs[4];
-  CHK(batch_io_fields(c, n, xs, bs));
-  for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
-  slpb_last_reset(c, n);
-  if (xx_parity >= 0) CHK(solve_xx_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, xx_parity, sloppy, iters, r2, nupdates));
-  else CHK(solve_full_batch_deflated_dev(c, *B, nev, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
-  for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
-  return 0;
+  return solve_batch_host(c, n, x, b, mass, r2req, maxits, xx_parity, sloppy, B, nev, iters, r2, nupdates);
 }
 extern "C" int qexhip_stag_solve_xx_batch_deflated(qexhip_handle c, int basis, int nev, int n, double *const *x, const double *const *b,
                                                    const double *mass, const double *r2req, int maxits, int par_even, int sloppy,

@@ -17,6 +17,7 @@
 #include "reduce.h"
 #include "dslash_core.h"
 #include "fused_sweep.h"
+#include "full_solve.h"
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -528,24 +529,16 @@ int solve_xx_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const d
 }
 
 // ---- n full solves D x_j = b_j (Staggered.solve, stagSolve.nim:224-294) with the even/odd CGs batched ----
-// Same decisions per system as solve_full_dev / solve_inner (solver.cpp): reconstruct-right for one-parity
-// sources (the HMC case: phi.odd = 0), reconstruct-left otherwise, true-residual outer loop.
+// Per system the decisions of solve_full_dev / solve_inner (solver.cpp), from the same eo_plan (full_solve.h): reconstruct-right
+// for one-parity sources (the HMC case: phi.odd = 0), reconstruct-left otherwise, true-residual outer loop.
 namespace {
 struct Sys {
   DevField *x, *b, *r, *y, *d;    // solution, source, residual, inner solution, inner source / work
   double m, r2req, b2, r2stop, r2e, r2o;
-  int its, n, kind, par;          // kind 0: ReconR, 1: ReconL
-  double rr;
+  int its, n;
+  EoPlan pl;
   DevField *src;
 };
-int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
-  CHK(blas_norm2(c, f, 0, &c->dscal[2]));
-  CHK(blas_norm2(c, f, 1, &c->dscal[3]));
-  double h[2];
-  CHK(read_scalars(c, &c->dscal[2], 2, h));
-  *e = h[0]; *o = h[1];
-  return 0;
-}
 }  // namespace
 
 // sloppy > 0: the inner solveXX's are the mixed-precision lock-step batch (batch_f32.hip), nupdates[j] <- system j's reliable updates
@@ -577,22 +570,16 @@ static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **
     for (int j : active) {
       Sys &s = S[j];
       const double r2 = s.r2e + s.r2o, rq = s.r2stop / r2;
-      const double stop = rq * r2, stop2 = 0.5 * stop;
-      const double stope = (s.r2o <= stop2) ? stop - s.r2o : stop2;
-      const double stopo = (s.r2e <= stop2) ? stop - s.r2e : stop2;
+      s.pl = eo_plan(rq * r2, s.r2e, s.r2o, s.m);
       s.n = 0;
-      if (s.r2e <= stope || s.r2o <= stopo) {
-        s.kind = 0; s.src = s.r;
-        if (s.r2e > stope) { s.par = 1; s.rr = stope / s.r2e; }
-        else if (s.r2o > stopo) { s.par = 0; s.rr = stopo / s.r2o; }
-        else s.par = -1;                                      // nothing to do
-      } else {
-        s.kind = 1; s.par = 1; s.src = s.d;
+      s.src = s.r;
+      if (s.pl.kind == EO_LEFT) {
+        s.src = s.d;
         CHK(op_D(c, *s.d, *s.r, s.m, -1.0));
         CHK(blas_norm2(c, *s.d, 0, &c->dscal[2]));
         double d2e;
         CHK(read_scalars(c, &c->dscal[2], 1, &d2e));
-        s.rr = 0.99 * rq * r2 * s.m * s.m / d2e;
+        s.pl.rr = eo_left_target(rq, r2, s.m, d2e);
       }
     }
     for (int par = 1; par >= 0; par--) {
@@ -600,8 +587,8 @@ static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **
       double ms[QX_MAXRHS], rrs[QX_MAXRHS];
       int idx[QX_MAXRHS], its[QX_MAXRHS], nup[QX_MAXRHS] = {0, 0, 0, 0}, k = 0, mx = 0;
       for (int j : active)
-        if (S[j].par == par) {
-          xs[k] = S[j].y; bs[k] = S[j].src; ms[k] = S[j].m; rrs[k] = S[j].rr; idx[k] = j;
+        if (S[j].pl.par == par) {
+          xs[k] = S[j].y; bs[k] = S[j].src; ms[k] = S[j].m; rrs[k] = S[j].pl.rr; idx[k] = j;
           mx = std::max(mx, maxits - S[j].its);
           k++;
         }
@@ -625,9 +612,9 @@ static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **
     std::vector<int> next;
     for (int j : active) {
       Sys &s = S[j];
-      if (s.par >= 0) {
-        if (s.kind == 0) {
-          CHK(blas_scale(c, 4.0, *s.y, s.par ? 0 : 1));
+      if (s.pl.par >= 0) {
+        if (s.pl.kind == EO_RIGHT) {
+          CHK(blas_scale(c, 4.0, *s.y, s.pl.par ? 0 : 1));
           CHK(blas_copy(c, *s.d, *s.y, 2));
           CHK(op_D(c, *s.y, *s.d, s.m, -1.0));
         } else {
@@ -639,10 +626,8 @@ static int solve_full_batch_impl(qexhip_ctx *c, int n, DevField **x, DevField **
       }
       s.its += s.n;
       CHK(blas_axpy(c, 1.0, *s.y, *s.x, 2));
-      CHK(op_D(c, *s.r, *s.x, s.m, 1.0));
-      CHK(blas_axpby(c, 1.0, *s.b, -1.0, *s.r, *s.r, 2));
-      CHK(norm2_eo(c, *s.r, &s.r2e, &s.r2o));
-      if (s.r2e + s.r2o > s.r2stop && s.its < maxits && s.par >= 0) next.push_back(j);
+      CHK(resid_eo(c, *s.r, *s.b, *s.x, s.m, &s.r2e, &s.r2o));
+      if (s.r2e + s.r2o > s.r2stop && s.its < maxits && s.pl.par >= 0) next.push_back(j);
     }
     active.swap(next);
   }
@@ -693,18 +678,5 @@ int batch_io_fields(qexhip_ctx *c, int n, DevField **xs, DevField **bs) {
   BatchState *B;
   CHK(batch_state(c, 9 * QX_MAXRHS, &B));        // 4 CG fields + r, y, d + x, b per system
   for (int j = 0; j < n; j++) { xs[j] = &B->f[7 * QX_MAXRHS + 2 * j]; bs[j] = &B->f[7 * QX_MAXRHS + 2 * j + 1]; }
-  return 0;
-}
-
-// host-field entry points
-int solve_batch_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass,
-                     const double *r2req, int maxits, int xx_parity, int *iters, double *r2) {
-  if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
-  DevField *xs[QX_MAXRHS], *bs[QX_MAXRHS];
-  CHK(batch_io_fields(c, n, xs, bs));
-  for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
-  if (xx_parity >= 0) CHK(solve_xx_batch_dev(c, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2));
-  else CHK(solve_full_batch_dev(c, n, xs, bs, mass, r2req, maxits, iters, r2));
-  for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
   return 0;
 }

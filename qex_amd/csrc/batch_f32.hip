@@ -400,17 +400,3 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
   }
   return 0;
 }
-
-// host-field entry points (solve_batch_host with the precision of the inner CG): xx_parity >= 0 solveXX on that parity, else the full solve
-int solve_batch_sloppy_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass, const double *r2req,
-                            int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates) {
-  CHK(batch_sloppy_check(c, n, mass));
-  DevField *xs[QX_MAXRHS], *bs[QX_MAXRHS];
-  CHK(batch_io_fields(c, n, xs, bs));
-  for (int j = 0; j < n; j++) CHK(field_upload(c, *bs[j], b[j]));
-  slpb_last_reset(c, n);
-  if (xx_parity >= 0) CHK(solve_xx_batch_sloppy_any(c, sloppy, n, xs, bs, mass, r2req, maxits, xx_parity, iters, r2, nupdates));
-  else CHK(solve_full_batch_sloppy_dev(c, n, xs, bs, mass, r2req, maxits, sloppy, iters, r2, nupdates));
-  for (int j = 0; j < n; j++) CHK(field_download(c, *xs[j], x[j]));
-  return 0;
-}

@@ -7,6 +7,7 @@
 // every shifted solution and search direction, reading r once.
 #include "qexhip_internal.h"
 #include "reduce.h"
+#include "full_solve.h"
 #include <algorithm>
 #include <cstring>
 
@@ -276,12 +277,10 @@ int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, con
   while (r2 > r2stop) {
     int mx = maxits - its;
     if (mx <= 0) break;
-    double rq = r2stop;
-    const double r2stop2 = 0.5 * rq;
-    const double r2stope = (b2o <= r2stop2) ? rq - b2o : r2stop2;
-    const double r2stopo = (b2e <= r2stop2) ? rq - b2e : r2stop2;
-    int even = 1;
-    if (b2e > r2stope) { rq = r2stope / b2e; even = 1; }
+    double rq = r2stop, r2stope, r2stopo;
+    eo_stops(r2stop, b2e, b2o, &r2stope, &r2stopo);
+    int even = 1;                           // (also where neither parity exceeds its target)
+    if (b2e > r2stope) rq = r2stope / b2e;
     else if (b2o > r2stopo) { rq = r2stopo / b2o; even = 0; }
     int n = 0, nu = 0;
     if (sloppy) CHK(solve_xx_multi_sloppy_dev(c, ys, *r, shifts.data(), nmass, rq, mx, even, &n, nullptr, &nu, nullptr));
@@ -290,12 +289,7 @@ int solve_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, con
     nupd += nu;
     for (int k = 0; k < nmass; k++) CHK(blas_axpy(c, 4.0, *ys[k], *xs[k], even ? 0 : 1));
     CHK(op_D(c, *xt, *xs[0], mass, -1.0));
-    CHK(op_D(c, *r, *xt, mass, 1.0));
-    CHK(blas_axpby(c, 1.0, b, -1.0, *r, *r, 2));
-    CHK(blas_norm2(c, *r, 0, &c->dscal[3]));
-    CHK(blas_norm2(c, *r, 1, &c->dscal[4]));
-    CHK(read_scalars(c, &c->dscal[3], 2, h));
-    b2e = h[0]; b2o = h[1];
+    CHK(resid_eo(c, *r, b, *xt, mass, &b2e, &b2o));
     r2 = b2e + b2o;
   }
   for (int k = 0; k < nmass; k++) {

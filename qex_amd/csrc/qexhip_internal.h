@@ -330,12 +330,8 @@ int solve_xx_batch_sloppy_any(qexhip_ctx *c, int sloppy, int n, DevField **x, De
                               int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
 void slpb_last_reset(qexhip_ctx *c, int n);             // the batched entries start a new report
 int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even);
-int solve_batch_sloppy_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass, const double *r2req,
-                            int maxits, int xx_parity, int sloppy, int *iters, double *r2, int *nupdates);
 int nhyp_fforce(qexhip_ctx *c, double *f_host, int n, const double *const *phi, const double *mass, const double *scale,
                 const double *r2req, int maxits, int bcmask, const int ph[4], int *iters, DevField *const *phi_dev = nullptr);
-int solve_batch_host(qexhip_ctx *c, int n, double *const *x, const double *const *b, const double *mass,
-                     const double *r2req, int maxits, int xx_parity, int *iters, double *r2);
 
 // reductions end in an all-reduce: more than one rank, or the one-rank rehearsal of that code path
 inline bool multi_rank(const qexhip_ctx *c) { return c->nranks > 1 || c->opt_multi_reduce; }
@@ -477,6 +473,9 @@ int cg_resume(qexhip_ctx *c, int k, double r2req, int maxits);   // CgState re-e
 int get_work(qexhip_ctx *c, int slot, DevField **f);
 int op_xx(qexhip_ctx *c, DevField &r, DevField &x, double m2, int par_even, int dot, const int *done, int *ndot = nullptr);
 int op_D(qexhip_ctx *c, DevField &r, DevField &x, double m, double sc, double a = 0.0);
+// the full solves' residual bookkeeping (single, lock-step batch, multi-shift): |f.even|^2 and |f.odd|^2 read back; r = b - D x first
+int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o);
+int resid_eo(qexhip_ctx *c, DevField &r, DevField &b, DevField &x, double m, double *e, double *o);
 int solve_xx_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits,
                  int par_even, int *iters, double *r2_over_b2, double *hist, int histcap);
 int solve_xx_continue_dev(qexhip_ctx *c, DevField &x, double r2req, int maxits, int *iters, double *r2_over_b2, double *hist, int histcap);

@@ -9,6 +9,7 @@
 // All vectors stay in HBM; the CG scalars stay on the device (CgScal) and the host only reads
 // the state back once per chunk of iterations.
 #include "qexhip_internal.h"
+#include "full_solve.h"
 #include "../../include/qexhip.h"
 #include <cmath>
 #include <cstring>
@@ -671,8 +672,8 @@ static int inner_xx(qexhip_ctx *c, DevField &x, DevField &b, double m, double r2
   return 0;
 }
 
-// ---- full solve (stagSolve.nim:141-294) ----
-static int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
+// ---- full solve (stagSolve.nim:141-294); the decisions are full_solve.h's ----
+int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
   CHK(blas_norm2(c, f, 0, &c->dscal[2]));
   CHK(blas_norm2(c, f, 1, &c->dscal[3]));
   double h[2];
@@ -680,37 +681,32 @@ static int norm2_eo(qexhip_ctx *c, DevField &f, double *e, double *o) {
   *e = h[0]; *o = h[1];
   return 0;
 }
+// r = b - D x at mass m with its two parity norms: the true residual every outer loop of a full solve stops on
+int resid_eo(qexhip_ctx *c, DevField &r, DevField &b, DevField &x, double m, double *e, double *o) {
+  CHK(op_D(c, r, x, m, 1.0));
+  CHK(blas_axpby(c, 1.0, b, -1.0, r, r, 2));       // r := b - r
+  return norm2_eo(c, r, e, o);
+}
 
 static int solve_inner(qexhip_ctx *c, DevField &x, DevField &b, double m, double r2req, int maxits,
                        double b2e, double b2o, int *its, int sloppy, int *nupd) {
   const double b2 = b2e + b2o;
-  const double r2stop = r2req * b2, r2stop2 = 0.5 * r2stop;
-  const double r2stope = (b2o <= r2stop2) ? r2stop - b2o : r2stop2;
-  const double r2stopo = (b2e <= r2stop2) ? r2stop - b2e : r2stop2;
+  const EoPlan pl = eo_plan(r2req * b2, b2e, b2o, m);
   *its = 0;
-  if (b2e <= r2stope || b2o <= r2stopo || m == 0.0) {
-    // solveReconR (:141-176)
-    DevField *y;
-    CHK(get_work(c, WK_D, &y));
-    if (b2e > r2stope) {
-      CHK(inner_xx(c, *y, b, m, r2stope / b2e, maxits, 1, its, sloppy, nupd));
-      CHK(blas_scale(c, 4.0, *y, 0));
-      CHK(op_D(c, x, *y, m, -1.0));
-    } else if (b2o > r2stopo) {
-      CHK(inner_xx(c, *y, b, m, r2stopo / b2o, maxits, 0, its, sloppy, nupd));
-      CHK(blas_scale(c, 4.0, *y, 1));
-      CHK(op_D(c, x, *y, m, -1.0));
+  DevField *w;                                      // ReconR: the inner solution y; ReconL: the inner source d
+  CHK(get_work(c, WK_D, &w));
+  if (pl.kind == EO_RIGHT) {
+    if (pl.par >= 0) {
+      CHK(inner_xx(c, *w, b, m, pl.rr, maxits, pl.par, its, sloppy, nupd));
+      CHK(blas_scale(c, 4.0, *w, pl.par ? 0 : 1));
+      CHK(op_D(c, x, *w, m, -1.0));
     }
   } else {
-    // solveReconL (:179-208)
-    DevField *d;
-    CHK(get_work(c, WK_D, &d));
-    CHK(op_D(c, *d, b, m, -1.0));
-    CHK(blas_norm2(c, *d, 0, &c->dscal[2]));
+    CHK(op_D(c, *w, b, m, -1.0));
+    CHK(blas_norm2(c, *w, 0, &c->dscal[2]));
     double d2e;
     CHK(read_scalars(c, &c->dscal[2], 1, &d2e));
-    const double rr = 0.99 * r2req * (b2e + b2o) * m * m / d2e;
-    CHK(inner_xx(c, x, *d, m, rr, maxits, 1, its, sloppy, nupd));
+    CHK(inner_xx(c, x, *w, m, eo_left_target(r2req, b2, m, d2e), maxits, 1, its, sloppy, nupd));
     CHK(blas_scale(c, 4.0, x, 0));
     CHK(op_eo_reconstruct(c, x, b, m));
   }
@@ -726,15 +722,14 @@ int solve_full_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double 
   double b2;
   CHK(read_scalars(c, &c->dscal[2], 1, &b2));
   const double r2stop = r2req * b2;
+  double r2e, r2o;
   if (use_prev) {                                  // sp.usePrevSoln (stagSolve.nim:234-238)
-    CHK(op_D(c, *r, x, mass, 1.0));
-    CHK(blas_axpby(c, 1.0, b, -1.0, *r, *r, 2));
+    CHK(resid_eo(c, *r, b, x, mass, &r2e, &r2o));
   } else {
     CHK(blas_zero(c, x, 2));
     CHK(blas_copy(c, *r, b, 2));
+    CHK(norm2_eo(c, *r, &r2e, &r2o));
   }
-  double r2e, r2o;
-  CHK(norm2_eo(c, *r, &r2e, &r2o));
   double r2 = r2e + r2o;
   int its = 0, nupd = 0;
   while (r2 > r2stop) {
@@ -744,9 +739,7 @@ int solve_full_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double 
     CHK(solve_inner(c, *y, *r, mass, r2stop / r2, mx, r2e, r2o, &n, sloppy, &nupd));
     its += n;
     CHK(blas_axpy(c, 1.0, *y, x, 2));
-    CHK(op_D(c, *r, x, mass, 1.0));
-    CHK(blas_axpby(c, 1.0, b, -1.0, *r, *r, 2));   // r := b - r
-    CHK(norm2_eo(c, *r, &r2e, &r2o));
+    CHK(resid_eo(c, *r, b, x, mass, &r2e, &r2o));
     r2 = r2e + r2o;
   }
   if (iters) *iters = its;

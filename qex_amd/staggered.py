@@ -36,6 +36,11 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ptrs(arrays):
+    """the C array of the fields' addresses (a `double *const *` argument)"""
+    return (C.c_void_p * len(arrays))(*[_p(a).value for a in arrays])
+
+
 class SolverParams:
     """solverBase.nim:10-58 (fields the staggered path uses)."""
 
@@ -692,12 +697,22 @@ class Staggered:
         # (s.g.len*4*72+60)*nEven*iterations  (stagSolve.nim:92)
         return float((self.nlinks * 4 * 72 + 60) * (self.ctx.vol // 2) * its)
 
+    def _record(self, sp, its, r2, seconds, nup=0):
+        """what one finished solve adds to its SolverParams (stagSolve.nim:88-94; nup: reliable updates of a mixed-precision solve)"""
+        sp.calls += 1
+        sp.iterations += its
+        sp.iterationsMax = max(sp.iterationsMax, its)
+        sp.seconds += seconds
+        sp.flops += self._flops(its)
+        sp.r2 = r2
+        sp.reliableUpdates += nup
+
     def solveXX(self, r, x, m, sp, parEven=True, histcap=0, deflate=None, nev=None):
         """solveXX(s, r, x, m, sp0, parEven) (stagSolve.nim:57-132): r <- solution, x = rhs.
         deflate = an EigBasis (even sites only): the deflated solve of hisqev.nim:653-705 with its leading nev vectors (default: the
         pairs Staggered.eigs returned); sp.r2 is then the TRUE residual and no history is kept."""
         t0 = time.time()
-        its, fin = C.c_int(0), C.c_double(0)
+        its, fin, nup = C.c_int(0), C.c_double(0), C.c_int(0)
         hist = np.zeros(max(histcap, 1))
         sloppy = int(getattr(sp, "sloppySolve", SloppyNone))
         if deflate is not None:
@@ -709,20 +724,13 @@ class Staggered:
             histcap = 0
         elif sloppy != SloppyNone:
             # mixed precision (no residual history: the fp32 iterations' residuals are not the true ones)
-            nup = C.c_int(0)
             check(lib().qexhip_stag_solve_xx_sloppy(self.ctx._h, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
                                                     1 if parEven else 0, sloppy, C.byref(its), C.byref(fin), C.byref(nup)))
-            sp.reliableUpdates += nup.value
             histcap = 0
         else:
             check(lib().qexhip_stag_solve_xx(self.ctx._h, _p(r), _p(x), float(m), float(sp.r2req), int(sp.maxits),
                                              1 if parEven else 0, C.byref(its), C.byref(fin), _p(hist), histcap))
-        sp.calls += 1
-        sp.iterations += its.value
-        sp.iterationsMax = max(sp.iterationsMax, its.value)
-        sp.seconds += time.time() - t0
-        sp.flops += self._flops(its.value)
-        sp.r2 = fin.value
+        self._record(sp, its.value, fin.value, time.time() - t0, nup.value)
         sp.r2hist = hist[: min(histcap, its.value + 1)] if histcap else None
         if sp.verbosity > 1:
             print(("solveEE" if parEven else "solveOO") + "(HIP): " + sp.getStats())
@@ -737,13 +745,7 @@ class Staggered:
         t0 = time.time()
         its, fin, nup = self._batch("xx", [r], [x], [m], sp.r2req, sp.maxits, False, int(getattr(sp, "sloppySolve", SloppyNone)),
                                     deflate=deflate, nev=nev)
-        sp.calls += 1
-        sp.iterations += its[0]
-        sp.iterationsMax = max(sp.iterationsMax, its[0])
-        sp.seconds += time.time() - t0
-        sp.flops += self._flops(its[0])
-        sp.reliableUpdates += nup[0]
-        sp.r2 = fin[0]
+        self._record(sp, its[0], fin[0], time.time() - t0, nup[0])
         sp.r2hist = None
         if sp.verbosity > 1:
             print("solveOO(HIP): " + sp.getStats())
@@ -762,12 +764,7 @@ class Staggered:
             n = len(deflate.evals) if nev is None else int(nev)
             check(lib().qexhip_stag_solve_deflated(self.ctx._h, deflate.id, n, _p(x), _p(b), float(m), float(sp.r2req), int(sp.maxits),
                                                    int(getattr(sp, "sloppySolve", SloppyNone)), C.byref(its), C.byref(fin)))
-            sp.calls += 1
-            sp.iterations += its.value
-            sp.iterationsMax = max(sp.iterationsMax, its.value)
-            sp.seconds += time.time() - t0
-            sp.flops += self._flops(its.value)
-            sp.r2 = fin.value
+            self._record(sp, its.value, fin.value, time.time() - t0)
             return
         if sloppy is not None:
             sloppy = _batch_sloppy(sloppy)
@@ -776,44 +773,31 @@ class Staggered:
             t0 = time.time()
             its, fin, nup = C.c_int(0), C.c_double(0), C.c_int(0)
             ms = np.array([float(v) for v in m], dtype=np.float64)
-            ptrs = (C.c_void_p * len(x))(*[_p(a).value for a in x])
+            ptrs = _ptrs(x)
             check(lib().qexhip_stag_solve_multi_sloppy(self.ctx._h, ptrs, _p(b), _p(ms), len(x), float(sp.r2req), int(sp.maxits),
                                                        sloppy, C.byref(its), C.byref(fin), C.byref(nup)))
-            sp.calls += 1
-            sp.iterations += its.value
-            sp.iterationsMax = max(sp.iterationsMax, its.value)
-            sp.seconds += time.time() - t0
-            sp.flops += self._flops(its.value)
-            sp.r2 = fin.value
-            sp.reliableUpdates += nup.value
+            self._record(sp, its.value, fin.value, time.time() - t0, nup.value)
             if sp.verbosity > 1:
                 print("stagSolve(HIP): " + sp.getStats())
             return
         t0 = time.time()
-        its, fin = C.c_int(0), C.c_double(0)
+        its, fin, nup = C.c_int(0), C.c_double(0), C.c_int(0)
         sloppy = int(getattr(sp, "sloppySolve", SloppyNone))
         if multi and sloppy != SloppyNone:
             raise ValueError("sloppySolve applies to single-mass solves only: a multi-shift solve runs in fp64 unless the "
                              "mixed-precision one is asked for with the keyword sloppy=1 (solve / solveXX_multi / dev_solve_xx_multi)")
         if sloppy != SloppyNone:
-            nup = C.c_int(0)
             check(lib().qexhip_stag_solve_sloppy(self.ctx._h, _p(x), _p(b), float(m), float(sp.r2req), int(sp.maxits),
                                                  1 if sp.usePrevSoln else 0, sloppy, C.byref(its), C.byref(fin), C.byref(nup)))
-            sp.reliableUpdates += nup.value
         elif isinstance(x, (list, tuple)):
             ms = np.array([float(v) for v in m], dtype=np.float64)
-            ptrs = (C.c_void_p * len(x))(*[_p(a).value for a in x])
+            ptrs = _ptrs(x)
             check(lib().qexhip_stag_solve_multi(self.ctx._h, ptrs, _p(b), _p(ms), len(x), float(sp.r2req),
                                                 int(sp.maxits), C.byref(its), C.byref(fin)))
         else:
             check(lib().qexhip_stag_solve_prev(self.ctx._h, _p(x), _p(b), float(m), float(sp.r2req), int(sp.maxits),
                                                1 if sp.usePrevSoln else 0, C.byref(its), C.byref(fin)))
-        sp.calls += 1
-        sp.iterations += its.value
-        sp.iterationsMax = max(sp.iterationsMax, its.value)
-        sp.seconds += time.time() - t0
-        sp.flops += self._flops(its.value)
-        sp.r2 = fin.value
+        self._record(sp, its.value, fin.value, time.time() - t0, nup.value)
         if sp.verbosity > 1:
             print("stagSolve(HIP): " + sp.getStats())
 
@@ -826,8 +810,8 @@ class Staggered:
         if deflate is not None or nev is not None:
             nev = _deflate_args(deflate, nev, n)
         rq = [float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]
-        xp = (C.c_void_p * n)(*[_p(a).value for a in xs])
-        bp = (C.c_void_p * n)(*[_p(a).value for a in bs])
+        xp = _ptrs(xs)
+        bp = _ptrs(bs)
         mv, rv = (C.c_double * n)(*[float(v) for v in ms]), (C.c_double * n)(*rq)
         its, fin = (C.c_int * n)(), (C.c_double * n)()
         if deflate is not None:
@@ -878,15 +862,8 @@ class Staggered:
             its, fin, nup = self._batch("solve", xs, bs, ms, [sp.r2req for sp in sl], min(sp.maxits for sp in sl), sloppy=sloppy,
                                         deflate=deflate, nev=nev)
         dt = (time.time() - t0) / len(xs)
-        for sp, u in zip(sl, nup):
-            sp.reliableUpdates += u
-        for sp, i, f in zip(sl, its, fin):
-            sp.calls += 1
-            sp.iterations += i
-            sp.iterationsMax = max(sp.iterationsMax, i)
-            sp.seconds += dt
-            sp.flops += self._flops(i)
-            sp.r2 = f
+        for sp, i, f, u in zip(sl, its, fin, nup):
+            self._record(sp, i, f, dt, u)
         return its
 
     def solveXX_batch(self, xs, bs, ms, r2req, maxits, parEven=True, sloppy=None, deflate=None, nev=None):
@@ -911,7 +888,7 @@ class Staggered:
             its, nup = C.c_int(0), C.c_int(0)
             fin, ref = (C.c_double * n)(), (C.c_int * n)()
             sh = np.array([float(v) for v in shifts], dtype=np.float64)
-            ptrs = (C.c_void_p * n)(*[_p(a).value for a in xs])
+            ptrs = _ptrs(xs)
             check(lib().qexhip_stag_solve_xx_multi_sloppy(self.ctx._h, ptrs, _p(b), _p(sh), n, float(sp.r2req), int(sp.maxits),
                                                           1 if parEven else 0, sloppy, C.byref(its), fin, C.byref(nup), ref))
             sp.iterations += its.value
@@ -927,7 +904,7 @@ class Staggered:
         its = C.c_int(0)
         sh = np.array([float(v) for v in shifts], dtype=np.float64)
         hist = np.zeros(max(histcap, 1))
-        ptrs = (C.c_void_p * len(xs))(*[_p(a).value for a in xs])
+        ptrs = _ptrs(xs)
         check(lib().qexhip_stag_solve_xx_multi(self.ctx._h, ptrs, _p(b), _p(sh), len(xs), float(sp.r2req),
                                                int(sp.maxits), 1 if parEven else 0, C.byref(its), _p(hist), histcap))
         sp.iterations += its.value
@@ -1211,7 +1188,7 @@ class HisqCoefs:
         def fermionForce(f, psis, scales):
             """fermionForce (hisqhmc.nim:496-541) for the fields psis; the closure must hold the PHASED links"""
             n = len(psis)
-            arr = (C.c_void_p * n)(*[_p(p).value for p in psis])
+            arr = _ptrs(psis)
             sc = (C.c_double * n)(*[float(v) for v in scales])
             check(lib().qexhip_hisq_fermion_force(ctx._h, _p(f), arr, sc, n))
 
@@ -1253,7 +1230,7 @@ class HypCoefs:
         def fforce(f, psis, scales, bc="aaaa"):
             """fforce + smeared_one_link_force (staghmc_spv.nim:716-865) for the fields psis"""
             n = len(psis)
-            arr = (C.c_void_p * n)(*[_p(p).value for p in psis])
+            arr = _ptrs(psis)
             sc = (C.c_double * n)(*[float(v) for v in scales])
             ap = (C.c_int * 4)(*[1 if ch == "a" else 0 for ch in bc])
             check(lib().qexhip_nhyp_fermion_force(ctx._h, _p(f), arr, sc, n, ap, None))
@@ -1262,7 +1239,7 @@ class HypCoefs:
             """the whole fforce incl. its solves (staghmc_sh.nim:387-427) on the operator's current links
             (build them from this closure: Staggered(ctx, None, smear=...)); returns the iteration counts"""
             n = len(phis)
-            arr = (C.c_void_p * n)(*[_p(p).value for p in phis])
+            arr = _ptrs(phis)
             ms = (C.c_double * n)(*[float(v) for v in masses])
             sc = (C.c_double * n)(*[float(v) for v in scales])
             rq = (C.c_double * n)(*([float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]))

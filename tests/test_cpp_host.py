@@ -87,6 +87,18 @@ def test_closed_form_exp_against_the_reference_algorithm_and_long_double(tmp_pat
     assert p.returncode == 0 and "0 scale(s) out of bounds" in p.stdout, p.stdout
 
 
+def test_full_solve_plan_is_the_reference_rule_bit_for_bit(tmp_path):
+    """csrc/full_solve.h, the one statement of the even/odd full solve's decisions (stop split, reconstruct-right / -left, parity,
+    inner targets) that the single solve, the lock-step batch and the multi-shift solve share: every case of stagSolve.nim:141-218,
+    the mass-0 rule and the `<=` at exactly half the target among them, with == on doubles (tests/cpp/test_full_solve_plan.cpp)."""
+    exe = str(tmp_path / "test_full_solve_plan")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "qex_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "test_full_solve_plan.cpp"), "-o", exe])
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
+    print(p.stdout)
+    assert p.returncode == 0 and "full solve plan: Passed" in p.stdout, p.stdout
+
+
 def test_peer_transport_host_rendezvous(tmp_path):
     """qex_amd/csrc/peer_shm.cpp, the out-of-band channel of the peer-memory transport (what QMP's init / barrier / max give
     QEX, src/comms/commsQmp.nim:14-33,127-140), CPU only: 1-8 forked ranks meet in the shm segment, pass 1000 barriers, agree
