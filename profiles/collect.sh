@@ -10,7 +10,7 @@ rm -rf $OUT
 mkdir -p $OUT
 export TMPDIR=/tmp
 # 1. per-kernel time of the default bench command (the 32^4 workload alone: no CPU leg, no 48^3x96 leg)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench_32x4 -- python3 bench.py --steps 200 --warmup 20 --no-cpu --no-48x96 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench_32x4 -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu --no-48x96 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 # 2. per-kernel time of the profiling workload (flow, nHYP chain, Naik multi-shift)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_workload -- python3 profiles/pmc_workload.py > $OUT/workload.log 2>&1
 # 3. PMC passes, one counter group each

@@ -3,7 +3,7 @@ tests/golden/shard_checks.json.
 
 The reference has no such facility: QEX's multi-rank runs are checked by eye against single-rank logs
 (the regression harness tests/extra/staghmc_sh/run:43-44 diffs printed energies).  Here every rank of
-`bench.py --gpus N` recomputes, on its slab of the benchmark inputs and through the same entry points the
+`bench.py --full --gpus N` recomputes, on its slab of the benchmark inputs and through the same entry points the
 timed region uses, a handful of GLOBAL quantities whose value cannot depend on the partition:
 
     plaq        the six plaquettes of the unphased start         src/gauge/gaugeUtils.nim:213-282

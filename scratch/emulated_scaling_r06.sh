@@ -2,7 +2,7 @@
 # auto choice between distinct devices of one node since round 6), and the peer-memory transport with its fused sweep.
 # exchange: 3 us latency + bytes / 45 GB/s per xGMI direction (62 us for a 48^3 face); all-reduce: +15 us on top of the one-rank
 # ncclAllReduce, +3 us inside the mailbox kernel.  Pessimistic rows: half the bandwidth, twice the latencies.
-run() { env "$1" timeout -k 5 240 python3 bench.py --no-cpu --no-extra --no-48x96 --no-shard-check --steps 200 --warmup 20 --repeats 3 "${@:2}" 2>/dev/null | python3 -c "
+run() { env "$1" timeout -k 5 240 python3 bench.py --full --no-cpu --no-extra --no-48x96 --no-shard-check --steps 200 --warmup 20 --repeats 3 "${@:2}" 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1]); m=d.get('multi_gpu',{}); sw=m.get('sweep',{})
 print('$*', '->', round(1e3*d['ms_per_step'],1), 'us/iteration; transport', d.get('transport'), 'overlap', sw.get('overlap'), 'form', sw.get('form'), 'exchange_us', round(sw.get('exchange_us',0),1), 'boundary_at', round(sw.get('boundary_at',0),2), 'tuned', [round(v) for v in sw.get('tuned_us_per_sweep',[])], 'anatomy', {k: m.get(k) for k in ('interior_us','boundary_us','exchange_us','allreduce_us')}, flush=True)" || { rc=$?; [ $rc -ge 124 ] && exit $rc; }; }

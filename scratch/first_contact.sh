@@ -11,7 +11,7 @@
 #   rung 2  tests/two_rank_worker.py, 2 ranks on 2 devices: every operator / solver / gauge-sector result of each rank's slab against
 #           the global oracle -- over RCCL alone, over RCCL + mailbox sums (what `auto` picks), over the peer-memory transport
 #   rung 3  tests/shared_device_worker.py across devices: the fused sweep at 48^3 slabs (8 links, 16 links), real neighbours
-#   rung 4  bench.py --gpus 2, 4, 8 (as many as the node has): the driver's own command line; every line self-verifies
+#   rung 4  bench.py --full --gpus 2, 4, 8 (as many as the node has): the driver's own command line; every line self-verifies
 #           (shard_check at 32^4 and 48^3 x 96 against the oracle-pinned fixture) and carries the multi_gpu block
 # What the logs overwrite in DESIGN.md section 5: the 45 GB/s / 3 us link constants (rung 1: GB/s and handoff latency), the
 # "predicted strong scaling" table (rung 4: cg_48x48x48x96.ms_per_step per N, its multi_gpu.sweep block: measured exchange us, where
@@ -66,6 +66,6 @@ rung "fused_sweep_48x48x48_8links" 300 env QEXHIP_TRANSPORT=peer QEXHIP_PEER_TIM
 rung "fused_sweep_48x48x48_16links" 300 env QEXHIP_TRANSPORT=peer QEXHIP_PEER_TIMEOUT=30 $(launch 2) tests/shared_device_worker.py 48 48 48 24 --naik --distinct-devices
 for n in 2 4 8; do
   [ "$n" -le "$NG" ] || continue
-  rung "bench_gpus$n" 1100 $(launch $n) bench.py --gpus $n --steps 200 --warmup 20
+  rung "bench_gpus$n" 1100 $(launch $n) bench.py --gpus $n --steps 200 --warmup 20 --full
 done
 echo "first contact: every rung passed" | tee -a "$OUT/summary.txt"

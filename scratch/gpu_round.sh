@@ -13,7 +13,7 @@ run() {   # run NAME LIMIT cmd... : rc 124/137 = killed -> stop everything
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "$name was killed at its limit: stopping"; tail -5 gpurun_out/$name.err; exit 1; fi
   return $rc
 }
-run bench_$TAG 500 python3 bench.py
+run bench_$TAG 500 python3 bench.py --full
 tail -c 1500 gpurun_out/bench_$TAG.log
 run smoke_$TAG 200 python3 -c "import __graft_entry__ as g; g.smoke()"
 tail -2 gpurun_out/smoke_$TAG.log

@@ -1,6 +1,6 @@
 # one rank's 48^3 x 12 share of 48^3 x 96 at N = 8, rehearsed on one GPU: where the iteration's time goes (timers on: perturbed)
 for ov in -1 0 1; do
-python3 bench.py --halo --lat 48 48 48 12 --no-cpu --no-extra --no-48x96 --no-shard-check --steps 200 --warmup 20 --repeats 3 --set-option overlap=$ov 2>/dev/null | python3 -c "
+python3 bench.py --full --halo --lat 48 48 48 12 --no-cpu --no-extra --no-48x96 --no-shard-check --steps 200 --warmup 20 --repeats 3 --set-option overlap=$ov 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 m=d['multi_gpu']

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generate tests/golden/shard_checks.json: the partition-independent quantities `bench.py --gpus N` recomputes on
+"""Generate tests/golden/shard_checks.json: the partition-independent quantities `bench.py --full --gpus N` recomputes on
 its sharded lattice before the timed region (qex_amd/selfcheck.py).
 
     python tests/golden/make_shard_checks.py                # on ONE GPU: 8^4, 32^4, 48^3x96 from the product (N = 1, periodic)

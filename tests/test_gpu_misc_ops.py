@@ -192,7 +192,7 @@ def test_bench_two_ranks_share_one_gpu(nranks):
     # profiles/r06_notes.md section 1)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4", QEX_BENCH_FORCE_CANARY="1", QEXHIP_HOP_SPLIT="2", QEXHIP_OVERLAP="1", QEXHIP_PEER_TIMEOUT="20")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(29531 + nranks), os.path.join(root, "bench.py"), "--gpus", str(nranks), "--steps", "20", "--warmup", "5"]
+           "--master-port", str(29531 + nranks), os.path.join(root, "bench.py"), "--gpus", str(nranks), "--steps", "20", "--warmup", "5", "--full"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root, env=env)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2000:])
     lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
@@ -234,7 +234,7 @@ def test_bench_self_verification_on_the_sharded_code_path(comm2):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", QEXHIP_COMM2=comm2)
     if comm2 == "mbox":          # the transport `auto` picks between distinct devices of one node: RCCL faces, mailbox rank sums
         env.update(QEXHIP_COMM2="1", QEXHIP_TRANSPORT="mbox")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--halo", "--steps", "20", "--warmup", "3", "--repeats", "2", "--no-cpu", "--no-48x96"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--halo", "--steps", "20", "--warmup", "3", "--repeats", "2", "--no-cpu", "--no-48x96"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=root, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     ln = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
@@ -259,12 +259,44 @@ def test_bench_self_verification_fails_loudly(tmp_path):
     bad = tmp_path / "bad.json"
     bad.write_text(json.dumps(fx))
     env = dict(os.environ, QEX_SHARD_FIXTURE=str(bad))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "2", "--repeats", "1", "--no-cpu", "--no-48x96", "--no-extra"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--repeats", "1", "--no-cpu", "--no-48x96", "--no-extra"]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=root, env=env)
     assert p.returncode == 4, (p.returncode, p.stderr[-1000:])
     ln = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
     assert ln["shard_check"]["ok"] is False and any("Db2" in f for f in ln["shard_check"]["failed"])
     assert "self-verification failed" in ln["error"] and ln["value"] > 0
+
+
+def test_bench_without_full_runs_the_headline_only():
+    """bench.py --gpus 1 --steps K --warmup W: the contract's keys, the headline with the roofline of its own timed region, and
+    none of what --full adds -- no self-verification, no legs, no CPU baseline, no 48^3 x 96 leg -- and at most
+    30 s of the run outside its steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2"]
+    t0 = time.perf_counter()
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, cwd=root)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    ln = lines[0]
+    assert "error" not in ln and ln["full"] is False and ln["n_gpus"] == 1 and ln["steps"] == 10 and ln["warmup"] == 2
+    assert ln["value"] > 0 and ln["ms_per_step"] > 0 and ln["unit"] == "GFLOP/s" and ln["higher_is_better"] is True and ln["dtype"] == "f64"
+    # the roofline comes out of the kernel timers of the last repeat's timed region: two sweeps per step, no run of its own
+    assert ln["repeats"]["n"] == 5 and ln["roofline"]["launches"] == 20 and ln["roofline"]["frac"] > 0
+    # at most 30 s of the whole process, start to exit, outside its steps (measured: about 3 s)
+    outside = wall - (10 + 2) * 1e-3 * ln["ms_per_step"]
+    print("plain run: %.2f s from start to exit, %.2f s outside its steps" % (wall, outside))
+    assert outside <= 30.0, outside
+    for k in ("shard_check", "compressed_links", "batched_cg_3_systems", "naik_multishift_32x4", "flow_step_32x4", "nhyp_smear_force_32x4",
+              "cpu_baseline", "vs_cpu_baseline_same_run", "cg_48x48x48x96", "naik_multishift_48x48x48x96", "multi_gpu"):
+        assert k not in ln, k
 
 
 @pytest.mark.parametrize("lt", [4, 8])

@@ -141,7 +141,7 @@ def test_four_ranks_against_the_global_oracle():
 @needs2
 def test_bench_two_ranks_real_rccl():
     """the driver's N = 2 launch line: self-verification green through real transport, and the line explains itself"""
-    p = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5", "--repeats", "2"], timeout=900)
+    p = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5", "--repeats", "2", "--full"], timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     ln = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
     assert "error" not in ln and ln["rccl_nranks"] == 2 and ln["shard_check"]["ok"] is True, ln.get("shard_check")

@@ -269,6 +269,15 @@ def test_bench_watchdog_turns_a_stall_into_a_nonzero_exit():
     assert "stalled" in ln["error"] and ln["value"] is None
 
 
+def test_bench_full_option_is_accepted_and_reported():
+    """--full (everything beyond the headline measurement) is an option of the command line and the line says whether it was given"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--gpus", "1", "--steps", "5", "--warmup", "1", "--full"]
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-1000:]
+    ln = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert ln["full"] is True and ln["dry_run"] is True and ln["value"] is None
+
+
 @pytest.mark.parametrize("lat", [[32, 32, 32, 32], [8, 8, 8, 8], [4, 6, 10, 6], [48, 48, 48, 12], [16, 4, 8, 24]])
 def test_plane_tile_order_is_a_permutation(lat):
     """The per-plane visiting order of the staple kernels (csrc/layout.hip: tile_order_plane) only re-orders the
