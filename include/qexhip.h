@@ -735,6 +735,8 @@ int qexhip_link_packed_host(const double *links, int n, unsigned char *escaped, 
  *                  block (test hook: the cleanup path everywhere)
  *   "chain_overlap" 0: the nHYP force chain of a t-sharded field exchanges a level's chain fields first and runs the next staple
  *                  derivative in one pass, instead of running its ghost-free slices beside the exchange (default 1; bit-identical)
+ *   "hisq_md_fused" the two kernels of qexhip_md_hisq_fforce / _fforce_solve (default 3): bit 0 = k_outer13 (0: the 2n outer-product launches
+ *                  it replaces), bit 1 = k_projtah_kick (0: TAH, then the kick, in two launches); bit-identical, A/B and test hook
  *   "force_pair"   0: k_force_lds (one tile and parity per workgroup), what shapes without paired tile positions run
  *   "obs_clover"   0: the generic path walker, what fmunu loops 3-5 run, for the clover loop as well
  *   "emu_exchange_us", "emu_allreduce_us"   transport emulation for one-GPU rehearsals: every face exchange / all-reduce is preceded,
@@ -902,6 +904,26 @@ int qexhip_md_kick(qexhip_handle h, int source, double t);
 int qexhip_md_shift_links(qexhip_handle h, int source, double t);
 int qexhip_md_save_links(qexhip_handle h);
 int qexhip_md_restore_links(qexhip_handle h);
+/* HISQ molecular dynamics on the resident fields: the force side of src/examples/hisqhmc.nim with nothing but the arguments
+ * crossing PCIe.  The state is the HISQ closure's (qexhip_hisq_prepare / qexhip_hisq_release), built from the resident links.
+ *   md_hisq_prepare: smearRephase (hisqhmc.nim:405-414) on the resident thin links of qexhip_md_begin / qexhip_gauge_set: a phased
+ *       copy (setBC + stagPhase; antiperiodic / phases NULL = the defaults of qexhip_stag_set_links_nhyp: t antiperiodic, QEX's
+ *       staggered phases), then u, v, w, su, sul exactly as qexhip_hisq_prepare builds them from that field.  The resident links
+ *       are not written (the reference rephases them back).  set_links != 0 also hands su, sul to the operator
+ *       (qexhip_stag_set_links_hisq(h, NULL); the reference's stag = newStag3(su, sul), :332).
+ *   md_hisq_fforce: fermionForce (:496-539) for n >= 1 resident full-volume vectors: f1 = sum_k scale[k] psi_k(x) (x) psi_k(x+mu)^+,
+ *       f3 the same with x+3mu, odd sites *= -1 (one launch per four vectors for both), smearedForce(ff, f1, f3),
+ *       f = TAH(ff u^+) with the phased u, and updateMomentum (:558-560) p += t f in the pass that stores f.
+ *   md_hisq_fforce_solve: the same with psi_k = D(mass[k])^-1 phi_k (Staggered.solve, :541-545) solved first, in lock-step
+ *       batches of at most four on the operator's current links; iters (nullable) receives the iteration counts.
+ *   md_hisq_force_get: the last f of those two, [vol][4][3][3][2] (tests, host integrators); QEXHIP_ERR_STATE if there is none.
+ * QEXHIP_ERR_ARG (n < 1, unknown or repeated field ids, NULL arrays) and QEXHIP_ERR_STATE (no resident links, no momenta, no
+ * prepare) are returned before anything is launched.  t-sharded: collective. */
+int qexhip_md_hisq_prepare(qexhip_handle h, const int antiperiodic[4], const int phases[4], int set_links);
+int qexhip_md_hisq_fforce(qexhip_handle h, int n, const int *psi_ids, const double *scale, double t);
+int qexhip_md_hisq_fforce_solve(qexhip_handle h, int n, const int *phi_ids, const double *mass, const double *scale, const double *r2req,
+                                int maxits, double t, int *iters);
+int qexhip_md_hisq_force_get(qexhip_handle h, double *f);
 
 /* ---------------- SciDAC/LIME gauge files (host only, no handle) ----------------
  * loadGauge / saveGauge (src/gauge/gaugeUtils.nim:87-122) via Reader / Writer (src/io/readerQiolite.nim:37-239,

@@ -511,6 +511,20 @@ class ResidentMD {
   void shiftLinks(Source s, double t) { check(qexhip_md_shift_links(c_.h, (int)s, t)); }        // fgv / fgvf
   void saveLinks() { check(qexhip_md_save_links(c_.h)); }
   void restoreLinks() { check(qexhip_md_restore_links(c_.h)); }
+  // HISQ molecular dynamics (hisqhmc.nim:405-414,496-545) on the resident fields: qexhip_md_hisq_*
+  void hisqPrepare(bool setLinks = true, const std::array<int, 4> &antiperiodic = {0, 0, 0, 1}) {
+    check(qexhip_md_hisq_prepare(c_.h, antiperiodic.data(), nullptr, setLinks ? 1 : 0));
+  }
+  void hisqFforce(const std::vector<int> &psiIds, const std::vector<double> &scale, double t) {
+    check(qexhip_md_hisq_fforce(c_.h, (int)psiIds.size(), psiIds.data(), scale.data(), t));
+  }
+  std::vector<int> hisqFforceSolve(const std::vector<int> &phiIds, const std::vector<double> &mass, const std::vector<double> &scale,
+                                   const std::vector<double> &r2req, int maxits, double t) {
+    std::vector<int> its(phiIds.size(), 0);
+    check(qexhip_md_hisq_fforce_solve(c_.h, (int)phiIds.size(), phiIds.data(), mass.data(), scale.data(), r2req.data(), maxits, t, its.data()));
+    return its;
+  }
+  void hisqForce(Field &f) { check(qexhip_md_hisq_force_get(c_.h, f.data())); }
 };
 // HisqCoefs.smear(g, fl, ll) (hisqLinks.nim:32-43)
 inline void hisqSmear(Context &c, const Field &g, Field &fl, Field &ll) { check(qexhip_hisq_smear(c.h, g.data(), fl.data(), ll.data())); }

@@ -200,6 +200,10 @@ SYMBOLS = [
     ("qexhip_md_shift_links", _ci, [_vp, _ci, _cd]),
     ("qexhip_md_save_links", _ci, [_vp]),
     ("qexhip_md_restore_links", _ci, [_vp]),
+    ("qexhip_md_hisq_prepare", _ci, [_vp, _pi, _pi, _ci]),
+    ("qexhip_md_hisq_fforce", _ci, [_vp, _ci, _pi, _pd, _cd]),
+    ("qexhip_md_hisq_fforce_solve", _ci, [_vp, _ci, _pi, _pd, _pd, _pd, _ci, _cd, _pi]),
+    ("qexhip_md_hisq_force_get", _ci, [_vp, _vp]),
     ("qexhip_io_metadata", _ci, [C.c_char_p, C.c_char_p, _ci, C.c_char_p, _ci, _pi, _pi]),
     ("qexhip_io_crc32", _ci, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint)]),   # data pointer, not a handle
     ("qexhip_io_gauge_info", _ci, [C.c_char_p, _pi, C.c_char_p, _pi]),

@@ -1192,6 +1192,10 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
   else if (n == "flow_exp") c->opt_flow_exp = value;
   else if (n == "smear_ca") c->opt_smear_ca = value;
   else if (n == "chain_overlap") c->opt_chain_overlap = value;
+  else if (n == "hisq_md_fused") {
+    if (value < 0 || value > 3) { qexhip_set_error("option hisq_md_fused: bit 0 k_outer13, bit 1 k_projtah_kick"); return QEXHIP_ERR_ARG; }
+    c->opt_hisq_md_fused = value;
+  }
   else if (n == "hop_split") {
     if (value != -1 && value != 0 && value != 2) { qexhip_set_error("option hop_split: -1 measured, 0 split by sites, 2 fused (the two-launch form 1 left the library in round 6)"); return QEXHIP_ERR_ARG; }
     c->opt_hop_split = value;
@@ -1643,5 +1647,48 @@ extern "C" int qexhip_md_gauge_force(qexhip_handle c, double cplaq, double crect
 }
 extern "C" int qexhip_md_kick(qexhip_handle c, int source, double t) { if (!c) return QEXHIP_ERR_ARG; HIPCHK(hipSetDevice(c->device)); return md_kick(c, source, t); }
 extern "C" int qexhip_md_shift_links(qexhip_handle c, int source, double t) { if (!c) return QEXHIP_ERR_ARG; HIPCHK(hipSetDevice(c->device)); return md_shift_links(c, source, t); }
+// ---- resident HISQ molecular dynamics (smear.hip: md_hisq_*; hisq_md.hip: k_outer13, k_projtah_kick) ----
+extern "C" int qexhip_md_hisq_prepare(qexhip_handle c, const int antiperiodic[4], const int phases[4], int set_links) {
+  if (!c) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  static const int defph[4] = {8, 9, 11, 0};
+  int mask = 0;
+  for (int mu = 0; mu < 4; mu++) if (antiperiodic ? antiperiodic[mu] : (mu == 3)) mask |= 1 << mu;
+  return md_hisq_prepare(c, mask, phases ? phases : defph, set_links);
+}
+// every argument and state check of the two force entries, before anything is launched
+static int md_hisq_fields(qexhip_ctx *c, const char *who, int n, const int *ids, const double *scale, std::vector<DevField *> &f) {
+  if (!ids || !scale) { qexhip_set_error("%s: null argument", who); return QEXHIP_ERR_ARG; }
+  if (n < 1) { qexhip_set_error("%s: n < 1", who); return QEXHIP_ERR_ARG; }
+  f.resize(n);
+  for (int k = 0; k < n; k++) {
+    CHK(find_field(c, ids[k], &f[k]));
+    for (int j = 0; j < k; j++)
+      if (ids[j] == ids[k]) { qexhip_set_error("%s: ids[%d] == ids[%d]", who, j, k); return QEXHIP_ERR_ARG; }
+  }
+  return md_hisq_check(c, who);
+}
+extern "C" int qexhip_md_hisq_fforce(qexhip_handle c, int n, const int *psi_ids, const double *scale, double t) {
+  if (!c) return QEXHIP_ERR_ARG;
+  std::vector<DevField *> f;
+  CHK(md_hisq_fields(c, "md_hisq_fforce", n, psi_ids, scale, f));
+  HIPCHK(hipSetDevice(c->device));
+  return md_hisq_fforce(c, n, f.data(), scale, t);
+}
+extern "C" int qexhip_md_hisq_fforce_solve(qexhip_handle c, int n, const int *phi_ids, const double *mass, const double *scale,
+                                           const double *r2req, int maxits, double t, int *iters) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!mass || !r2req) { qexhip_set_error("md_hisq_fforce_solve: null argument"); return QEXHIP_ERR_ARG; }
+  std::vector<DevField *> f;
+  CHK(md_hisq_fields(c, "md_hisq_fforce_solve", n, phi_ids, scale, f));
+  if (!c->W) { qexhip_set_error("md_hisq_fforce_solve: the operator has no links (qexhip_md_hisq_prepare with set_links)"); return QEXHIP_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  return md_hisq_fforce_solve(c, n, f.data(), mass, scale, r2req, maxits, t, iters);
+}
+extern "C" int qexhip_md_hisq_force_get(qexhip_handle c, double *f) {
+  if (!c || !f) return QEXHIP_ERR_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  return md_hisq_force_get(c, f);
+}
 extern "C" int qexhip_md_save_links(qexhip_handle c) { if (!c) return QEXHIP_ERR_ARG; HIPCHK(hipSetDevice(c->device)); return md_save_links(c); }
 extern "C" int qexhip_md_restore_links(qexhip_handle c) { if (!c) return QEXHIP_ERR_ARG; HIPCHK(hipSetDevice(c->device)); return md_restore_links(c); }

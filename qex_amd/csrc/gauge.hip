@@ -278,11 +278,7 @@ __global__ void __launch_bounds__(512) k_force_lds2(Geom g, const double2 *__res
 }
 
 // RK3 stage, second half: U <- exp(v) U with v already in the momentum field (wflow.nim:40-43)
-// body link-tiles of both parity halves: linear index -> offset (skips the ghost tiles of a sharded field)
-__device__ __forceinline__ size_t body_tile_off(size_t tile, size_t ntile4, size_t etile4) {
-  const size_t p = tile >= ntile4;
-  return (p * etile4 + (tile - p * ntile4)) * 576;
-}
+// (body_tile_off, qexhip_internal.h: the body link-tiles of both parity halves, linear index -> offset)
 __global__ void __launch_bounds__(256) k_exp_update(size_t nlinks_tiles, double2 *G, const double2 *V, double t, size_t ntile4, size_t etile4) {
   size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;  // (tile-of-links, lane)
   size_t tile = j >> 6;
@@ -1417,6 +1413,10 @@ int md_kick(qexhip_ctx *c, int source, double t) {
   CHK(md_ready(c));
   const double2 *F;
   CHK(md_source(c, source, &F));
+  return md_kick_dev(c, F, t);
+}
+int md_kick_dev(qexhip_ctx *c, const double2 *F, double t) {
+  CHK(md_ready(c));
   const size_t ltiles = (size_t)2 * c->g.ntile * 4;
   k_links_axpy<<<link_blocks(c), 256, 0, c->stream>>>(ltiles, c->gn->M, F, t, (size_t)c->g.ntile * 4, (size_t)c->g.etile * 4);
   HIPCHK(hipGetLastError());

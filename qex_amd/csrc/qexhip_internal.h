@@ -40,6 +40,12 @@ __host__ __device__ inline size_t vec_off(int pos, int colour) {
   return (size_t)(pos >> 6) * 192 + (size_t)colour * 64 + (size_t)(pos & 63);
 }
 
+// body link-tiles of both parity halves of a natural-layout gauge field: linear index -> offset (skips the ghost tiles of a sharded field)
+__host__ __device__ inline size_t body_tile_off(size_t tile, size_t ntile4, size_t etile4) {
+  const size_t p = tile >= ntile4;
+  return (p * etile4 + (tile - p * ntile4)) * 576;
+}
+
 struct DevField {  // full-volume colour vector: parity halves, each with its ghost tiles
   double2 *d = nullptr;
   size_t half = 0;  // double2 elements per parity half (= etile*192)
@@ -200,6 +206,8 @@ struct qexhip_ctx {
   int form_auto[2]{-1, -1};     // measured at set_links: 2 fused / 0 by sites for 8- and 16-link operators (-1: not measured)
   int opt_chain_overlap = 1; // option "chain_overlap" (A/B, test hook): 1 = the nHYP force chain's staple derivatives of a t-sharded field run in two passes,
                           // the ghost-free slices beside the exchange of the level's chain fields, the boundary slices behind it
+  int opt_hisq_md_fused = 3;  // option "hisq_md_fused" (A/B, test hook): bit 0 = the outer products of qexhip_md_hisq_fforce* in k_outer13 launches (0: the 2n
+                          // k_outer launches they replace), bit 1 = TAH and kick in k_projtah_kick (0: k_force_projtah, then k_links_axpy); same bits either way
   int opt_smear_ca = 1;   // option "smear_ca" (A/B, test hook): 1 = the nHYP levels of a t-sharded field are computed on shrinking ghost slices from
                           // ONE depth-3 thin-link exchange; 0 = every projected level field refreshes its ghost slices (rounds 1-4)
   int opt_flow_exp = 1;   // QEXHIP_FLOW_EXP / option "flow_exp": 1 = closed-form exp(v) in the fused Wilson-flow stage (same function,
@@ -583,6 +591,16 @@ int hisq_closure_force(qexhip_ctx *c, const double *dfl_host, const double *dll_
 int gauge_deriv_dev(qexhip_ctx *c, const double2 *G, double2 *F, double cplaq, double c2, int kind);
 int stag_outer_dev(qexhip_ctx *c, DevField &fx, double2 *F, double se, double so, int accumulate, int hop = 1);
 int hisq_fermion_force(qexhip_ctx *c, double *f_host, const double *const *psi, const double *scale, int n);
+int force_projtah_dev(qexhip_ctx *c, double2 *F, const double2 *G, int adj);             // F <- TAH(F G^+) (adj: TAH(G F^+)), ghost tiles included
+// resident HISQ molecular dynamics (qexhip_md_hisq_*): the state is the HISQ closure's, the two kernels are hisq_md.hip's
+int md_hisq_prepare(qexhip_ctx *c, int bcmask, const int ph[4], int set_links);
+int md_hisq_check(qexhip_ctx *c, const char *who);                                       // QEXHIP_ERR_STATE before anything is launched
+int md_hisq_fforce(qexhip_ctx *c, int n, DevField *const *psi, const double *scale, double t);
+int md_hisq_fforce_solve(qexhip_ctx *c, int n, DevField *const *phi, const double *mass, const double *scale, const double *r2req, int maxits,
+                         double t, int *iters);
+int md_hisq_force_get(qexhip_ctx *c, double *f_host);
+int hisq_outer13_dev(qexhip_ctx *c, int n, DevField *const *xs, const double *scale, double2 *CF, double2 *CL, int accumulate);
+int hisq_projtah_kick_dev(qexhip_ctx *c, double2 *F, const double2 *G, double2 *P, double t);
 int nhyp_gauge_force(qexhip_ctx *c, double *f_host, double cplaq, double c2, int kind);
 int nhyp_fermion_force(qexhip_ctx *c, double *f_host, const double *const *psi, const double *scale, int n, int bcmask, const int ph[4]);
 int nhyp_prepare(qexhip_ctx *c, const double *g_host, double a1, double a2, double a3, double *fl_host);
@@ -605,6 +623,7 @@ int md_momentum_norm2(qexhip_ctx *c, double *out);
 int md_update_links(qexhip_ctx *c, double t);
 int md_gauge_force(qexhip_ctx *c, double cplaq, double c2, int kind);
 int md_kick(qexhip_ctx *c, int source, double t);
+int md_kick_dev(qexhip_ctx *c, const double2 *F, double t);      // p += t F for a device force field in the links' layout
 int md_shift_links(qexhip_ctx *c, int source, double t);
 int md_save_links(qexhip_ctx *c);
 int md_restore_links(qexhip_ctx *c);

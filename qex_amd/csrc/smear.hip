@@ -1220,12 +1220,14 @@ __global__ void k_force_projtah(size_t nlinks_tiles, double2 *F, const double2 *
 struct HisqState {
   Smear S;
   double2 *G = nullptr, *V = nullptr, *W = nullptr, *FL = nullptr, *LL = nullptr, *CF = nullptr, *CL = nullptr, *F = nullptr;
+  bool md_force = false;               // F holds the last force of qexhip_md_hisq_fforce / _fforce_solve (qexhip_md_hisq_force_get)
   explicit HisqState(qexhip_ctx *c) : S(c) {}
 };
 void hisq_state_free(qexhip_ctx *c) {
   if (c->hisq) { delete (HisqState *)c->hisq; c->hisq = nullptr; }
 }
-int hisq_prepare(qexhip_ctx *c, const double *g_host, double *fl_host, double *ll_host) {
+// the closure's fields (allocated once per context) ...
+static int hisq_state_get(qexhip_ctx *c, HisqState **pst) {
   for (int i = 0; i < 4; i++) if (c->g.X[i] < 4) { qexhip_set_error("HISQ smearing needs lattice extents >= 4"); return -1; }
   HisqState *st = (HisqState *)c->hisq;
   if (!st) {
@@ -1234,13 +1236,24 @@ int hisq_prepare(qexhip_ctx *c, const double *g_host, double *fl_host, double *l
     Smear &S = st->S;
     for (double2 **p : {&st->G, &st->V, &st->W, &st->FL, &st->LL, &st->CF, &st->CL, &st->F}) CHK(S.alloc(p, S.gsz));
   }
+  *pst = st;
+  return 0;
+}
+// ... and v, w, su, sul from the u that st->G holds
+static int hisq_state_build(qexhip_ctx *c, HisqState *st) {
   Smear &S = st->S;
-  S.scratch_begin();                   // the scratch of the two fat7 passes is kept from call to call (qexhip_hisq_release / finalize free it)
   const double naik = 1.0, f2 = 2.0;
   const double c_second[5] = {(1.0 + 3.0 * f2 + naik) / 8.0, -1.0 / 16.0, 1.0 / 64.0, -1.0 / 384.0, -f2 / 16.0};
-  CHK(S.upload(st->G, g_host));
   CHK(S.hisq_first(st->G, st->V, st->W, !(c->g.halo && c->opt_smear_ca)));
-  CHK(S.fat7(st->FL, st->W, c_second, st->LL, st->W, -naik / 24.0));
+  return S.fat7(st->FL, st->W, c_second, st->LL, st->W, -naik / 24.0);
+}
+int hisq_prepare(qexhip_ctx *c, const double *g_host, double *fl_host, double *ll_host) {
+  HisqState *st;
+  CHK(hisq_state_get(c, &st));
+  Smear &S = st->S;
+  S.scratch_begin();                   // the scratch of the two fat7 passes is kept from call to call (qexhip_hisq_release / finalize free it)
+  CHK(S.upload(st->G, g_host));
+  CHK(hisq_state_build(c, st));
   if (fl_host) CHK(S.download(fl_host, st->FL));
   if (ll_host) CHK(S.download(ll_host, st->LL));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1252,6 +1265,7 @@ int hisq_closure_force(qexhip_ctx *c, const double *dfl_host, const double *dll_
   Smear &S = st->S;
   S.scratch_begin();                   // the reverse pass's scratch: the buffers of the previous call again
   CHK(S.upload(st->CF, dfl_host)); CHK(S.upload(st->CL, dll_host));
+  st->md_force = false;
   CHK(S.hisq_reverse(st->G, st->V, st->W, st->CF, st->CL, st->F));
   CHK(S.download(f_host, st->F));
   return 0;
@@ -1264,6 +1278,7 @@ int hisq_fermion_force(qexhip_ctx *c, double *f_host, const double *const *psi, 
   if (n < 1) { qexhip_set_error("hisq fermion force: n < 1"); return -1; }
   Smear &S = st->S;
   S.scratch_begin();
+  st->md_force = false;
   DevField *fx;
   CHK(get_work(c, WK_IN, &fx));
   for (int k = 0; k < n; k++) {
@@ -1283,6 +1298,71 @@ int hisq_set_links_from_closure(qexhip_ctx *c) {
   if (!st) { qexhip_set_error("set_links_hisq(g = NULL) needs qexhip_hisq_prepare first"); return -1; }
   CHK(st->S.ghosts_tlinks_lo(st->FL, 1)); CHK(st->S.ghosts_tlinks_lo(st->LL, 3));
   return links_from_natural(c, st->FL, st->LL);
+}
+
+__global__ void __launch_bounds__(256) k_rephase(Geom g, double2 *G, int bcmask, int ph0, int ph1, int ph2, int ph3, int tlast);
+static int smear_check(qexhip_ctx *c, int min_extent);
+// ---- resident HISQ molecular dynamics (qexhip_md_hisq_*) ----
+// smearRephase (hisqhmc.nim:405-414) on the resident thin links: the closure is built from a phased COPY (the reference rephases
+// its links in place, smears, and rephases them back), so the resident links are never written
+int md_hisq_prepare(qexhip_ctx *c, int bcmask, const int ph[4], int set_links) {
+  CHK(smear_check(c, 4));
+  const double2 *U = gauge_resident_links(c);
+  if (!U) { qexhip_set_error("md_hisq_prepare needs a resident gauge field (qexhip_gauge_set / qexhip_md_begin)"); return -3; }
+  HisqState *st;
+  CHK(hisq_state_get(c, &st));
+  Smear &S = st->S;
+  S.scratch_begin();
+  HIPCHK(hipMemcpyAsync(st->G, U, S.gsz * sizeof(double2), hipMemcpyDeviceToDevice, c->stream));
+  k_rephase<<<S.nb(), 256, 0, c->stream>>>(S.g, st->G, bcmask, ph[0], ph[1], ph[2], ph[3], c->rankCoord[3] == c->rankGeom[3] - 1);
+  HIPCHK(hipGetLastError());
+  CHK(hisq_state_build(c, st));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return set_links ? hisq_set_links_from_closure(c) : 0;
+}
+int md_hisq_check(qexhip_ctx *c, const char *who) {
+  if (!c->gn) { qexhip_set_error("%s: no resident gauge field (qexhip_gauge_set / qexhip_md_begin)", who); return -3; }
+  if (!c->gn->M) { qexhip_set_error("%s: no resident momenta (qexhip_md_begin / qexhip_md_refresh_momenta)", who); return -3; }
+  if (!c->hisq) { qexhip_set_error("%s: call qexhip_md_hisq_prepare first (smearRephase)", who); return -3; }
+  return 0;
+}
+// smearedForce(ff, f1, f3), f = TAH(ff u^+), p += t f: the chain from the outer products CF, CL of the closure
+static int md_hisq_finish(qexhip_ctx *c, HisqState *st, double t) {
+  CHK(st->S.hisq_reverse(st->G, st->V, st->W, st->CF, st->CL, st->F));
+  CHK(hisq_projtah_kick_dev(c, st->F, st->G, c->gn->M, t));
+  st->md_force = true;
+  return 0;
+}
+int md_hisq_fforce(qexhip_ctx *c, int n, DevField *const *psi, const double *scale, double t) {
+  CHK(md_hisq_check(c, "md_hisq_fforce"));
+  HisqState *st = (HisqState *)c->hisq;
+  st->S.scratch_begin();
+  st->md_force = false;
+  CHK(hisq_outer13_dev(c, n, psi, scale, st->CF, st->CL, 0));
+  return md_hisq_finish(c, st, t);
+}
+// the same with psi_k = D(mass_k)^-1 phi_k solved first (hisqhmc.nim:541-545), in lock-step batches of four on the operator's current
+// links; a batch's solutions go into the outer products before the next batch reuses their fields
+int md_hisq_fforce_solve(qexhip_ctx *c, int n, DevField *const *phi, const double *mass, const double *scale, const double *r2req, int maxits,
+                         double t, int *iters) {
+  CHK(md_hisq_check(c, "md_hisq_fforce_solve"));
+  HisqState *st = (HisqState *)c->hisq;
+  st->S.scratch_begin();
+  st->md_force = false;
+  for (int k0 = 0; k0 < n; k0 += 4) {
+    const int k = std::min(4, n - k0);
+    DevField *xs[4], *bs[4];
+    CHK(batch_io_fields(c, k, xs, bs));
+    for (int j = 0; j < k; j++) bs[j] = phi[k0 + j];         // read only (the solver copies its source first)
+    CHK(solve_full_batch_dev(c, k, xs, bs, mass + k0, r2req + k0, maxits, iters ? iters + k0 : nullptr, nullptr));
+    CHK(hisq_outer13_dev(c, k, xs, scale + k0, st->CF, st->CL, k0 > 0));
+  }
+  return md_hisq_finish(c, st, t);
+}
+int md_hisq_force_get(qexhip_ctx *c, double *f_host) {
+  HisqState *st = (HisqState *)c->hisq;
+  if (!st || !st->md_force) { qexhip_set_error("md_hisq_force_get: no force yet (qexhip_md_hisq_fforce / _fforce_solve)"); return -3; }
+  return st->S.download(f_host, st->F);
 }
 
 // setBC_cust + stagPhase on a device gauge field (stagg_pv_hmc/staghmc_spv.nim:367-401,
@@ -1417,6 +1497,12 @@ __global__ void __launch_bounds__(256) k_force_projtah(size_t nlinks_tiles, doub
   size_t o = tile * 576 + (j & 63);
   const M3 f = m3_load(F + o, 64), u = m3_load(G + o, 64);
   m3_store(F + o, 64, m3_tah(adj ? m3_mul_na(u, f) : m3_mul_na(f, u)));
+}
+int force_projtah_dev(qexhip_ctx *c, double2 *F, const double2 *G, int adj) {
+  const size_t ltiles = (size_t)2 * c->g.etile * 4;       // ghost tiles included: harmless, keeps the index linear
+  k_force_projtah<<<(unsigned)((ltiles * 64 + 255) / 256), 256, 0, c->stream>>>(ltiles, F, G, adj);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 static int nhyp_finish(qexhip_ctx *c, NhypState *st, int adj, double *f_host) {
   CHK(nhyp_backward_dev(c, st));

@@ -169,6 +169,11 @@ proc qexhip_md_kick(h: pointer; source: cint; t: cdouble): cint {.qh.}
 proc qexhip_md_shift_links(h: pointer; source: cint; t: cdouble): cint {.qh.}
 proc qexhip_md_save_links(h: pointer): cint {.qh.}
 proc qexhip_md_restore_links(h: pointer): cint {.qh.}
+proc qexhip_md_hisq_prepare(h: pointer; antiperiodic, phases: ptr cint; setLinks: cint): cint {.qh.}
+proc qexhip_md_hisq_fforce(h: pointer; n: cint; psiIds: ptr cint; scale: ptr cdouble; t: cdouble): cint {.qh.}
+proc qexhip_md_hisq_fforce_solve(h: pointer; n: cint; phiIds: ptr cint; mass, scale, r2req: ptr cdouble; maxits: cint; t: cdouble;
+                                 iters: ptr cint): cint {.qh.}
+proc qexhip_md_hisq_force_get(h: pointer; f: ptr cdouble): cint {.qh.}
 proc qexhip_io_metadata(path: cstring; fileMd: cstring; fileCap: cint; recMd: cstring; recCap: cint; fileLen, recLen: ptr cint): cint {.qh.}
 proc qexhip_io_write_gauge(path: cstring; lat: ptr cint; g: ptr cdouble; prec: cchar; fileMd, recMd: cstring): cint {.qh.}
 

@@ -1097,6 +1097,41 @@ class ResidentMD:
     def restore_links(self):
         check(lib().qexhip_md_restore_links(self.ctx._h))
 
+    def reunit_links(self):
+        """g.projectSU on the resident links (qexhip_gauge_reunit)"""
+        check(lib().qexhip_gauge_reunit(self.ctx._h))
+
+    # ---- HISQ molecular dynamics (src/examples/hisqhmc.nim) on the resident fields: qexhip_md_hisq_* ----
+    def hisq_prepare(self, antiperiodic=None, phases=None, set_links=True):
+        """smearRephase (hisqhmc.nim:405-414) on the resident thin links, which stay as they are: the HISQ closure is built from a
+        phased copy on the device (defaults: t antiperiodic, QEX's staggered phases); set_links also hands su, sul to the operator"""
+        ap = (C.c_int * 4)(*[int(bool(v)) for v in antiperiodic]) if antiperiodic is not None else None
+        ph = (C.c_int * 4)(*[int(v) for v in phases]) if phases is not None else None
+        check(lib().qexhip_md_hisq_prepare(self.ctx._h, ap, ph, 1 if set_links else 0))
+
+    def hisq_fforce(self, psi_ids, scale, t):
+        """fermionForce (hisqhmc.nim:496-539) for the resident vectors psi_ids, left on the device (hisq_force()), and p += t f"""
+        n = len(psi_ids)
+        check(lib().qexhip_md_hisq_fforce(self.ctx._h, n, (C.c_int * n)(*[int(v) for v in psi_ids]),
+                                          (C.c_double * n)(*[float(v) for v in scale]), float(t)))
+
+    def hisq_fforce_solve(self, phi_ids, mass, scale, r2req, maxits, t):
+        """the same with psi_k = D(mass_k)^-1 phi_k solved first on the operator's current links (lock-step batches of four);
+        returns the iteration counts"""
+        n = len(phi_ids)
+        rq = [float(r2req)] * n if np.isscalar(r2req) else [float(v) for v in r2req]
+        its = (C.c_int * n)()
+        check(lib().qexhip_md_hisq_fforce_solve(self.ctx._h, n, (C.c_int * n)(*[int(v) for v in phi_ids]),
+                                                (C.c_double * n)(*[float(v) for v in mass]), (C.c_double * n)(*[float(v) for v in scale]),
+                                                (C.c_double * n)(*rq), int(maxits), float(t), its))
+        return list(its)
+
+    def hisq_force(self):
+        """the last force of hisq_fforce / hisq_fforce_solve, [vol][4][3][3][2]"""
+        f = np.zeros((self.ctx.vol, 4, 3, 3, 2))
+        check(lib().qexhip_md_hisq_force_get(self.ctx._h, _p(f)))
+        return f
+
 
 def reunit(ctx, g):
     """g.projectSU in place (gaugeUtils.nim:1333-1334)"""
