@@ -111,6 +111,7 @@ class HisqHMC:
             its, _ = self.ctx.dev_solve_batch([self.psi], [self.phi], [-self.mass], ACTION_TOL, MAXITS)
             fermion = 0.5 * self.ctx.dev_norm2(self.psi)
         self.iters["action"] += its[0]
+        self.terms = (kinetic, gauge, fermion)                       # what the line below prints, for callers that drive the class
         print("kinetic = %r, gauge = %r, fermion = %r" % (kinetic, gauge, fermion))
         return kinetic + gauge + fermion
 

@@ -1,7 +1,11 @@
 """HISQ molecular dynamics resident on the device (qexhip_md_hisq_*, ResidentMD.hisq_*, examples/hisqhmc.py) against the
 host-pointer entries, which tests/test_smear.py holds to the oracle: the closure built from the resident links is the one built
 from a host field, the resident force is the host-pointer force bit for bit, and a trajectory of the example is the same
-trajectory on either path.  Observed figures are printed (pytest -s)."""
+trajectory on either path.  Observed figures are printed (pytest -s).
+Everything here compares the library with itself.  The trajectory as a whole (schedule, heatbath, the three energy terms, link
+update, reunit / revert, accept/reject stream) is held to the oracle replay of hisqhmc.nim by tests/test_gpu_hisq_hmc.py, and the
+pairing of the force with the action it integrates (odd-site sign, hop-3 term, TAH(F u^+), the step factor -1/2 dt / m) by the
+gradient and dH ~ dt^2 tests there (product) and in tests/test_hisq_hmc_ref.py (oracle, no GPU)."""
 import ctypes as C
 import functools
 import os
