@@ -362,6 +362,23 @@ int qexhip_dev_solve_xx_multi(qexhip_handle h, const int *x_ids, int b_id, const
 int qexhip_dev_solve_xx_multi_sloppy(qexhip_handle h, const int *x_ids, int b_id, const double *shifts, int nmass, double r2req,
                                      int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2, int *nupdates,
                                      int *refine_iters);
+/* Rational functions of the one-parity operator (the rooted staggered action; restates the rooted field of
+ * src/mcmc/fields/staggeredFields.nim:58-95,191-230 on M^+M, see DESIGN.md "Rooted HISQ").
+ *   M^+M = m^2 - D_eo D_oe on the even sites (par_even; parities swapped otherwise) = A(m)/4, A the operator of qexhip_dev_op_xx.
+ *   r(x) = f0 + sum_{k<nterm} alpha[k] / (x + beta[k]).
+ * out[par] = r(M^+M) b[par]; the other parity of out is zeroed.  ONE multi-shift solve: the terms are sorted by beta, the base
+ * mass is m_0 = sqrt(mass^2 + beta_min), the shifts are sigma_k = 4 (beta_k - beta_min) in the convention of
+ * qexhip_dev_solve_xx_multi ((A(m_0) + sigma_k) y_k = b), and out = f0 b + sum_k 4 alpha[k] y_k.  No y_k is ever stored: the update
+ * kernel accumulates the sum (2 vector streams per shift instead of 4) and the workspace is nterm search directions plus work
+ * fields.  fp64 only.  Stop criterion: the BASE system's iterated residual |r_0|^2 <= r2req |b|^2, as in the fp64 multi-shift
+ * solve; iters and hist are bit for bit those of qexhip_dev_solve_xx_multi with shifts [m_0, sigma_1, ...].
+ * QEXHIP_ERR_ARG before anything is launched: nterm outside 1..32, mass^2 + beta_min <= 0, non-finite mass / f0 / alpha / beta,
+ * out_id == b_id, unknown ids, NULL arrays.  beta[k] = 0 and repeated beta are legal.  t-sharded: collective.
+ * qexhip_stag_rational_xx is the host-pointer twin (b up, out down; out != b). */
+int qexhip_dev_rational_xx(qexhip_handle h, int out_id, int b_id, double mass, double f0, int nterm, const double *alpha,
+                           const double *beta, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);
+int qexhip_stag_rational_xx(qexhip_handle h, double *out, const double *b, double mass, double f0, int nterm, const double *alpha,
+                            const double *beta, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);
 
 /* Free the multi-shift solvers' persistent workspace (up to 3 x nmass full fields kept between solves; QEX allocates its
  * ps / ys per call with newOneOf and leaves them to the GC, src/solvers/cgm.nim:120-131, src/physics/stagSolve.nim:376-381).
@@ -916,13 +933,20 @@ int qexhip_md_restore_links(qexhip_handle h);
  *       f = TAH(ff u^+) with the phased u, and updateMomentum (:558-560) p += t f in the pass that stores f.
  *   md_hisq_fforce_solve: the same with psi_k = D(mass[k])^-1 phi_k (Staggered.solve, :541-545) solved first, in lock-step
  *       batches of at most four on the operator's current links; iters (nullable) receives the iteration counts.
- *   md_hisq_force_get: the last f of those two, [vol][4][3][3][2] (tests, host integrators); QEXHIP_ERR_STATE if there is none.
+ *   md_hisq_fforce_rational: the force of S = 1/2 Re<phi, r(M^+M) phi>_even with r as in qexhip_dev_rational_xx (the rooted branch
+ *       of stagForce, mcmc/fields/staggeredFields.nim:434-467): ONE multi-shift solve on phi.even (mapping as there; sloppy = 1:
+ *       the mixed-precision multi-shift solve, 2 runs single), m_k = sqrt(mass^2 + beta[k]), psi_k = D(m_k)^-1 phi with phi.odd = 0,
+ *       i.e. psi_k.even = 4 m_k y_k, psi_k.odd = -D_oe psi_k.even / m_k, then md_hisq_fforce with scale_k = alpha[k] / m_k.  f0
+ *       contributes nothing.  iters (nullable): the iterations of the one solve.  QEXHIP_ERR_ARG as qexhip_dev_rational_xx.
+ *   md_hisq_force_get: the last f of those three, [vol][4][3][3][2] (tests, host integrators); QEXHIP_ERR_STATE if there is none.
  * QEXHIP_ERR_ARG (n < 1, unknown or repeated field ids, NULL arrays) and QEXHIP_ERR_STATE (no resident links, no momenta, no
  * prepare) are returned before anything is launched.  t-sharded: collective. */
 int qexhip_md_hisq_prepare(qexhip_handle h, const int antiperiodic[4], const int phases[4], int set_links);
 int qexhip_md_hisq_fforce(qexhip_handle h, int n, const int *psi_ids, const double *scale, double t);
 int qexhip_md_hisq_fforce_solve(qexhip_handle h, int n, const int *phi_ids, const double *mass, const double *scale, const double *r2req,
                                 int maxits, double t, int *iters);
+int qexhip_md_hisq_fforce_rational(qexhip_handle h, int phi_id, double mass, int nterm, const double *alpha, const double *beta,
+                                   double r2req, int maxits, int sloppy, double t, int *iters);
 int qexhip_md_hisq_force_get(qexhip_handle h, double *f);
 
 /* ---------------- SciDAC/LIME gauge files (host only, no handle) ----------------

@@ -138,6 +138,16 @@ class Context {
     if (rIds.size() != xIds.size() || rIds.size() != m2.size()) throw std::invalid_argument("devOpXXHalfBatch: sizes differ");
     check(qexhip_dev_op_xx_half_batch(h, (int)rIds.size(), rIds.data(), xIds.data(), m2.data(), parEven ? 1 : 0));
   }
+  // out[par] = r(M^+M) b[par] on resident fields, r(x) = f0 + sum_k alpha_k / (x + beta_k): one accumulating multi-shift solve
+  // (qexhip_dev_rational_xx); returns the iterations of the base system
+  int devRationalXX(int outId, int bId, double mass, double f0, const std::vector<double> &alpha, const std::vector<double> &beta,
+                    double r2req, int maxits, bool parEven = true) {
+    if (alpha.size() != beta.size()) throw std::invalid_argument("devRationalXX: sizes differ");
+    int its = 0;
+    check(qexhip_dev_rational_xx(h, outId, bId, mass, f0, (int)alpha.size(), alpha.data(), beta.data(), r2req, maxits, parEven ? 1 : 0,
+                                 &its, nullptr, 0));
+    return its;
+  }
   static int deviceCount() { int n = 0; check(qexhip_device_count(&n)); return n; }
 };
 
@@ -187,6 +197,18 @@ class Staggered {
       check(qexhip_stag_solve_xx(c_.h, r.data(), x.data(), m, sp.r2req, sp.maxits, parEven ? 1 : 0, &its, &fin, hist.data(), histcap));
     });
     sp.r2 = fin;
+    sp.r2hist.assign(hist.begin(), hist.begin() + (histcap > 0 ? std::min(histcap, its + 1) : 0));
+  }
+  // r <- r(M^+M) x on one parity for host fields (qexhip_stag_rational_xx; fp64 whatever sp.sloppySolve says)
+  void rationalXX(Field &r, const Field &x, double m, double f0, const std::vector<double> &alpha, const std::vector<double> &beta,
+                  SolverParams &sp, bool parEven = true, int histcap = 0) {
+    if (alpha.size() != beta.size()) throw std::invalid_argument("rationalXX: sizes differ");
+    int its = 0;
+    std::vector<double> hist(histcap > 0 ? histcap : 1);
+    timed(sp, its, [&] {
+      check(qexhip_stag_rational_xx(c_.h, r.data(), x.data(), m, f0, (int)alpha.size(), alpha.data(), beta.data(), sp.r2req, sp.maxits,
+                                    parEven ? 1 : 0, &its, hist.data(), histcap));
+    });
     sp.r2hist.assign(hist.begin(), hist.begin() + (histcap > 0 ? std::min(histcap, its + 1) : 0));
   }
   void solveEE(Field &r, const Field &x, double m, SolverParams &sp, int histcap = 0) { solveXX(r, x, m, sp, true, histcap); }
@@ -522,6 +544,13 @@ class ResidentMD {
                                    const std::vector<double> &r2req, int maxits, double t) {
     std::vector<int> its(phiIds.size(), 0);
     check(qexhip_md_hisq_fforce_solve(c_.h, (int)phiIds.size(), phiIds.data(), mass.data(), scale.data(), r2req.data(), maxits, t, its.data()));
+    return its;
+  }
+  // the rooted force: r(x) = f0 + sum_k alpha_k / (x + beta_k) of M^+M, every pole's vector from one multi-shift solve
+  int hisqFforceRational(int phiId, double mass, const std::vector<double> &alpha, const std::vector<double> &beta, double r2req,
+                         int maxits, double t, int sloppy = 0) {
+    int its = 0;
+    check(qexhip_md_hisq_fforce_rational(c_.h, phiId, mass, (int)alpha.size(), alpha.data(), beta.data(), r2req, maxits, sloppy, t, &its));
     return its;
   }
   void hisqForce(Field &f) { check(qexhip_md_hisq_force_get(c_.h, f.data())); }

@@ -203,6 +203,9 @@ SYMBOLS = [
     ("qexhip_md_hisq_prepare", _ci, [_vp, _pi, _pi, _ci]),
     ("qexhip_md_hisq_fforce", _ci, [_vp, _ci, _pi, _pd, _cd]),
     ("qexhip_md_hisq_fforce_solve", _ci, [_vp, _ci, _pi, _pd, _pd, _pd, _ci, _cd, _pi]),
+    ("qexhip_md_hisq_fforce_rational", _ci, [_vp, _ci, _cd, _ci, _pd, _pd, _cd, _ci, _ci, _cd, _pi]),
+    ("qexhip_dev_rational_xx", _ci, [_vp, _ci, _ci, _cd, _cd, _ci, _pd, _pd, _cd, _ci, _ci, _pi, _vp, _ci]),
+    ("qexhip_stag_rational_xx", _ci, [_vp, _vp, _vp, _cd, _cd, _ci, _pd, _pd, _cd, _ci, _ci, _pi, _vp, _ci]),
     ("qexhip_md_hisq_force_get", _ci, [_vp, _vp]),
     ("qexhip_io_metadata", _ci, [C.c_char_p, C.c_char_p, _ci, C.c_char_p, _ci, _pi, _pi]),
     ("qexhip_io_crc32", _ci, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint)]),   # data pointer, not a handle

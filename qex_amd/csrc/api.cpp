@@ -5,6 +5,7 @@
 #include <string>
 #include "../../include/qexhip.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
@@ -801,6 +802,33 @@ extern "C" int qexhip_dev_solve_xx_multi_sloppy(qexhip_handle c, const int *x_id
   std::vector<DevField *> xp(nmass);
   CHK(find_solve_fields(c, "dev_solve_xx_multi_sloppy", true, nmass, x_ids, b_id, xp.data(), &fb));
   return solve_xx_multi_sloppy_dev(c, xp, *fb, shifts, nmass, r2req, maxits, par_even, iters, r2_over_b2, nupdates, refine_iters);
+}
+
+// out[par] = r(M^+M) b[par], r(x) = f0 + sum_k alpha_k / (x + beta_k), by the accumulating multi-shift solve (multishift.hip).  Every
+// refusal comes before anything is launched or staged
+extern "C" int qexhip_dev_rational_xx(qexhip_handle c, int out_id, int b_id, double mass, double f0, int nterm, const double *alpha,
+                                      const double *beta, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap) {
+  if (!c) return QEXHIP_ERR_ARG;
+  double shifts[CGM_MAXM];
+  int order[CGM_MAXM];
+  CHK(rational_map("dev_rational_xx", mass, nterm, alpha, beta, shifts, order));
+  if (!std::isfinite(f0)) { qexhip_set_error("dev_rational_xx: f0 is not finite"); return QEXHIP_ERR_ARG; }
+  DevField *fo, *fb;
+  CHK(find_solve_fields(c, "dev_rational_xx", false, 1, &out_id, b_id, &fo, &fb));
+  HIPCHK(hipSetDevice(c->device));
+  return rational_xx_dev(c, *fo, *fb, mass, f0, nterm, alpha, beta, r2req, maxits, par_even, iters, hist, histcap);
+}
+extern "C" int qexhip_stag_rational_xx(qexhip_handle c, double *out, const double *b, double mass, double f0, int nterm, const double *alpha,
+                                       const double *beta, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap) {
+  if (!c || !out || !b) return QEXHIP_ERR_ARG;
+  double shifts[CGM_MAXM];
+  int order[CGM_MAXM];
+  CHK(rational_map("stag_rational_xx", mass, nterm, alpha, beta, shifts, order));
+  if (!std::isfinite(f0)) { qexhip_set_error("stag_rational_xx: f0 is not finite"); return QEXHIP_ERR_ARG; }
+  DevField *fb, *fx;
+  CHK(stage_in(c, out, b, 0, &fx, &fb));
+  CHK(rational_xx_dev(c, *fx, *fb, mass, f0, nterm, alpha, beta, r2req, maxits, par_even, iters, hist, histcap));
+  return field_download(c, *fx, out);
 }
 
 // The multi-shift solvers keep up to 3 x nmass full fields (search directions, per-parity and host-entry solutions) between
@@ -1684,6 +1712,20 @@ extern "C" int qexhip_md_hisq_fforce_solve(qexhip_handle c, int n, const int *ph
   if (!c->W) { qexhip_set_error("md_hisq_fforce_solve: the operator has no links (qexhip_md_hisq_prepare with set_links)"); return QEXHIP_ERR_STATE; }
   HIPCHK(hipSetDevice(c->device));
   return md_hisq_fforce_solve(c, n, f.data(), mass, scale, r2req, maxits, t, iters);
+}
+extern "C" int qexhip_md_hisq_fforce_rational(qexhip_handle c, int phi_id, double mass, int nterm, const double *alpha, const double *beta,
+                                              double r2req, int maxits, int sloppy, double t, int *iters) {
+  if (!c) return QEXHIP_ERR_ARG;
+  double shifts[CGM_MAXM];
+  int order[CGM_MAXM];
+  CHK(rational_map("md_hisq_fforce_rational", mass, nterm, alpha, beta, shifts, order));
+  CHK(sloppy_check(c, sloppy));
+  DevField *phi;
+  CHK(find_field(c, phi_id, &phi));
+  CHK(md_hisq_check(c, "md_hisq_fforce_rational"));
+  if (!c->W) { qexhip_set_error("md_hisq_fforce_rational: the operator has no links (qexhip_md_hisq_prepare with set_links)"); return QEXHIP_ERR_STATE; }
+  HIPCHK(hipSetDevice(c->device));
+  return md_hisq_fforce_rational(c, *phi, mass, nterm, alpha, beta, r2req, maxits, sloppy, t, iters);
 }
 extern "C" int qexhip_md_hisq_force_get(qexhip_handle c, double *f) {
   if (!c || !f) return QEXHIP_ERR_ARG;

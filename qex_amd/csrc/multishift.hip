@@ -8,7 +8,9 @@
 #include "qexhip_internal.h"
 #include "reduce.h"
 #include "full_solve.h"
+#include "../../include/qexhip.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 struct CgmScal {
@@ -16,6 +18,8 @@ struct CgmScal {
   double alpha, beta, alphaim1, betaim1;
   double sg[CGM_MAXM], zi[CGM_MAXM], zim1[CGM_MAXM], axz[CGM_MAXM], zip1[CGM_MAXM], bzz[CGM_MAXM];
   double2 *xs[CGM_MAXM], *ps[CGM_MAXM];
+  double cs[CGM_MAXM];                 // the accumulating solve: weight of shift k in the sum; sum: where it is kept
+  double2 *sum;
 };
 
 // after op.apply and redot: alpha, r -= alpha Ap, x += alpha p   (cgm.nim:226-233).  With ndot > 0 (single rank)
@@ -118,6 +122,68 @@ __global__ void __launch_bounds__(256) k_cgm_update(const double2 *r, size_t n, 
     }
   }
 }
+// The accumulating form of k_cgm_update (qexhip_dev_rational_xx): no x_k exists.  S += sum_{k>=1} cs[k] axz[k] p_k is read and written
+// once, every p_k once: 2 streams per shift plus S and r instead of 4 per shift.  Same pending / cont protocol.  The shifts go in
+// groups of four so that a group's loads are in flight together (the stores of one p_k may alias the next load as far as the
+// compiler can tell).
+__global__ void __launch_bounds__(256) k_cgm_update_sum(const double2 *r, size_t n, const CgmScal *m) {
+  if (!m->pending) return;
+  const int cont = m->cont, nm = m->nmass;
+  const double beta = m->beta;
+  double2 *const S = m->sum;
+  // the per-shift scalars and pointers go to LDS once: read from *m inside the loop they would be re-fetched after every store
+  __shared__ double w_s[CGM_MAXM], z_s[CGM_MAXM], b_s[CGM_MAXM];
+  __shared__ double2 *p_s[CGM_MAXM];
+  if ((int)threadIdx.x < nm) {
+    const int k = threadIdx.x;
+    w_s[k] = m->cs[k] * m->axz[k]; z_s[k] = m->zip1[k]; b_s[k] = m->bzz[k]; p_s[k] = m->ps[k];
+  }
+  __syncthreads();
+  double2 *const p0 = p_s[0];
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const double2 rv = r[i];
+    if (cont) {
+      double2 pv = p0[i];
+      p0[i] = make_double2(rv.x + beta * pv.x, rv.y + beta * pv.y);
+    }
+    if (nm < 2) continue;
+    double2 sv = S[i];
+    for (int k0 = 1; k0 < nm; k0 += 4) {
+      const int kn = min(4, nm - k0);
+      double2 pv[4];
+      for (int j = 0; j < 4; j++) if (j < kn) pv[j] = p_s[k0 + j][i];
+      for (int j = 0; j < 4; j++) if (j < kn) {
+        const int k = k0 + j;
+        const double w = w_s[k];
+        sv.x += w * pv[j].x; sv.y += w * pv[j].y;
+        if (cont) {
+          const double z = z_s[k], b = b_s[k];
+          p_s[k][i] = make_double2(z * rv.x + b * pv[j].x, z * rv.y + b * pv[j].y);
+        }
+      }
+    }
+    S[i] = sv;
+  }
+}
+// r := b; S := 0; the base solution := 0; ps[k] := r -- the start of the accumulating solve
+__global__ void __launch_bounds__(256) k_cgm_start_sum(double2 *r, double2 *x0, const double2 *b, size_t n, const CgmScal *m) {
+  const int nm = m->nmass;
+  double2 *const S = m->sum;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const double2 bv = b[i];
+    r[i] = bv;
+    x0[i] = make_double2(0, 0);
+    S[i] = make_double2(0, 0);
+    for (int k = 0; k < nm; k++) m->ps[k][i] = bv;
+  }
+}
+// the closing launch of the accumulating solve: out := f0 b + c0 x_0 + S  (S lives in out)
+__global__ void __launch_bounds__(256) k_cgm_sum_close(double2 *out, const double2 *b, const double2 *x0, size_t n, double f0, double c0) {
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const double2 bv = b[i], xv = x0[i], sv = out[i];
+    out[i] = make_double2(f0 * bv.x + c0 * xv.x + sv.x, f0 * bv.y + c0 * xv.y + sv.y);
+  }
+}
 __global__ void k_cgm_init(CgScal *s, const double *dscal, double r2req, int maxits, double *hist, int histcap) {
   s->b2 = dscal[0];
   s->r2 = dscal[0];  // r := b, r2 = b2 (cgm.nim:169-175)
@@ -163,8 +229,11 @@ int pool_field(qexhip_ctx *c, int idx, DevField **f) {
   return 0;
 }
 
-int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts,
-                       int nmass, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap) {
+// The multi-shift CG.  sum == nullptr: every shift's solution into xs[k].  Otherwise the accumulating form: xs[0] is the base
+// solution, sum[par] collects sum_{k>=1} cs[k] x_k without any x_k (k_cgm_update_sum); the scalar side -- k_cgm_base, k_cgm_close,
+// the reductions, the sharded branches -- is the same code, so count and history are bit for bit the same.
+static int cgm_solve(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts, int nmass, double r2req,
+                     int maxits, int par_even, int *iters, double *hist, int histcap, DevField *sum, const double *cs) {
   if (nmass < 1 || nmass > CGM_MAXM) { qexhip_set_error("multishift: 1 <= nmass <= %d", CGM_MAXM); return -1; }
   c->cg_resume.valid = 0;                 // the device CG state and the history buffer are taken over
   const int par = par_even ? 0 : 1;
@@ -192,14 +261,21 @@ int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, 
   for (int k = 0; k < nmass; k++) {
     hm->sg[k] = (k == 0) ? 0.0 : shifts[k];
     hm->zi[k] = 1.0; hm->zim1[k] = 1.0;
-    hm->xs[k] = xs[k]->par(par);
+    hm->xs[k] = sum ? xs[0]->par(par) : xs[k]->par(par);
     hm->ps[k] = ps[k]->par(par);
+    hm->cs[k] = sum ? cs[k] : 0.0;
   }
+  hm->sum = sum ? sum->par(par) : nullptr;
   HIPCHK(hipMemcpyAsync(g_cgm_dev, hm, sizeof(*hm), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));            // the pinned page is reused by read_cg below
   const double mass = shifts[0], m2 = mass * mass;
-  for (int k = 0; k < nmass; k++) CHK(blas_zero(c, *xs[k], 1 - par));   // the other parity of every solution
-  k_cgm_start<<<nb, 256, 0, c->stream>>>(r->par(par), b.par(par), n, g_cgm_dev);   // q := z ; ps[m] := p (cgm.nim:196-207)
+  if (sum) {
+    CHK(blas_zero(c, *sum, 1 - par));
+    k_cgm_start_sum<<<nb, 256, 0, c->stream>>>(r->par(par), xs[0]->par(par), b.par(par), n, g_cgm_dev);
+  } else {
+    for (int k = 0; k < nmass; k++) CHK(blas_zero(c, *xs[k], 1 - par));   // the other parity of every solution
+    k_cgm_start<<<nb, 256, 0, c->stream>>>(r->par(par), b.par(par), n, g_cgm_dev);   // q := z ; ps[m] := p (cgm.nim:196-207)
+  }
   HIPCHK(hipGetLastError());
   CHK(blas_norm2(c, b, par, &c->dscal[0]));
   k_cgm_init<<<1, 1, 0, c->stream>>>(c->cg, c->dscal, r2req, maxits, c->hist, c->histcap);
@@ -230,9 +306,15 @@ int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, 
         k_cgm_close<<<1, 256, 0, c->stream>>>(r2p, nr2, c->partials, ndot, c->cg, g_cgm_dev, c->hist, c->histcap);
         HIPCHK(hipGetLastError());
       }
-      ScopedTimer tm(c, "cgm_update", c->stream);
-      k_cgm_update<<<nb, 256, 0, c->stream>>>(r->par(par), n, g_cgm_dev);
-      HIPCHK(hipGetLastError());
+      if (sum) {
+        ScopedTimer tm(c, "cgm_update_sum", c->stream);
+        k_cgm_update_sum<<<nb, 256, 0, c->stream>>>(r->par(par), n, g_cgm_dev);
+        HIPCHK(hipGetLastError());
+      } else {
+        ScopedTimer tm(c, "cgm_update", c->stream);
+        k_cgm_update<<<nb, 256, 0, c->stream>>>(r->par(par), n, g_cgm_dev);
+        HIPCHK(hipGetLastError());
+      }
     }
     CHK(comm_agree_post(c));
     CHK(read_cg(c, &st));
@@ -244,6 +326,52 @@ int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, 
     HIPCHK(hipMemcpyAsync(hist, c->hist, sizeof(double) * nh, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
+  return 0;
+}
+
+int solve_xx_multi_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevField &b, const double *shifts,
+                       int nmass, double r2req, int maxits, int par_even, int *iters, double *hist, int histcap) {
+  return cgm_solve(c, xs, b, shifts, nmass, r2req, maxits, par_even, iters, hist, histcap, nullptr, nullptr);
+}
+
+// The terms of r(x) = f0 + sum_k alpha_k / (x + beta_k) as the multi-shift solver takes them: sorted by beta, base mass
+// m_0 = sqrt(m^2 + beta_min), shifts[0] = m_0, shifts[k] = 4 (beta_k - beta_min); order[k]: the caller's index of sorted term k.
+// QEXHIP_ERR_ARG for everything the rational entries refuse.
+int rational_map(const char *who, double mass, int nterm, const double *alpha, const double *beta, double *shifts, int *order) {
+  if (!alpha || !beta) { qexhip_set_error("%s: null argument", who); return QEXHIP_ERR_ARG; }
+  if (nterm < 1 || nterm > CGM_MAXM) { qexhip_set_error("%s: 1 <= nterm <= %d (nterm = %d)", who, CGM_MAXM, nterm); return QEXHIP_ERR_ARG; }
+  if (!std::isfinite(mass)) { qexhip_set_error("%s: mass is not finite", who); return QEXHIP_ERR_ARG; }
+  for (int k = 0; k < nterm; k++)
+    if (!std::isfinite(alpha[k]) || !std::isfinite(beta[k])) { qexhip_set_error("%s: term %d is not finite", who, k); return QEXHIP_ERR_ARG; }
+  for (int k = 0; k < nterm; k++) order[k] = k;
+  std::stable_sort(order, order + nterm, [&](int a, int b) { return beta[a] < beta[b]; });
+  const double bmin = beta[order[0]], m02 = mass * mass + bmin;
+  if (!(m02 > 0.0)) { qexhip_set_error("%s: m^2 + beta_min = %g is not positive", who, m02); return QEXHIP_ERR_ARG; }
+  shifts[0] = std::sqrt(m02);
+  for (int k = 1; k < nterm; k++) shifts[k] = 4.0 * (beta[order[k]] - bmin);
+  return 0;
+}
+
+// out[par] = r(M^+M) b[par] = f0 b + sum_k 4 alpha_k y_k with (A(m_0) + sigma_k) y_k = b, the other parity of out zeroed.  The sum is
+// accumulated in out itself; the base solution is the work field WK_Y.  Stops on the base system's iterated residual.
+int rational_xx_dev(qexhip_ctx *c, DevField &out, DevField &b, double mass, double f0, int nterm, const double *alpha, const double *beta,
+                    double r2req, int maxits, int par_even, int *iters, double *hist, int histcap) {
+  double shifts[CGM_MAXM], cs[CGM_MAXM];
+  int order[CGM_MAXM];
+  CHK(rational_map("rational_xx", mass, nterm, alpha, beta, shifts, order));
+  if (!std::isfinite(f0)) { qexhip_set_error("rational_xx: f0 is not finite"); return QEXHIP_ERR_ARG; }
+  if (out.d == b.d) { qexhip_set_error("rational_xx: the output field is the source field"); return QEXHIP_ERR_ARG; }
+  for (int k = 0; k < nterm; k++) cs[k] = 4.0 * alpha[order[k]];
+  DevField *x0;
+  CHK(get_work(c, WK_Y, &x0));
+  std::vector<DevField *> xs(1, x0);
+  CHK(cgm_solve(c, xs, b, shifts, nterm, r2req, maxits, par_even, iters, hist, histcap, &out, cs));
+  const int par = par_even ? 0 : 1;
+  const size_t n = (size_t)c->g.ntile * 192;
+  const int nb = (int)std::min<size_t>((n + 255) / 256, 2048);
+  k_cgm_sum_close<<<nb, 256, 0, c->stream>>>(out.par(par), b.par(par), x0->par(par), n, f0, cs[0]);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -513,6 +513,10 @@ int solve_xx_multi_sloppy_dev(qexhip_ctx *c, std::vector<DevField *> &xs, DevFie
 // persistent multi-shift workspace (multishift.hip): search directions, per-parity solutions, host-entry solutions
 enum { POOL_PS = 0, POOL_YS = 32, POOL_XS = 64, POOL_REF = 96 };   // POOL_REF: 4 corrections + 4 residuals of the sloppy solve's refinement
 int pool_field(qexhip_ctx *c, int idx, DevField **f);
+// rational functions of M^+M (multishift.hip): the terms as the multi-shift solver takes them, and the accumulating solve
+int rational_map(const char *who, double mass, int nterm, const double *alpha, const double *beta, double *shifts, int *order);
+int rational_xx_dev(qexhip_ctx *c, DevField &out, DevField &b, double mass, double f0, int nterm, const double *alpha, const double *beta,
+                    double r2req, int maxits, int par_even, int *iters, double *hist, int histcap);
 
 int solve_xx_deflated_dev(qexhip_ctx *c, EigBasis &B, int nev, DevField &x, DevField &b, double mass, double r2req, int maxits,
                           int sloppy, int *iters, double *r2_over_b2);
@@ -598,6 +602,8 @@ int md_hisq_check(qexhip_ctx *c, const char *who);                              
 int md_hisq_fforce(qexhip_ctx *c, int n, DevField *const *psi, const double *scale, double t);
 int md_hisq_fforce_solve(qexhip_ctx *c, int n, DevField *const *phi, const double *mass, const double *scale, const double *r2req, int maxits,
                          double t, int *iters);
+int md_hisq_fforce_rational(qexhip_ctx *c, DevField &phi, double mass, int nterm, const double *alpha, const double *beta, double r2req,
+                            int maxits, int sloppy, double t, int *iters);
 int md_hisq_force_get(qexhip_ctx *c, double *f_host);
 int hisq_outer13_dev(qexhip_ctx *c, int n, DevField *const *xs, const double *scale, double2 *CF, double2 *CL, int accumulate);
 int hisq_projtah_kick_dev(qexhip_ctx *c, double2 *F, const double2 *G, double2 *P, double t);

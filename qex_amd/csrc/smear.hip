@@ -1359,6 +1359,32 @@ int md_hisq_fforce_solve(qexhip_ctx *c, int n, DevField *const *phi, const doubl
   }
   return md_hisq_finish(c, st, t);
 }
+// The rooted force (mcmc/fields/staggeredFields.nim:434-467, the rooted branch of stagForce): the vectors of every pole of
+// r(x) = f0 + sum_k alpha_k / (x + beta_k) from ONE multi-shift solve on phi.even.  With (A(m_0) + sigma_k) y_k = phi.even
+// (rational_map), m_k = sqrt(m^2 + beta_k): psi_k = D(m_k)^-1 phi (phi.odd = 0) is psi_k.even = 4 m_k y_k,
+// psi_k.odd = -D_oe psi_k.even / m_k (one single sweep per pole), and its weight is alpha_k / m_k.  f0 has no gradient.
+int md_hisq_fforce_rational(qexhip_ctx *c, DevField &phi, double mass, int nterm, const double *alpha, const double *beta, double r2req,
+                            int maxits, int sloppy, double t, int *iters) {
+  double shifts[CGM_MAXM], scale[CGM_MAXM];
+  int order[CGM_MAXM];
+  CHK(rational_map("md_hisq_fforce_rational", mass, nterm, alpha, beta, shifts, order));
+  CHK(md_hisq_check(c, "md_hisq_fforce_rational"));
+  HisqState *st = (HisqState *)c->hisq;
+  st->S.scratch_begin();
+  st->md_force = false;
+  std::vector<DevField *> ys(nterm);
+  for (int k = 0; k < nterm; k++) CHK(pool_field(c, POOL_YS + k, &ys[k]));
+  if (sloppy) CHK(solve_xx_multi_sloppy_dev(c, ys, phi, shifts, nterm, r2req, maxits, 1, iters, nullptr, nullptr, nullptr));
+  else CHK(solve_xx_multi_dev(c, ys, phi, shifts, nterm, r2req, maxits, 1, iters, nullptr, 0));
+  for (int k = 0; k < nterm; k++) {
+    const double mk = std::sqrt(mass * mass + beta[order[k]]);
+    CHK(blas_scale(c, 4.0 * mk, *ys[k], 0));
+    CHK(op_stagD_pub(c, *ys[k], *ys[k], 1, 0.0, -1.0 / mk, 0.0));
+    scale[k] = alpha[order[k]] / mk;
+  }
+  CHK(hisq_outer13_dev(c, nterm, ys.data(), scale, st->CF, st->CL, 0));
+  return md_hisq_finish(c, st, t);
+}
 int md_hisq_force_get(qexhip_ctx *c, double *f_host) {
   HisqState *st = (HisqState *)c->hisq;
   if (!st || !st->md_force) { qexhip_set_error("md_hisq_force_get: no force yet (qexhip_md_hisq_fforce / _fforce_solve)"); return -3; }

@@ -173,7 +173,14 @@ proc qexhip_md_hisq_prepare(h: pointer; antiperiodic, phases: ptr cint; setLinks
 proc qexhip_md_hisq_fforce(h: pointer; n: cint; psiIds: ptr cint; scale: ptr cdouble; t: cdouble): cint {.qh.}
 proc qexhip_md_hisq_fforce_solve(h: pointer; n: cint; phiIds: ptr cint; mass, scale, r2req: ptr cdouble; maxits: cint; t: cdouble;
                                  iters: ptr cint): cint {.qh.}
+proc qexhip_md_hisq_fforce_rational(h: pointer; phiId: cint; mass: cdouble; nterm: cint; alpha, beta: ptr cdouble; r2req: cdouble;
+                                    maxits, sloppy: cint; t: cdouble; iters: ptr cint): cint {.qh.}
 proc qexhip_md_hisq_force_get(h: pointer; f: ptr cdouble): cint {.qh.}
+# r(M^+M) b, r(x) = f0 + sum_k alpha_k / (x + beta_k), by one accumulating multi-shift solve (the rooted action)
+proc qexhip_dev_rational_xx(h: pointer; outId, bId: cint; mass, f0: cdouble; nterm: cint; alpha, beta: ptr cdouble; r2req: cdouble;
+                            maxits, parEven: cint; iters: ptr cint; hist: ptr cdouble; histcap: cint): cint {.qh.}
+proc qexhip_stag_rational_xx(h: pointer; o, b: ptr cdouble; mass, f0: cdouble; nterm: cint; alpha, beta: ptr cdouble; r2req: cdouble;
+                             maxits, parEven: cint; iters: ptr cint; hist: ptr cdouble; histcap: cint): cint {.qh.}
 proc qexhip_io_metadata(path: cstring; fileMd: cstring; fileCap: cint; recMd: cstring; recCap: cint; fileLen, recLen: ptr cint): cint {.qh.}
 proc qexhip_io_write_gauge(path: cstring; lat: ptr cint; g: ptr cdouble; prec: cchar; fileMd, recMd: cstring): cint {.qh.}
 

@@ -244,6 +244,19 @@ class Context:
                                               1 if par_even else 0, C.byref(its), _p(hist), histcap))
         return its.value, hist[: min(histcap, its.value + 1)]
 
+    def dev_rational_xx(self, out_id, b_id, mass, f0, alpha, beta, r2req, maxits, par_even=True, histcap=0):
+        """out[par] = r(M^+M) b[par] on resident fields, r(x) = f0 + sum_k alpha_k / (x + beta_k), M^+M = m^2 - D_eo D_oe: one
+        accumulating multi-shift solve (qexhip_dev_rational_xx); returns (iterations, history of the base system)"""
+        n = len(alpha)
+        if len(beta) != n:
+            raise ValueError("dev_rational_xx: %d residues, %d poles" % (n, len(beta)))
+        its = C.c_int(0)
+        hist = np.zeros(max(histcap, 1))
+        check(lib().qexhip_dev_rational_xx(self._h, int(out_id), int(b_id), float(mass), float(f0), n,
+                                           (C.c_double * n)(*[float(v) for v in alpha]), (C.c_double * n)(*[float(v) for v in beta]),
+                                           float(r2req), int(maxits), 1 if par_even else 0, C.byref(its), _p(hist), histcap))
+        return its.value, hist[: min(histcap, its.value + 1)]
+
     def dev_solve_xx_sloppy(self, x_id, b_id, mass, r2req, maxits, par_even=True, sloppy=SloppySingle):
         """mixed-precision solveXX on resident fields (qexhip_dev_solve_xx_sloppy); returns (fp32 iterations, true r2/b2,
         reliable updates)"""
@@ -910,6 +923,24 @@ class Staggered:
         sp.iterations += its.value
         sp.r2hist = hist[: min(histcap, its.value + 1)] if histcap else None
 
+    def rationalXX(self, out, b, mass, rat, sp, parEven=True, histcap=0):
+        """out[par] = r(M^+M) b[par] for host arrays; rat: a qex_amd.rational.Rational or (f0, alpha, beta).  One accumulating
+        multi-shift solve in fp64 (qexhip_stag_rational_xx); sp.iterations / sp.r2hist as solveXX_multi"""
+        f0, alpha, beta = (rat.f0, rat.alpha, rat.beta) if hasattr(rat, "alpha") else rat
+        al = np.array([float(v) for v in alpha], dtype=np.float64)
+        be = np.array([float(v) for v in beta], dtype=np.float64)
+        if al.shape != be.shape:
+            raise ValueError("rationalXX: %d residues, %d poles" % (al.size, be.size))
+        if int(getattr(sp, "sloppySolve", SloppyNone)) != SloppyNone:
+            raise ValueError("rationalXX runs in fp64: the mixed-precision multi-shift solve refines every shift on its own solution "
+                             "and cannot accumulate")
+        its = C.c_int(0)
+        hist = np.zeros(max(histcap, 1))
+        check(lib().qexhip_stag_rational_xx(self.ctx._h, _p(out), _p(b), float(mass), float(f0), int(al.size), (C.c_double * al.size)(*al), (C.c_double * be.size)(*be),
+                                            float(sp.r2req), int(sp.maxits), 1 if parEven else 0, C.byref(its), _p(hist), histcap))
+        sp.iterations += its.value
+        sp.r2hist = hist[: min(histcap, its.value + 1)] if histcap else None
+
 
 def _deflate_args(deflate, nev, n):
     """the keywords deflate= / nev= of the batched solves, checked before any library call; returns nev (None -> deflate.nconv)"""
@@ -1126,8 +1157,20 @@ class ResidentMD:
                                                 (C.c_double * n)(*rq), int(maxits), float(t), its))
         return list(its)
 
+    def hisq_fforce_rational(self, phi_id, mass, alpha, beta, r2req, maxits, t, sloppy=0):
+        """the force of 1/2 Re<phi, r(M^+M) phi>_even, r(x) = f0 + sum_k alpha_k / (x + beta_k): every pole's vector from ONE
+        multi-shift solve on phi.even, weights alpha_k / sqrt(mass^2 + beta_k), and p += t f; returns the iterations"""
+        n = len(alpha)
+        if len(beta) != n:
+            raise ValueError("hisq_fforce_rational: %d residues, %d poles" % (n, len(beta)))
+        its = C.c_int(0)
+        check(lib().qexhip_md_hisq_fforce_rational(self.ctx._h, int(phi_id), float(mass), n, (C.c_double * n)(*[float(v) for v in alpha]),
+                                                   (C.c_double * n)(*[float(v) for v in beta]), float(r2req), int(maxits), int(sloppy),
+                                                   float(t), C.byref(its)))
+        return its.value
+
     def hisq_force(self):
-        """the last force of hisq_fforce / hisq_fforce_solve, [vol][4][3][3][2]"""
+        """the last force of hisq_fforce / hisq_fforce_solve / hisq_fforce_rational, [vol][4][3][3][2]"""
         f = np.zeros((self.ctx.vol, 4, 3, 3, 2))
         check(lib().qexhip_md_hisq_force_get(self.ctx._h, _p(f)))
         return f
