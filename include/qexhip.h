@@ -694,10 +694,13 @@ int qexhip_stag_links_info(qexhip_handle h, int *nlinks, int *compressed, double
  * rows 0,1 are stored exactly, row 2 as int16 multiples of one ulp of its rebuild +-conj(row0 x row1), and a link whose row 2 this
  * does not reproduce bit for bit is "escaped" (its row 2 is read from the 18 reals).  The operator is the 18-real one bit for bit,
  * so qexhip_stag_links_info reports format 0.  Taken when at most 1 % of the links escape; option "lossless" = 0 (or "recon"
- * = 0) keeps it off.  100 for the packed form of the same (option "lossless" = 2, the default): the residuals, 19 bits wide, sit in
+ * = 0) keeps it off.  100 for the packed form of the same (option "lossless" = 2): the residuals, 19 bits wide, sit in
  * bits 62..56 of the 12 reals of rows 0,1, which are constant for 2^-15 <= |v| < 2, and in one extra 4-byte word; a link with a real
  * outside that window is escaped too, and an escaped link is read whole from the 18 reals.  Above 1 % escaped the choice falls to
- * the 108-byte format under its own rule, then to 18 reals.  escaped = the links the last encoding escaped (0 if it did not run). */
+ * the 108-byte format under its own rule, then to 18 reals.  92 for the orthogonal form (option "lossless" = 3, the default): row 1's
+ * last element is rebuilt as well, from the orthogonality of rows 0 and 1 (two IEEE divisions by |a2|^2), so ten slots are stored;
+ * the residuals -- 20 bits for row 2, 23 for that element -- sit in the ten slots' payload bits and in an 8- and a 4-byte word.  Above
+ * 1 % escaped the choice falls to the packed form.  escaped = the links the last encoding escaped (0 if it did not run). */
 int qexhip_stag_links_storage(qexhip_handle h, int *bytes_per_link, long long *escaped);
 /* The residual format's encoder and decoder on the host, for n links of 18 doubles (3x3 complex, row-major, re/im): escaped[i] =
  * link i is escaped; row2[6 i ..] = its row 2 as decoded (the rebuild for an escaped link).  Either output may be null.  Needs no
@@ -705,13 +708,16 @@ int qexhip_stag_links_storage(qexhip_handle h, int *bytes_per_link, long long *e
 int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped, double *row2);
 /* The same for the packed form: decoded[18 i ..] = link i as decoded, all 18 reals. */
 int qexhip_link_packed_host(const double *links, int n, unsigned char *escaped, double *decoded);
+/* The same for the orthogonal form. */
+int qexhip_link_ortho_host(const double *links, int n, unsigned char *escaped, double *decoded);
 /* Options of a context.  Unknown names are an error (QEXHIP_ERR_ARG).
  *   "recon"        cap on the link compression (0 keep all 18 reals, 1 sign format only, 2 also the U(3) format; default 2),
  *                  effective at the next set_links (the fp32 copy of the sloppy solves: 0 keeps 18 reals, else the sign format
  *                  where it applies); 0 also keeps the lossless format off
  *   "lossless"     8-link operators that fit neither compressed format take a lossless format (qexhip_stag_links_storage) if at most
- *                  1 % of their links escape it.  2 (default): the packed 100-byte form, else the 108-byte residual format, else 18
- *                  reals; 1: the 108-byte format, else 18 reals; 0: 18 reals.  Effective at the next set_links
+ *                  1 % of their links escape it.  3 (default): the orthogonal 92-byte form, else as 2; 2: the packed 100-byte form, else
+ *                  the 108-byte residual format, else 18 reals; 1: the 108-byte format, else 18 reals; 0: 18 reals.  Effective at the
+ *                  next set_links
  *   "sloppy_check" the sloppy solves post their (device-gated) reliable-update launches every this many fp32 iterations, and
  *                  at maxits (default 4; 1: in the iteration that calls for an update)
  *   "half"         1: sloppy = 2 (SloppyHalf) iterates on 16-bit storage in the single-system solves of a one-rank context;

@@ -9,7 +9,7 @@ from .layout import Layout  # noqa: F401
 from .gauge import setBC, stagPhase, rephase, unit, synthetic_random_su3, synthetic_gaussian_vector  # noqa: F401
 from .gauge import getGaugeFixTransform, gaugeTransform, linkTrace  # noqa: F401
 from .staggered import (  # noqa: F401
-    Context, device_count, Staggered, SolverParams, newStag, newStag3, link_residual_host, link_packed_host, half_pack_host, half_unpack_host, plaq, gaugeForce, gaugeFlow, gaugeSet, gaugeFlowResident, flowEQ, flowMeasure, gaugeAction, gaugeUpdate, reunit, wline, ploops, s4_gauge, ResidentMD, HisqCoefs, HypCoefs, makeImpLinks, fat7lDeriv, EVEN, ODD, ALL,
+    Context, device_count, Staggered, SolverParams, newStag, newStag3, link_residual_host, link_packed_host, link_ortho_host, half_pack_host, half_unpack_host, plaq, gaugeForce, gaugeFlow, gaugeSet, gaugeFlowResident, flowEQ, flowMeasure, gaugeAction, gaugeUpdate, reunit, wline, ploops, s4_gauge, ResidentMD, HisqCoefs, HypCoefs, makeImpLinks, fat7lDeriv, EVEN, ODD, ALL,
     SloppyNone, SloppySingle, SloppyHalf, EigBasis, EigOpts, eig_check_opts, symeig_host,
 )
 from .stout import StoutSmear, newStoutSmear, stoutSmear, stoutSmearGetForce  # noqa: F401

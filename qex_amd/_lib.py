@@ -124,6 +124,7 @@ SYMBOLS = [
     ("qexhip_stag_links_storage", _ci, [_vp, _pi, C.POINTER(C.c_longlong)]),
     ("qexhip_link_residual_host", _ci, [_vp, _ci, _vp, _vp]),
     ("qexhip_link_packed_host", _ci, [_vp, _ci, _vp, _vp]),
+    ("qexhip_link_ortho_host", _ci, [_vp, _ci, _vp, _vp]),
     ("qexhip_set_option", _ci, [_vp, C.c_char_p, _ci]),
     ("qexhip_fat7_deriv", _ci, [_vp, _vp, _vp, _vp, _vp, _cd, _vp]),
     ("qexhip_hisq_force", _ci, [_vp, _vp, _vp, _vp, _vp]),

@@ -6,7 +6,7 @@
 // wavefront per 64-site tile: the wavefront streams its contiguous block of links (72 KiB /
 // 144 KiB) with 16-byte loads, neighbour vectors come from the opposite-parity field with
 // unit-stride (x), row-stride (y), plane-stride (z) or slice-stride (t) access, all coalesced.
-// HBM-bound: 1248 B and 570 flop per site (1-hop; 960 B on the lossless 108-byte links, 898 B on their packed form, link_residual.h), no MFMA on purpose.
+// HBM-bound: 1248 B and 570 flop per site (1-hop; 960 B on the lossless 108-byte links, 898 B on their packed form, 834 B on the orthogonal form, link_residual.h), no MFMA on purpose.
 //
 // Two kernels with disjoint roles (round 6; rounds 4-5 had one kernel with seven template parameters) around one dslash_body; the link
 // fetch is LinkCursor's (dslash_core.h), the workgroup -> site mapping sweep_site's (site_index.h), shared with the batched and fp32 sweeps:
@@ -29,8 +29,8 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 
 struct DslashArgs {
   Geom g;
-  const double2 *W;      // links of the output parity (RECON 1, 2: rows 0,1 (+ det) only, [tile][dir][6|7][64]; 3, 4: link_residual.h rows)
-  const unsigned long long *S;   // RECON 1: sign masks [tile][dir], bit = lane; 3, 4: [tile][dir][sign, escape] (S[-2]: this parity's W)
+  const double2 *W;      // links of the output parity (RECON 1, 2: rows 0,1 (+ det) only, [tile][dir][6|7][64]; 3, 4, 5: link_residual.h rows)
+  const unsigned long long *S;   // RECON 1: sign masks [tile][dir], bit = lane; 3, 4, 5: [tile][dir][sign, escape] (S[-2]: this parity's W)
   const double2 *in;     // hop source (opposite parity half)
   double2 *out;          // output parity half
   const double2 *rin;    // a-term
@@ -131,6 +131,10 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
         const size_t fr = ((size_t)L.tile * NDIR + 2 * pr) * 576 + L.lane;
         if (do_f) recon_packed(U, wp - L.lane, L.sm + 4 * pr, L.hdr, fr, L.lane);
         if (do_b) recon_packed(W, wp - L.lane + LROW, L.sm + 4 * pr + 2, L.hdr, fr + 576, L.lane);
+      } else if (RECON == 5) {
+        const size_t fr = ((size_t)L.tile * NDIR + 2 * pr) * 576 + L.lane;
+        if (do_f) recon_ortho(U, wp - L.lane, L.sm + 4 * pr, L.hdr, fr, L.lane);
+        if (do_b) recon_ortho(W, wp - L.lane + LROW, L.sm + 4 * pr + 2, L.hdr, fr + 576, L.lane);
       } else if (RECON == 2) {
         if (do_f) recon_row2<2>(U, false);
         if (do_b) recon_row2<2>(W, false);
@@ -205,7 +209,10 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       // packed lossless 8-link kernel (100 B/link, 898 B/site): rolled 77.2 + 80.4 us per sweep pair (134-150 VGPRs, 3 waves per SIMD),
       //   x2 76.5 + 80.1 us (217-231 VGPRs, 2 waves); 0.2126-0.2140 against 0.2117-0.2126 ms per iteration over six alternating bench.py
       //   runs, but one x2 run at 0.2212: rolled, the steadier one (profiles/packed_bench_32x4.log)
-      constexpr int UNR = (NDIR == 8) ? (RECON == 4 ? 1 : RECON == 3 ? (FUSED ? 1 : 2) : (RECON ? 1 : 4)) : 2;
+      // orthogonal lossless 8-link kernel (92 B/link, 834 B/site): rolled 74.2 + 74.2 us per sweep pair (135-159 VGPRs, 3 waves per SIMD);
+      //   x2 239-254 VGPRs, 2 waves, 0.2089-0.2178 against 0.2027-0.2096 ms per iteration over six alternating bench.py runs, slower
+      //   in every pair: rolled (profiles/ortho_bench_32x4.log)
+      constexpr int UNR = (NDIR == 8) ? (RECON >= 4 ? 1 : RECON == 3 ? (FUSED ? 1 : 2) : (RECON ? 1 : 4)) : 2;
       if (!edge) {
         // every hop of the site: the loop of the one-launch kernel
 #pragma unroll UNR
@@ -242,7 +249,7 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       }
     }
     if (DOT && !skip && !parked) {
-      // (RECON 3, 4: the slot of the logical block, which the XCD swizzle leaves where the unswizzled launch puts it -- the partials are
+      // (RECON 3, 4, 5: the slot of the logical block, which the XCD swizzle leaves where the unswizzled launch puts it -- the partials are
       // summed in slot order, and this format computes the 18-real operator's bits, the residual history included)
       const int pidx = !FUSED ? (RECON >= 3 ? lb : (int)blockIdx.x) : fused_partial_slot(A.fs, R, lb);
       double r = block_sum_256(dotv);
@@ -300,7 +307,8 @@ static int launch(qexhip_ctx *c, DslashArgs &A, int c0, int c1, bool init, bool 
   if (c->recon == 1) QX_LAUNCH(1);
   else if (c->recon == 2) QX_LAUNCH(2);
   else if constexpr (NDIR == 8) {
-    if (c->lres == 2) QX_LAUNCH(4);
+    if (c->lres == 3) QX_LAUNCH(5);
+    else if (c->lres == 2) QX_LAUNCH(4);
     else if (c->lres) QX_LAUNCH(3);
     else QX_LAUNCH(0);
   } else QX_LAUNCH(0);
@@ -352,7 +360,7 @@ static double exchange_estimate_us(const qexhip_ctx *c) {
 // about one exchange time, then parks), but the waiting ones do hold slots meanwhile.
 // nrhs > 1 (the lock-step batch): the links once, the vectors and the faces nrhs times.
 double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs) {
-  const double bsite = c->ndir * (c->recon == 1 ? 96.0 : (c->recon == 2 ? 112.0 : (c->lres == 2 ? 100.0 : (c->lres ? 108.0 : 144.0)))) + 120.0 * nrhs;
+  const double bsite = c->ndir * (c->recon == 1 ? 96.0 : (c->recon == 2 ? 112.0 : (c->lres == 3 ? 92.0 : c->lres == 2 ? 100.0 : (c->lres ? 108.0 : 144.0)))) + 120.0 * nrhs;
   const double t_int = (double)interior_sites * bsite / 5.5e6;       // us
   return t_int > 0 ? std::min(1.0, std::max(0.65, nrhs * exchange_estimate_us(c) / t_int)) : 1.0;
 }
@@ -498,7 +506,7 @@ void stag_link_bases(const qexhip_ctx *c, int parity, bool lossless, const doubl
     *W = c->Wc + rows * (c->recon == 1 ? LinkFormat<1>::LROW : LinkFormat<2>::LROW);
     *S = c->Ws + rows;
   } else if (lossless) {
-    *W = c->Wc + rows * (c->lres == 2 ? LinkFormat<4>::LROW : LinkFormat<3>::LROW);
+    *W = c->Wc + rows * (c->lres == 3 ? LinkFormat<5>::LROW : c->lres == 2 ? LinkFormat<4>::LROW : LinkFormat<3>::LROW);
     *S = c->Wm + (size_t)parity * (2 + c->g.ntile * c->ndir * 2) + 2;
   } else {
     *W = c->W + rows * LinkFormat<0>::LROW;

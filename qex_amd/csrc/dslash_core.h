@@ -86,14 +86,32 @@ __device__ __forceinline__ void recon_packed(double2 U[9], const double2 *row, c
   }
 }
 
-// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3: lossless (link_residual.h), 4: its packed form
+// orthogonal lossless format (RECON 5, link_residual.h): the whole link from the five slot pairs in U[0..4] and the row's two extra
+// words; an escaped lane reads all 18 reals from W (arguments as above)
+__device__ __forceinline__ void recon_ortho(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
+                                            size_t fr, int lane) {
+  const uint64_t exlo = __builtin_nontemporal_load((const uint64_t *)(row + LO_EXLO) + lane);
+  const uint32_t exhi = __builtin_nontemporal_load((const uint32_t *)(row + LO_EXHI) + lane);
+  uint64_t s[10];
+#pragma unroll
+  for (int k = 0; k < 5; k++) { s[2 * k] = lr_bits(U[k].x); s[2 * k + 1] = lr_bits(U[k].y); }
+  lo_decode(s, exlo, exhi, (m[0] >> lane) & 1ull, U);
+  if ((m[1] >> lane) & 1ull) {
+    const double2 *wf = (const double2 *)(uintptr_t)hdr[0] + fr;
+#pragma unroll
+    for (int k = 0; k < 9; k++) U[k] = wf[k * 64];
+  }
+}
+
+// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3: lossless (link_residual.h), 4: its packed
+// form, 5: its orthogonal form
 template <int RECON> struct LinkFormat {
-  static constexpr int NLOAD = (RECON == 1 || RECON >= 3) ? 6 : (RECON == 2 ? 7 : 9);      // double2 loaded per lane and link
-  static constexpr int LROW = RECON == 3 ? LR_ROW : (RECON == 4 ? LP_ROW : NLOAD * 64);     // double2 per (tile, direction) row
+  static constexpr int NLOAD = RECON == 5 ? 5 : ((RECON == 1 || RECON >= 3) ? 6 : (RECON == 2 ? 7 : 9));      // double2 loaded per lane and link
+  static constexpr int LROW = RECON == 3 ? LR_ROW : (RECON == 4 ? LP_ROW : (RECON == 5 ? LO_ROW : NLOAD * 64));     // double2 per (tile, direction) row
 };
 
 // The links of one output site as a sweep reads them: built once per site from the parity's link base W, its mask base S (RECON 1:
-// sign masks [tile][dir], bit = lane; 3, 4: [tile][dir][sign, escape], S[-2] = this parity's 18-real W) and the site c.
+// sign masks [tile][dir], bit = lane; 3, 4, 5: [tile][dir][sign, escape], S[-2] = this parity's 18-real W) and the site c.
 // fetch(pr, ..) gives the forward link of hop pair pr (direction 2 pr; fat links: pairs 0..3, 3-hop links: 4..7) in U and the backward
 // link (direction 2 pr + 1) in Wb, rebuilt to 3x3.  The batched sweep (batch.hip) calls it; dslash_body (dslash.hip) takes the cursor's
 // rows and masks but spells the same statements out in place, because through the call its RECON 1 / 2 kernels change registers
@@ -102,8 +120,8 @@ template <int NDIR, int RECON>
 struct LinkCursor {
   static constexpr int NLOAD = LinkFormat<RECON>::NLOAD, LROW = LinkFormat<RECON>::LROW;
   const double2 *w;                  // this lane's element of the site's first (tile, direction) row
-  const unsigned long long *sm;      // the tile's mask row (RECON 1, 3, 4)
-  const unsigned long long *hdr;     // RECON 3, 4: header of the parity's mask block
+  const unsigned long long *sm;      // the tile's mask row (RECON 1, 3, 4, 5)
+  const unsigned long long *hdr;     // RECON 3, 4, 5: header of the parity's mask block
   int tile, lane;
   __device__ __forceinline__ LinkCursor(const double2 *W, const unsigned long long *S, const int c)
       : w(W + (size_t)(c >> 6) * (NDIR * LROW) + (c & 63)),
@@ -141,6 +159,10 @@ struct LinkCursor {
       const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
       if (do_f) recon_packed(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
       if (do_b) recon_packed(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
+    } else if (RECON == 5) {
+      const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
+      if (do_f) recon_ortho(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
+      if (do_b) recon_ortho(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
     } else if (RECON == 2) {
       if (do_f) recon_row2<2>(U, false);
       if (do_b) recon_row2<2>(Wb, false);

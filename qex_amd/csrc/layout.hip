@@ -288,6 +288,36 @@ __global__ void __launch_bounds__(256) k_links_packed(size_t nrows, size_t prows
   }
 }
 
+// The orthogonal form of the same (link_residual.h, RECON 5): slots and the two extra words into Wc (row stride LO_ROW), the masks and
+// the empty lanes as above.
+__global__ void __launch_bounds__(256) k_links_ortho(size_t nrows, size_t prows, int Vh, const double2 *__restrict__ W, double2 *Wc,
+                                                     unsigned long long *Wm, unsigned int *nesc) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // (row = (parity, tile, dir), lane)
+  const size_t row = j >> 6;
+  if (row >= nrows) return;
+  const int l = j & 63;
+  const double2 *w = W + row * 576 + l;
+  double2 u[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) u[k] = w[k * 64];
+  bool neg;
+  uint64_t s[10], exlo;
+  uint32_t exhi;
+  const bool ok = lo_encode(u, &neg, s, &exlo, &exhi) || (long long)((row % prows) / 8 * 64 + l) >= Vh;
+  ulonglong2 *o = (ulonglong2 *)(Wc + row * LO_ROW) + l;
+#pragma unroll
+  for (int k = 0; k < 5; k++) o[k * 64] = make_ulonglong2(s[2 * k], s[2 * k + 1]);
+  ((uint64_t *)(Wc + row * LO_ROW + LO_EXLO))[l] = exlo;
+  ((uint32_t *)(Wc + row * LO_ROW + LO_EXHI))[l] = exhi;
+  const unsigned long long sgn = __ballot(neg), esc = __ballot(!ok);
+  if (l == 0) {
+    unsigned long long *m = Wm + 2 * (row + row / prows + 1);
+    m[0] = sgn;
+    m[1] = esc;
+    if (esc) atomicAdd(nesc, (unsigned int)__popcll(esc));
+  }
+}
+
 // The same encoder and decoder on the host (qexhip_link_residual_host): n links of 9 double2 each
 int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2 *row2) {
   for (long i = 0; i < n; i++) {
@@ -309,6 +339,19 @@ int link_packed_host(const double2 *u, long n, unsigned char *escaped, double2 *
     const bool ok = lp_encode(u + 9 * i, &neg, s, &extra);
     if (escaped) escaped[i] = !ok;
     if (dec) lp_decode(s, extra, neg, dec + 9 * i);
+  }
+  return 0;
+}
+
+// ... and of the orthogonal form (qexhip_link_ortho_host)
+int link_ortho_host(const double2 *u, long n, unsigned char *escaped, double2 *dec) {
+  for (long i = 0; i < n; i++) {
+    bool neg;
+    uint64_t s[10], exlo;
+    uint32_t exhi;
+    const bool ok = lo_encode(u + 9 * i, &neg, s, &exlo, &exhi);
+    if (escaped) escaped[i] = !ok;
+    if (dec) lo_decode(s, exlo, exhi, neg, dec + 9 * i);
   }
   return 0;
 }
@@ -344,8 +387,9 @@ int links_compress(qexhip_ctx *c) {
     if (dev <= 5e-14f) { c->recon = fmt; break; }
   }
   // neither format holds: a lossless form when at most 1 % of the links escape it (8-link operators; it stores the same operator
-  // bit for bit, so qexhip_stag_links_info keeps reporting format 0).  Option lossless = 2: the packed 100-byte form first, then
-  // the 108-byte residual form under its own rule; 1: the residual form only
+  // bit for bit, so qexhip_stag_links_info keeps reporting format 0).  Option lossless = 3: the orthogonal 92-byte form first, then
+  // the packed 100-byte form, then the 108-byte residual form, each under its own rule; 2: from the packed form on; 1: the residual
+  // form only
   if (!c->recon && c->opt_lossless && c->ndir == 8) {
     if (!c->Wm || c->Wm_rows < nrows) {
       if (c->Wm) HIPCHK(hipFree(c->Wm));
@@ -355,9 +399,10 @@ int links_compress(qexhip_ctx *c) {
     }
     const size_t prows = nrows / 2;
     const unsigned long long hdr[2][2] = {{(unsigned long long)(uintptr_t)c->W, 0}, {(unsigned long long)(uintptr_t)(c->W + prows * 576), 0}};
-    for (int form = c->opt_lossless >= 2 ? 2 : 1; form >= 1 && !c->lres; form--) {
+    for (int form = c->opt_lossless >= 3 ? 3 : (c->opt_lossless == 2 ? 2 : 1); form >= 1 && !c->lres; form--) {
       HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
-      if (form == 2) k_links_packed<<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
+      if (form == 3) k_links_ortho<<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
+      else if (form == 2) k_links_packed<<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
       else k_links_residual<<<nblk, 256, 0, c->stream>>>(nrows, prows, c->W, c->Wc, c->Wm, flag);
       HIPCHK(hipGetLastError());
       unsigned int nesc = 0;

@@ -180,10 +180,10 @@ struct qexhip_ctx {
   double2 *Wc = nullptr; unsigned long long *Ws = nullptr; size_t Wc_rows = 0; int recon = 0; double recon_dev = 0;
   // lossless formats (link_residual.h) of 8-link operators that fit neither format: lres = 1 the residual format (rows 0,1 + int16
   // residuals of row 2 in Wc, [sign, escape] masks per row in Wm), 2 its packed form (residuals in the exponent bits of rows 0,1;
-  // same masks); recon stays 0 (the values ARE the 18-real links, which W keeps: the escaped lanes,
+  // same masks), 3 its orthogonal form (row 1's last element rebuilt too, 92 B; same masks); recon stays 0 (the values ARE the 18-real links, which W keeps: the escaped lanes,
   // the fp32 builder and every kernel but k_dslash / k_dslash_fused read them there)
   unsigned long long *Wm = nullptr; size_t Wm_rows = 0; int lres = 0; long long lres_esc = 0;
-  int opt_lossless = 2;   // option "lossless": 0 keeps the lossless formats off, 1 the residual format only, 2 the packed form first
+  int opt_lossless = 3;   // option "lossless": 0 keeps the lossless formats off, 1 the residual format only, 2 the packed form first, 3 the orthogonal form first
   int opt_batch_multi = 0; // test hook: take the multi-rank reduction branch of the batched CG on one rank
   int opt_multi_reduce = 0; // test hook: take the multi-rank reduction branches of CG / multi-shift CG / norms on one rank
                             // (with a one-rank RCCL communicator the all-reduces are real collectives)
@@ -297,6 +297,7 @@ int links_from_natural(qexhip_ctx *c, const double2 *fat, const double2 *lng);
 int links_compress(qexhip_ctx *c);
 int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2 *row2);   // the residual format's encoder + decoder on the host
 int link_packed_host(const double2 *u, long n, unsigned char *escaped, double2 *dec);      // the packed form's: the whole link
+int link_ortho_host(const double2 *u, long n, unsigned char *escaped, double2 *dec);       // the orthogonal form's: the whole link
 int op_eo_reconstruct_pub(qexhip_ctx *c, DevField &r, DevField &b, double m);
 int op_eo_reduce_pub(qexhip_ctx *c, DevField &r, DevField &b, double m);
 int op_stagD_pub(qexhip_ctx *c, DevField &r, DevField &x, int parity, double m, double sc, double a);   // one subset of stagD

@@ -646,8 +646,8 @@ class Staggered:
 
     def links_storage(self):
         """(bytes per link the sweep streams, links escaped by the last lossless encoding): 144 / 96 / 112 for formats 0 / 1 / 2,
-        108 for the lossless residual format and 100 for its packed form (the 18-real operator bit for bit: links_info reports
-        format 0)"""
+        108 for the lossless residual format, 100 for its packed form and 92 for its orthogonal form (the 18-real operator bit for
+        bit: links_info reports format 0)"""
         nb, ne = C.c_int(0), C.c_longlong(0)
         check(lib().qexhip_stag_links_storage(self.ctx._h, C.byref(nb), C.byref(ne)))
         return nb.value, ne.value
@@ -994,6 +994,20 @@ def link_packed_host(links):
     esc = np.zeros(n, dtype=np.uint8)
     dec = np.zeros((n, 3, 3, 2), dtype=np.float64)
     check(lib().qexhip_link_packed_host(a.ctypes.data, n, esc.ctypes.data, dec.ctypes.data))
+    return esc.astype(bool), dec
+
+
+def link_ortho_host(links):
+    """The orthogonal lossless link format's encoder + decoder on the host (no device needed).  links as for link_residual_host.
+    Returns (escaped: bool per link, decoded: every link as decoded, shape (n, 3, 3, 2))."""
+    a = np.asarray(links)
+    if np.iscomplexobj(a):
+        a = np.stack([a.real, a.imag], axis=-1)
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 18)
+    n = a.shape[0]
+    esc = np.zeros(n, dtype=np.uint8)
+    dec = np.zeros((n, 3, 3, 2), dtype=np.float64)
+    check(lib().qexhip_link_ortho_host(a.ctypes.data, n, esc.ctypes.data, dec.ctypes.data))
     return esc.astype(bool), dec
 
 

@@ -1,0 +1,66 @@
+"""Worker of tests/test_gpu_link_ortho.py: two ranks sharing device 0 on the peer transport, t-sharded, the fused sweep forced
+(overlap 1, hop_split 2).  Each rank takes QEX g.random on its slab and computes D, stagD2ee and a fixed-length CG with option
+lossless = 3 (the orthogonal 92-byte form) and then 0; everything must agree bit for bit.
+
+  python -m torch.distributed.run --nproc-per-node 2 tests/link_ortho_rank_worker.py LX LY LZ LT_GLOBAL
+
+Prints one line `ORTHO rank r {...}` per rank.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    lat = [int(v) for v in sys.argv[1:5]]
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    import torch.distributed as dist
+
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    import qex_amd as q
+    from oracle import oracle as o
+
+    loc = list(lat)
+    loc[3] //= world
+    lo = o.Layout(loc)
+    rf = o.RngField(lo, o.RNG_MILC6, 987654321 + rank)
+    g = o.gauge_random(lo, rf)
+    o.rephase(lo, g)
+    b = o.vector_gaussian(lo, rf)
+    ctx = q.Context(loc, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
+    ctx.set_option("transport", 2)
+    uid = [q.Context.unique_id() if rank == 0 else None]
+    dist.broadcast_object_list(uid, src=0)
+    ctx.comm_init(uid[0], world, rank)
+    ctx.set_option("overlap", 1)
+    ctx.set_option("hop_split", 2)
+    res, out = {}, {"rank": rank}
+    for lossless in (3, 0):
+        ctx.set_option("lossless", lossless)
+        s = q.newStag(ctx, g)
+        r = {"storage": s.links_storage(), "form": 2 if ctx.sweep_tuning()["form"] == "fused" else 0}
+        d = np.zeros_like(b)
+        s.D(d, b, 0.1)
+        r["D"] = d.copy()
+        s.stagD2ee(d, b, 0.01)
+        r["stagD2ee"] = d.copy()
+        sp = q.SolverParams(r2req=0.0, maxits=60, verbosity=0)
+        x = np.zeros_like(b)
+        s.solveEE(x, b, 0.1, sp, histcap=80)
+        r["hist"], r["x"], r["its"] = np.array(sp.r2hist), x.copy(), int(sp.iterations)
+        res[lossless] = r
+    out["storage"], out["storage_ref"], out["form"] = res[3]["storage"], res[0]["storage"], res[3]["form"]
+    out["equal"] = {k: bool(np.array_equal(res[3][k], res[0][k])) for k in ("D", "stagD2ee", "hist", "x", "its")}
+    sys.stdout.write("\nORTHO rank %d %s\n" % (rank, json.dumps(out)))
+    sys.stdout.flush()
+    os._exit(0)
+
+
+if __name__ == "__main__":
+    main()
