@@ -1317,21 +1317,21 @@ extern "C" int qexhip_stag_links_info(qexhip_handle c, int *nlinks, int *compres
 }
 extern "C" int qexhip_stag_links_storage(qexhip_handle c, int *bytes_per_link, long long *escaped) {
   if (!c) return QEXHIP_ERR_ARG;
-  if (bytes_per_link) *bytes_per_link = !c->W ? 0 : (c->lres == 3 ? 92 : c->lres == 2 ? 100 : c->lres ? 108 : (c->recon == 1 ? 96 : (c->recon == 2 ? 112 : 144)));
+  if (bytes_per_link) *bytes_per_link = c->W ? stag_link_storage(c).bytes : 0;
   if (escaped) *escaped = c->lres_esc;
   return 0;
 }
 extern "C" int qexhip_link_residual_host(const double *links, int n, unsigned char *escaped, double *row2) {
   if (!links || n < 0) return QEXHIP_ERR_ARG;
-  return link_residual_host((const double2 *)links, n, escaped, (double2 *)row2);
+  return link_lossless_host(1, (const double2 *)links, n, escaped, (double2 *)row2);
 }
 extern "C" int qexhip_link_packed_host(const double *links, int n, unsigned char *escaped, double *decoded) {
   if (!links || n < 0) return QEXHIP_ERR_ARG;
-  return link_packed_host((const double2 *)links, n, escaped, (double2 *)decoded);
+  return link_lossless_host(2, (const double2 *)links, n, escaped, (double2 *)decoded);
 }
 extern "C" int qexhip_link_ortho_host(const double *links, int n, unsigned char *escaped, double *decoded) {
   if (!links || n < 0) return QEXHIP_ERR_ARG;
-  return link_ortho_host((const double2 *)links, n, escaped, (double2 *)decoded);
+  return link_lossless_host(3, (const double2 *)links, n, escaped, (double2 *)decoded);
 }
 extern "C" int qexhip_hisq_prepare(qexhip_handle c, const double *g, double *fl, double *ll) {
   if (!c || !g) return QEXHIP_ERR_ARG;

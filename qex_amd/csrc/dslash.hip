@@ -101,9 +101,9 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
       const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
       const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
       double2 U[9], W[9], vf[3], vb[3];
-      // L.fetch(pr, do_f, do_b, U, W), spelled out: through the call the compiler orders the loop differently (every load first, the
-      // rebuild behind the neighbour loads) and the RECON 1 / 2 instantiations of k_dslash move by -14 .. +6 VGPRs
-      // (profiles/sweep_refactor_resources.txt).  The rows, masks and constants are the cursor's; keep the two texts the same.
+      // The loads of L.fetch(pr, do_f, do_b, U, W), spelled out: through the call the compiler orders the loop differently (every load
+      // first, the rebuild behind the neighbour loads) and the RECON 1 / 2 instantiations of k_dslash move by -14 .. +6 VGPRs
+      // (profiles/sweep_refactor_resources.txt).  The rebuild behind them is the cursor's.
       constexpr int NLOAD = LinkFormat<RECON>::NLOAD, LROW = LinkFormat<RECON>::LROW;
       const double2 *wp = L.w + (size_t)pr * (2 * LROW);
       if (do_f) {
@@ -120,25 +120,7 @@ __device__ __forceinline__ void dslash_body(const DslashArgs &A) {
           W[k] = make_double2(t.x, t.y);
         }
       }
-      if (RECON == 1) {
-        if (do_f) recon_row2<1>(U, (L.sm[2 * pr] >> L.lane) & 1ull);
-        if (do_b) recon_row2<1>(W, (L.sm[2 * pr + 1] >> L.lane) & 1ull);
-      } else if (RECON == 3) {
-        const size_t fr = ((size_t)L.tile * NDIR + 2 * pr) * 576 + L.lane;
-        if (do_f) recon_row2_res(U, wp - L.lane, L.sm + 4 * pr, L.hdr, fr, L.lane);
-        if (do_b) recon_row2_res(W, wp - L.lane + LROW, L.sm + 4 * pr + 2, L.hdr, fr + 576, L.lane);
-      } else if (RECON == 4) {
-        const size_t fr = ((size_t)L.tile * NDIR + 2 * pr) * 576 + L.lane;
-        if (do_f) recon_packed(U, wp - L.lane, L.sm + 4 * pr, L.hdr, fr, L.lane);
-        if (do_b) recon_packed(W, wp - L.lane + LROW, L.sm + 4 * pr + 2, L.hdr, fr + 576, L.lane);
-      } else if (RECON == 5) {
-        const size_t fr = ((size_t)L.tile * NDIR + 2 * pr) * 576 + L.lane;
-        if (do_f) recon_ortho(U, wp - L.lane, L.sm + 4 * pr, L.hdr, fr, L.lane);
-        if (do_b) recon_ortho(W, wp - L.lane + LROW, L.sm + 4 * pr + 2, L.hdr, fr + 576, L.lane);
-      } else if (RECON == 2) {
-        if (do_f) recon_row2<2>(U, false);
-        if (do_b) recon_row2<2>(W, false);
-      }
+      L.rebuild(pr, do_f, do_b, wp, U, W);
       const double2 *srcf = (FUSED && mu == 3) ? (hop == 3 ? in_f3 : in_f1) : A.in;
       const double2 *srcb = (FUSED && mu == 3) ? (hop == 3 ? in_b3 : in_b1) : A.in;
       if (do_f) {
@@ -304,12 +286,13 @@ static int launch(qexhip_ctx *c, DslashArgs &A, int c0, int c1, bool init, bool 
     else if (dot) launch_timed(c, tname, k_dslash<NDIR, HALO, false, true, R>, grid, block, A, st); \
     else launch_timed(c, tname, k_dslash<NDIR, HALO, false, false, R>, grid, block, A, st); \
   } while (0)
-  if (c->recon == 1) QX_LAUNCH(1);
-  else if (c->recon == 2) QX_LAUNCH(2);
-  else if constexpr (NDIR == 8) {
-    if (c->lres == 3) QX_LAUNCH(5);
-    else if (c->lres == 2) QX_LAUNCH(4);
-    else if (c->lres) QX_LAUNCH(3);
+  const int recon = stag_link_storage(c).recon;
+  if (recon == 1) QX_LAUNCH(1);
+  else if (recon == 2) QX_LAUNCH(2);
+  else if constexpr (NDIR == 8) {              // (the lossless forms are 8-link operators' only)
+    if (recon == 5) QX_LAUNCH(5);
+    else if (recon == 4) QX_LAUNCH(4);
+    else if (recon == 3) QX_LAUNCH(3);
     else QX_LAUNCH(0);
   } else QX_LAUNCH(0);
 #undef QX_LAUNCH
@@ -360,7 +343,7 @@ static double exchange_estimate_us(const qexhip_ctx *c) {
 // about one exchange time, then parks), but the waiting ones do hold slots meanwhile.
 // nrhs > 1 (the lock-step batch): the links once, the vectors and the faces nrhs times.
 double sweep_push_fraction(const qexhip_ctx *c, int interior_sites, int nrhs) {
-  const double bsite = c->ndir * (c->recon == 1 ? 96.0 : (c->recon == 2 ? 112.0 : (c->lres == 3 ? 92.0 : c->lres == 2 ? 100.0 : (c->lres ? 108.0 : 144.0)))) + 120.0 * nrhs;
+  const double bsite = c->ndir * (double)stag_link_storage(c).bytes + 120.0 * nrhs;
   const double t_int = (double)interior_sites * bsite / 5.5e6;       // us
   return t_int > 0 ? std::min(1.0, std::max(0.65, nrhs * exchange_estimate_us(c) / t_int)) : 1.0;
 }
@@ -502,16 +485,17 @@ int sweep_autotune(qexhip_ctx *c) {
 // sweep, whose kernel reads them; false for the batch, which reads the 18 reals beside them; else the 18 reals), S = its masks
 void stag_link_bases(const qexhip_ctx *c, int parity, bool lossless, const double2 **W, const unsigned long long **S) {
   const size_t rows = (size_t)parity * c->g.ntile * c->ndir;         // (tile, direction) rows before this parity
-  if (c->recon) {
-    *W = c->Wc + rows * (c->recon == 1 ? LinkFormat<1>::LROW : LinkFormat<2>::LROW);
-    *S = c->Ws + rows;
-  } else if (lossless) {
-    *W = c->Wc + rows * (c->lres == 3 ? LinkFormat<5>::LROW : c->lres == 2 ? LinkFormat<4>::LROW : LinkFormat<3>::LROW);
-    *S = c->Wm + (size_t)parity * (2 + c->g.ntile * c->ndir * 2) + 2;
-  } else {
-    *W = c->W + rows * LinkFormat<0>::LROW;
-    *S = nullptr;
-  }
+  const LinkStorage ls = stag_link_storage(c, lossless);
+  *W = (ls.recon ? c->Wc : c->W) + rows * ls.lrow;
+  if (ls.recon >= 3) *S = c->Wm + (size_t)parity * (2 + c->g.ntile * c->ndir * 2) + 2;
+  else *S = ls.recon ? c->Ws + rows : nullptr;
+}
+
+// The one answer to "which kernel, which stride, how many bytes": c->recon (formats 1, 2) or the lossless form c->lres
+LinkStorage stag_link_storage(const qexhip_ctx *c, bool lossless) {
+  static constexpr int lrow[6] = {LinkFormat<0>::LROW, LinkFormat<1>::LROW, LinkFormat<2>::LROW, LinkFormat<3>::LROW, LinkFormat<4>::LROW, LinkFormat<5>::LROW};
+  const int recon = c->recon ? c->recon : (lossless && c->lres ? lossless_recon(c->lres) : 0);
+  return {recon, lrow[recon], lrow[recon] * (int)sizeof(double2) / 64};
 }
 
 int dslash_sweep(qexhip_ctx *c, DevField &out, DevField &in, int parity, const DslashOpts &o) {

@@ -1,5 +1,6 @@
 // dslash_core.h -- device pieces shared by the fp64 Dslash kernels (dslash.hip, batch.hip) and meson.hip: the matrix-vector
-// product, the row-2 rebuilds of the compressed link formats, and LinkCursor -- the ONE place a sweep fetches a hop pair's links
+// product, the rebuilds of the compressed link formats (recon_row2; recon_lossless over link_residual.h's traits), and LinkCursor -- the ONE
+// place a sweep fetches and rebuilds a hop pair's links
 #pragma once
 #include <hip/hip_runtime.h>
 #include "link_residual.h"
@@ -52,70 +53,50 @@ __device__ __forceinline__ void recon_row2(double2 U[9], bool neg) {
   for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
 }
 
-// lossless format (RECON 3, link_residual.h): row 2 of a link whose rows 0,1 are in U[0..5].  `row` = the link's (tile, dir) row,
-// `m` its [sign, escape] masks; an escaped lane reads row 2 from the 18 reals: element `fr` of W's parity half, whose address the
-// header `hdr` of the parity's mask block holds (the kernels' argument block stays as it is)
-__device__ __forceinline__ void recon_row2_res(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
+// lossless forms (RECON 3, 4, 5 = LosslessForm<RECON - 2>, link_residual.h): the link whose loaded words are in U[0..NLOAD).  `row` =
+// the link's (tile, dir) row, `m` its [sign, escape] masks; an escaped lane re-reads what the form says (row 2, or the whole link)
+// from the 18 reals: element `fr` of W's parity half, whose address the header `hdr` of the parity's mask block holds (the
+// kernels' argument block stays as it is).  Each mask is read where it is used: hoisted into locals they move registers.
+template <int RECON>
+__device__ __forceinline__ void recon_lossless(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
                                                size_t fr, int lane) {
-  const uint64_t lo = __builtin_nontemporal_load((const uint64_t *)(row + LR_RES) + lane);
-  const uint32_t hi = __builtin_nontemporal_load((const uint32_t *)(row + LR_RES + 32) + lane);
-  double2 r2[3];
-  lr_decode(U, (m[0] >> lane) & 1ull, lo, hi, r2);
+  typedef LosslessForm<RECON - 2> F;
+  LinkExtra x = {0, 0};
+  if constexpr (F::LO_OFF >= 0) x.lo = __builtin_nontemporal_load((const uint64_t *)(row + F::LO_OFF) + lane);
+  x.hi = __builtin_nontemporal_load((const uint32_t *)(row + F::HI_OFF) + lane);
+  // (the whole link: decoded in place; row 2 only: through a temporary that takes the escape too -- written straight into U it moves
+  // the RECON 3 kernels' registers)
+  constexpr int NOUT = 9 - F::ESC_FIRST;
+  double2 tmp[NOUT];
+  double2 *o = F::ESC_FIRST ? tmp : U;
+  F::decode(U, x, (m[0] >> lane) & 1ull, o);
   if ((m[1] >> lane) & 1ull) {
     const double2 *wf = (const double2 *)(uintptr_t)hdr[0] + fr;
 #pragma unroll
-    for (int k = 0; k < 3; k++) r2[k] = wf[(6 + k) * 64];
+    for (int k = 0; k < NOUT; k++) o[k] = wf[(F::ESC_FIRST + k) * 64];
   }
+  if constexpr (F::ESC_FIRST > 0) {
 #pragma unroll
-  for (int k = 0; k < 3; k++) U[6 + k] = r2[k];
-}
-
-// packed lossless format (RECON 4, link_residual.h): the whole link from the slots in U[0..5] and the row's extra word; an escaped
-// lane reads all 18 reals from W (arguments as above)
-__device__ __forceinline__ void recon_packed(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
-                                             size_t fr, int lane) {
-  const uint32_t extra = __builtin_nontemporal_load((const uint32_t *)(row + LP_EXTRA) + lane);
-  uint64_t s[12];
-#pragma unroll
-  for (int k = 0; k < 6; k++) { s[2 * k] = lr_bits(U[k].x); s[2 * k + 1] = lr_bits(U[k].y); }
-  lp_decode(s, extra, (m[0] >> lane) & 1ull, U);
-  if ((m[1] >> lane) & 1ull) {
-    const double2 *wf = (const double2 *)(uintptr_t)hdr[0] + fr;
-#pragma unroll
-    for (int k = 0; k < 9; k++) U[k] = wf[k * 64];
+    for (int k = 0; k < NOUT; k++) U[F::ESC_FIRST + k] = tmp[k];
   }
 }
 
-// orthogonal lossless format (RECON 5, link_residual.h): the whole link from the five slot pairs in U[0..4] and the row's two extra
-// words; an escaped lane reads all 18 reals from W (arguments as above)
-__device__ __forceinline__ void recon_ortho(double2 U[9], const double2 *row, const unsigned long long *m, const unsigned long long *hdr,
-                                            size_t fr, int lane) {
-  const uint64_t exlo = __builtin_nontemporal_load((const uint64_t *)(row + LO_EXLO) + lane);
-  const uint32_t exhi = __builtin_nontemporal_load((const uint32_t *)(row + LO_EXHI) + lane);
-  uint64_t s[10];
-#pragma unroll
-  for (int k = 0; k < 5; k++) { s[2 * k] = lr_bits(U[k].x); s[2 * k + 1] = lr_bits(U[k].y); }
-  lo_decode(s, exlo, exhi, (m[0] >> lane) & 1ull, U);
-  if ((m[1] >> lane) & 1ull) {
-    const double2 *wf = (const double2 *)(uintptr_t)hdr[0] + fr;
-#pragma unroll
-    for (int k = 0; k < 9; k++) U[k] = wf[k * 64];
-  }
-}
-
-// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3: lossless (link_residual.h), 4: its packed
-// form, 5: its orthogonal form
-template <int RECON> struct LinkFormat {
-  static constexpr int NLOAD = RECON == 5 ? 5 : ((RECON == 1 || RECON >= 3) ? 6 : (RECON == 2 ? 7 : 9));      // double2 loaded per lane and link
-  static constexpr int LROW = RECON == 3 ? LR_ROW : (RECON == 4 ? LP_ROW : (RECON == 5 ? LO_ROW : NLOAD * 64));     // double2 per (tile, direction) row
+// what a link format stores per link.  RECON 0: 18 reals; 1: rows 0,1 + a sign bit; 2: rows 0,1 + det; 3, 4, 5: the lossless forms
+// (link_residual.h).  NLOAD: double2 loaded per lane and link; LROW: double2 per (tile, direction) row (= 4 x the bytes per link)
+template <int RECON, bool LOSSLESS = (RECON >= 3)> struct LinkFormat {
+  static constexpr int NLOAD = RECON == 1 ? 6 : (RECON == 2 ? 7 : 9);
+  static constexpr int LROW = NLOAD * 64;
+};
+template <int RECON> struct LinkFormat<RECON, true> {
+  static constexpr int NLOAD = LosslessForm<RECON - 2>::NLOAD, LROW = LosslessForm<RECON - 2>::ROW;
 };
 
 // The links of one output site as a sweep reads them: built once per site from the parity's link base W, its mask base S (RECON 1:
 // sign masks [tile][dir], bit = lane; 3, 4, 5: [tile][dir][sign, escape], S[-2] = this parity's 18-real W) and the site c.
 // fetch(pr, ..) gives the forward link of hop pair pr (direction 2 pr; fat links: pairs 0..3, 3-hop links: 4..7) in U and the backward
-// link (direction 2 pr + 1) in Wb, rebuilt to 3x3.  The batched sweep (batch.hip) calls it; dslash_body (dslash.hip) takes the cursor's
-// rows and masks but spells the same statements out in place, because through the call its RECON 1 / 2 kernels change registers
-// (see there).  The two must reconstruct the same bits (tests/test_gpu_batch.py): change them together.
+// link (direction 2 pr + 1) in Wb, rebuilt to 3x3: the loads, then rebuild().  The batched sweep (batch.hip) calls it; dslash_body
+// (dslash.hip) spells the LOADS out in place, because through the call its RECON 1 / 2 kernels change registers (see there), and calls
+// rebuild() itself.
 template <int NDIR, int RECON>
 struct LinkCursor {
   static constexpr int NLOAD = LinkFormat<RECON>::NLOAD, LROW = LinkFormat<RECON>::LROW;
@@ -147,23 +128,19 @@ struct LinkCursor {
         Wb[k] = make_double2(t.x, t.y);
       }
     }
-    if (RECON == 1) {
+    rebuild(pr, do_f, do_b, wp, U, Wb);
+  }
+  // everything after the loads: U / Wb hold the words of the pair's rows at wp / wp + LROW on entry, the 3x3 links on return
+  __device__ __forceinline__ void rebuild(const int pr, const bool do_f, const bool do_b, const double2 *wp, double2 U[9], double2 Wb[9]) const {
+    if constexpr (RECON == 1) {
       if (do_f) recon_row2<1>(U, (sm[2 * pr] >> lane) & 1ull);
       if (do_b) recon_row2<1>(Wb, (sm[2 * pr + 1] >> lane) & 1ull);
-    } else if (RECON == 3) {
-      // row 2 = rebuild + int16 residuals (link_residual.h), bit for bit the 18-real link; an escaped lane reads it from W
+    } else if constexpr (RECON >= 3) {
+      // bit for bit the 18-real link; an escaped lane reads it from W
       const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
-      if (do_f) recon_row2_res(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
-      if (do_b) recon_row2_res(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
-    } else if (RECON == 4) {
-      const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
-      if (do_f) recon_packed(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
-      if (do_b) recon_packed(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
-    } else if (RECON == 5) {
-      const size_t fr = ((size_t)tile * NDIR + 2 * pr) * 576 + lane;
-      if (do_f) recon_ortho(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
-      if (do_b) recon_ortho(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
-    } else if (RECON == 2) {
+      if (do_f) recon_lossless<RECON>(U, wp - lane, sm + 4 * pr, hdr, fr, lane);
+      if (do_b) recon_lossless<RECON>(Wb, wp - lane + LROW, sm + 4 * pr + 2, hdr, fr + 576, lane);
+    } else if constexpr (RECON == 2) {
       if (do_f) recon_row2<2>(U, false);
       if (do_b) recon_row2<2>(Wb, false);
     }

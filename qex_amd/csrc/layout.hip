@@ -5,7 +5,7 @@
 #include <vector>
 #include "qexhip_internal.h"
 #include "site_index.h"
-#include "link_residual.h"
+#include "dslash_core.h"
 #include <cstring>
 
 int geom_init(Geom &g, const int X[4], int depth, int halo) {
@@ -227,42 +227,15 @@ __global__ void __launch_bounds__(256) k_links_compress(size_t nrows, const doub
   }
   if (l == 0 && bits > __hip_atomic_load(maxdev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxdev, bits);
 }
-// The lossless residual format (link_residual.h) of an 8-link operator whose links fit neither format 1 nor 2 (QEX's g.random is
-// unitary only to ~1e-11, but to a few ulp for almost every link): rows 0,1 into Wc (row stride LR_ROW), the int16 residuals of
-// row 2 behind them, sign and escape masks into Wm[parity][2 + prows][2] (each parity's block behind a header: the host writes it);
-// `nesc` counts the escaped links (one atomic per wavefront).
-__global__ void __launch_bounds__(256) k_links_residual(size_t nrows, size_t prows, const double2 *__restrict__ W, double2 *Wc,
+// A lossless form (LosslessForm<FORM>, link_residual.h) of an 8-link operator whose links fit neither format 1 nor 2 (QEX's g.random
+// is unitary only to ~1e-11, but to a few ulp for almost every link): the form's words and extra words into Wc (row stride
+// F::ROW), sign and escape masks into Wm[parity][2 + prows][2] (each parity's block behind a header: the host writes it); `nesc`
+// counts the escaped links (one atomic per wavefront).  Lanes beyond the parity's last site (Vh) hold no link and are never read:
+// the forms that encode rows 0,1 (2, 3) would escape their zeros, so there they count as kept.
+template <int FORM>
+__global__ void __launch_bounds__(256) k_links_lossless(size_t nrows, size_t prows, int Vh, const double2 *__restrict__ W, double2 *Wc,
                                                         unsigned long long *Wm, unsigned int *nesc) {
-  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // (row = (parity, tile, dir), lane)
-  const size_t row = j >> 6;
-  if (row >= nrows) return;
-  const int l = j & 63;
-  const double2 *w = W + row * 576 + l;
-  double2 *o = Wc + row * LR_ROW + l;
-  double2 u[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) u[k] = w[k * 64];
-#pragma unroll
-  for (int k = 0; k < 6; k++) o[k * 64] = u[k];
-  bool neg;
-  uint64_t lo;
-  uint32_t hi;
-  const bool ok = lr_encode(u, &neg, &lo, &hi);
-  ((uint64_t *)(Wc + row * LR_ROW + LR_RES))[l] = lo;
-  ((uint32_t *)(Wc + row * LR_ROW + LR_RES + 32))[l] = hi;
-  const unsigned long long sgn = __ballot(neg), esc = __ballot(!ok);
-  if (l == 0) {
-    unsigned long long *m = Wm + 2 * (row + row / prows + 1);
-    m[0] = sgn;
-    m[1] = esc;
-    if (esc) atomicAdd(nesc, (unsigned int)__popcll(esc));
-  }
-}
-
-// The packed form of the same (link_residual.h, RECON 4): slots and extra into Wc (row stride LP_ROW), the masks as above.  Lanes
-// beyond the parity's last site (Vh) hold no link: never read, never escaped.
-__global__ void __launch_bounds__(256) k_links_packed(size_t nrows, size_t prows, int Vh, const double2 *__restrict__ W, double2 *Wc,
-                                                      unsigned long long *Wm, unsigned int *nesc) {
+  typedef LosslessForm<FORM> F;
   const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // (row = (parity, tile, dir), lane)
   const size_t row = j >> 6;
   if (row >= nrows) return;
@@ -272,13 +245,14 @@ __global__ void __launch_bounds__(256) k_links_packed(size_t nrows, size_t prows
 #pragma unroll
   for (int k = 0; k < 9; k++) u[k] = w[k * 64];
   bool neg;
-  uint64_t s[12];
-  uint32_t extra;
-  const bool ok = lp_encode(u, &neg, s, &extra) || (long long)((row % prows) / 8 * 64 + l) >= Vh;
-  ulonglong2 *o = (ulonglong2 *)(Wc + row * LP_ROW) + l;
+  double2 s[F::NLOAD];
+  LinkExtra x;
+  const bool ok = F::encode(u, &neg, s, &x) || (FORM >= 2 && (long long)((row % prows) / 8 * 64 + l) >= Vh);
+  double2 *o = Wc + row * F::ROW + l;
 #pragma unroll
-  for (int k = 0; k < 6; k++) o[k * 64] = make_ulonglong2(s[2 * k], s[2 * k + 1]);
-  ((uint32_t *)(Wc + row * LP_ROW + LP_EXTRA))[l] = extra;
+  for (int k = 0; k < F::NLOAD; k++) o[k * 64] = s[k];
+  if constexpr (F::LO_OFF >= 0) ((uint64_t *)(Wc + row * F::ROW + F::LO_OFF))[l] = x.lo;
+  ((uint32_t *)(Wc + row * F::ROW + F::HI_OFF))[l] = x.hi;
   const unsigned long long sgn = __ballot(neg), esc = __ballot(!ok);
   if (l == 0) {
     unsigned long long *m = Wm + 2 * (row + row / prows + 1);
@@ -288,73 +262,29 @@ __global__ void __launch_bounds__(256) k_links_packed(size_t nrows, size_t prows
   }
 }
 
-// The orthogonal form of the same (link_residual.h, RECON 5): slots and the two extra words into Wc (row stride LO_ROW), the masks and
-// the empty lanes as above.
-__global__ void __launch_bounds__(256) k_links_ortho(size_t nrows, size_t prows, int Vh, const double2 *__restrict__ W, double2 *Wc,
-                                                     unsigned long long *Wm, unsigned int *nesc) {
-  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // (row = (parity, tile, dir), lane)
-  const size_t row = j >> 6;
-  if (row >= nrows) return;
-  const int l = j & 63;
-  const double2 *w = W + row * 576 + l;
-  double2 u[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) u[k] = w[k * 64];
-  bool neg;
-  uint64_t s[10], exlo;
-  uint32_t exhi;
-  const bool ok = lo_encode(u, &neg, s, &exlo, &exhi) || (long long)((row % prows) / 8 * 64 + l) >= Vh;
-  ulonglong2 *o = (ulonglong2 *)(Wc + row * LO_ROW) + l;
-#pragma unroll
-  for (int k = 0; k < 5; k++) o[k * 64] = make_ulonglong2(s[2 * k], s[2 * k + 1]);
-  ((uint64_t *)(Wc + row * LO_ROW + LO_EXLO))[l] = exlo;
-  ((uint32_t *)(Wc + row * LO_ROW + LO_EXHI))[l] = exhi;
-  const unsigned long long sgn = __ballot(neg), esc = __ballot(!ok);
-  if (l == 0) {
-    unsigned long long *m = Wm + 2 * (row + row / prows + 1);
-    m[0] = sgn;
-    m[1] = esc;
-    if (esc) atomicAdd(nesc, (unsigned int)__popcll(esc));
-  }
-}
-
-// The same encoder and decoder on the host (qexhip_link_residual_host): n links of 9 double2 each
-int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2 *row2) {
+// The same encoder and decoder on the host (qexhip_link_{residual,packed,ortho}_host): n links of 9 double2 each; `out` takes what
+// an escaped lane would re-read -- row 2 (3 double2 per link) of the residual form, the whole link of the other two -- as decoded
+template <int FORM>
+static void link_lossless_host_form(const double2 *u, long n, unsigned char *escaped, double2 *out) {
+  typedef LosslessForm<FORM> F;
   for (long i = 0; i < n; i++) {
     bool neg;
-    uint64_t lo;
-    uint32_t hi;
-    const bool ok = lr_encode(u + 9 * i, &neg, &lo, &hi);
+    double2 w[F::NLOAD];
+    LinkExtra x;
+    const bool ok = F::encode(u + 9 * i, &neg, w, &x);
     if (escaped) escaped[i] = !ok;
-    if (row2) lr_decode(u + 9 * i, neg, lo, hi, row2 + 3 * i);
+    if (out) F::decode(w, x, neg, out + (9 - F::ESC_FIRST) * i);
   }
-  return 0;
 }
-// ... and of the packed form (qexhip_link_packed_host): the whole link as decoded
-int link_packed_host(const double2 *u, long n, unsigned char *escaped, double2 *dec) {
-  for (long i = 0; i < n; i++) {
-    bool neg;
-    uint64_t s[12];
-    uint32_t extra;
-    const bool ok = lp_encode(u + 9 * i, &neg, s, &extra);
-    if (escaped) escaped[i] = !ok;
-    if (dec) lp_decode(s, extra, neg, dec + 9 * i);
-  }
+int link_lossless_host(int form, const double2 *u, long n, unsigned char *escaped, double2 *out) {
+  if (form == 3) link_lossless_host_form<3>(u, n, escaped, out);
+  else if (form == 2) link_lossless_host_form<2>(u, n, escaped, out);
+  else link_lossless_host_form<1>(u, n, escaped, out);
   return 0;
 }
 
-// ... and of the orthogonal form (qexhip_link_ortho_host)
-int link_ortho_host(const double2 *u, long n, unsigned char *escaped, double2 *dec) {
-  for (long i = 0; i < n; i++) {
-    bool neg;
-    uint64_t s[10], exlo;
-    uint32_t exhi;
-    const bool ok = lo_encode(u + 9 * i, &neg, s, &exlo, &exhi);
-    if (escaped) escaped[i] = !ok;
-    if (dec) lo_decode(s, exlo, exhi, neg, dec + 9 * i);
-  }
-  return 0;
-}
+// double2 per (tile, direction) row of Wc: the widest compressed row of any format
+static constexpr int WC_ROW = std::max({LinkFormat<1>::LROW, LinkFormat<2>::LROW, LinkFormat<3>::LROW, LinkFormat<4>::LROW, LinkFormat<5>::LROW});
 
 int links_compress(qexhip_ctx *c) {
   const Geom &g = c->g;
@@ -366,7 +296,7 @@ int links_compress(qexhip_ctx *c) {
   if (c->Wc_rows < nrows) {
     if (c->Wc) HIPCHK(hipFree(c->Wc));
     if (c->Ws) HIPCHK(hipFree(c->Ws));
-    HIPCHK(hipMalloc((void **)&c->Wc, nrows * 448 * sizeof(double2)));
+    HIPCHK(hipMalloc((void **)&c->Wc, nrows * WC_ROW * sizeof(double2)));
     HIPCHK(hipMalloc((void **)&c->Ws, nrows * sizeof(unsigned long long)));
     c->Wc_rows = nrows;
   }
@@ -401,9 +331,9 @@ int links_compress(qexhip_ctx *c) {
     const unsigned long long hdr[2][2] = {{(unsigned long long)(uintptr_t)c->W, 0}, {(unsigned long long)(uintptr_t)(c->W + prows * 576), 0}};
     for (int form = c->opt_lossless >= 3 ? 3 : (c->opt_lossless == 2 ? 2 : 1); form >= 1 && !c->lres; form--) {
       HIPCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int), c->stream));
-      if (form == 3) k_links_ortho<<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
-      else if (form == 2) k_links_packed<<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
-      else k_links_residual<<<nblk, 256, 0, c->stream>>>(nrows, prows, c->W, c->Wc, c->Wm, flag);
+      if (form == 3) k_links_lossless<3><<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
+      else if (form == 2) k_links_lossless<2><<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
+      else k_links_lossless<1><<<nblk, 256, 0, c->stream>>>(nrows, prows, g.Vh, c->W, c->Wc, c->Wm, flag);
       HIPCHK(hipGetLastError());
       unsigned int nesc = 0;
       HIPCHK(hipMemcpyAsync(&nesc, flag, sizeof(nesc), hipMemcpyDeviceToHost, c->stream));

@@ -295,9 +295,8 @@ int links_upload(qexhip_ctx *c, const double *fat, const double *lng);
 int ensure_stage(qexhip_ctx *c, size_t bytes);
 int links_from_natural(qexhip_ctx *c, const double2 *fat, const double2 *lng);
 int links_compress(qexhip_ctx *c);
-int link_residual_host(const double2 *u, long n, unsigned char *escaped, double2 *row2);   // the residual format's encoder + decoder on the host
-int link_packed_host(const double2 *u, long n, unsigned char *escaped, double2 *dec);      // the packed form's: the whole link
-int link_ortho_host(const double2 *u, long n, unsigned char *escaped, double2 *dec);       // the orthogonal form's: the whole link
+// lossless form `form`'s (1, 2, 3: link_residual.h) encoder + decoder on the host; out: row 2 (form 1) or the whole link, as decoded
+int link_lossless_host(int form, const double2 *u, long n, unsigned char *escaped, double2 *out);
 int op_eo_reconstruct_pub(qexhip_ctx *c, DevField &r, DevField &b, double m);
 int op_eo_reduce_pub(qexhip_ctx *c, DevField &r, DevField &b, double m);
 int op_stagD_pub(qexhip_ctx *c, DevField &r, DevField &x, int parity, double m, double sc, double a);   // one subset of stagD
@@ -409,6 +408,10 @@ struct DslashOpts {
                                    // sites leaves its join from the comm stream to that kernel's prologue where the mailboxes carry the sum
 };
 int dslash_sweep(qexhip_ctx *c, DevField &out, DevField &in, int parity, const DslashOpts &o);
+// The storage a sweep reads its links from -- what set_links chose; `lossless` false: the 18 reals kept beside a lossless form --:
+// the sweep kernels' RECON (dslash_core.h), double2 per (tile, direction) row, bytes per link
+struct LinkStorage { int recon, lrow, bytes; };
+LinkStorage stag_link_storage(const qexhip_ctx *c, bool lossless = true);
 void stag_link_bases(const qexhip_ctx *c, int parity, bool lossless, const double2 **W, const unsigned long long **S);   // a parity's link and mask base
 int sweep_autotune(qexhip_ctx *c);      // measure the sweep's forms once per operator shape (collective)
 void sweep_plan(const qexhip_ctx *c, int *lo_end, int *hi_beg, int *overlap);   // boundary / interior ranges and the overlap decision

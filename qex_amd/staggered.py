@@ -969,46 +969,34 @@ def newStag3(ctx, g, g3):
     return Staggered(ctx, g, g3)
 
 
-def link_residual_host(links):
-    """The lossless link format's encoder + decoder on the host (no device needed).  links: complex or (..., 3, 3, 2) real array
-    of 3x3 matrices.  Returns (escaped: bool per link, row2: the decoded row 2 of every link, shape (n, 3, 2))."""
+def _link_lossless_host(entry, links, out_shape):
     a = np.asarray(links)
     if np.iscomplexobj(a):
         a = np.stack([a.real, a.imag], axis=-1)
     a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 18)
     n = a.shape[0]
     esc = np.zeros(n, dtype=np.uint8)
-    row2 = np.zeros((n, 3, 2), dtype=np.float64)
-    check(lib().qexhip_link_residual_host(a.ctypes.data, n, esc.ctypes.data, row2.ctypes.data))
-    return esc.astype(bool), row2
+    out = np.zeros((n,) + out_shape, dtype=np.float64)
+    check(getattr(lib(), entry)(a.ctypes.data, n, esc.ctypes.data, out.ctypes.data))
+    return esc.astype(bool), out
+
+
+def link_residual_host(links):
+    """The lossless link format's encoder + decoder on the host (no device needed).  links: complex or (..., 3, 3, 2) real array
+    of 3x3 matrices.  Returns (escaped: bool per link, row2: the decoded row 2 of every link, shape (n, 3, 2))."""
+    return _link_lossless_host("qexhip_link_residual_host", links, (3, 2))
 
 
 def link_packed_host(links):
     """The packed lossless link format's encoder + decoder on the host (no device needed).  links as for link_residual_host.
     Returns (escaped: bool per link, decoded: every link as decoded, shape (n, 3, 3, 2))."""
-    a = np.asarray(links)
-    if np.iscomplexobj(a):
-        a = np.stack([a.real, a.imag], axis=-1)
-    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 18)
-    n = a.shape[0]
-    esc = np.zeros(n, dtype=np.uint8)
-    dec = np.zeros((n, 3, 3, 2), dtype=np.float64)
-    check(lib().qexhip_link_packed_host(a.ctypes.data, n, esc.ctypes.data, dec.ctypes.data))
-    return esc.astype(bool), dec
+    return _link_lossless_host("qexhip_link_packed_host", links, (3, 3, 2))
 
 
 def link_ortho_host(links):
     """The orthogonal lossless link format's encoder + decoder on the host (no device needed).  links as for link_residual_host.
     Returns (escaped: bool per link, decoded: every link as decoded, shape (n, 3, 3, 2))."""
-    a = np.asarray(links)
-    if np.iscomplexobj(a):
-        a = np.stack([a.real, a.imag], axis=-1)
-    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 18)
-    n = a.shape[0]
-    esc = np.zeros(n, dtype=np.uint8)
-    dec = np.zeros((n, 3, 3, 2), dtype=np.float64)
-    check(lib().qexhip_link_ortho_host(a.ctypes.data, n, esc.ctypes.data, dec.ctypes.data))
-    return esc.astype(bool), dec
+    return _link_lossless_host("qexhip_link_ortho_host", links, (3, 3, 2))
 
 
 def half_pack_host(v):

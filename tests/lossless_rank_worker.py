@@ -1,8 +1,9 @@
-"""Worker of tests/test_gpu_lossless.py: two ranks sharing device 0 on the peer transport, t-sharded, the fused sweep forced
-(overlap 1, hop_split 2).  Each rank takes QEX g.random on its slab and computes D, stagD2ee and a fixed-length CG with option
-lossless = 1 and then 0; everything must agree bit for bit.
+"""Worker of tests/test_gpu_lossless.py, test_gpu_link_packed.py and test_gpu_link_ortho.py (lossless_links.two_ranks): two ranks
+sharing device 0 on the peer transport, t-sharded, the fused sweep forced (overlap 1, hop_split 2).  Each rank takes QEX g.random on
+its slab and computes D, stagD2ee and a fixed-length CG with option lossless = FORM (1 the 108-byte residual form, 2 the packed
+100-byte form, 3 the orthogonal 92-byte form) and then 0; everything must agree bit for bit.
 
-  python -m torch.distributed.run --nproc-per-node 2 tests/lossless_rank_worker.py LX LY LZ LT_GLOBAL
+  python -m torch.distributed.run --nproc-per-node 2 tests/lossless_rank_worker.py FORM LX LY LZ LT_GLOBAL
 
 Prints one line `LOSSLESS rank r {...}` per rank.
 """
@@ -17,7 +18,8 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    lat = [int(v) for v in sys.argv[1:5]]
+    form = int(sys.argv[1])
+    lat = [int(v) for v in sys.argv[2:6]]
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     import torch.distributed as dist
@@ -41,7 +43,7 @@ def main():
     ctx.set_option("overlap", 1)
     ctx.set_option("hop_split", 2)
     res, out = {}, {"rank": rank}
-    for lossless in (1, 0):
+    for lossless in (form, 0):
         ctx.set_option("lossless", lossless)
         s = q.newStag(ctx, g)
         r = {"storage": s.links_storage(), "form": 2 if ctx.sweep_tuning()["form"] == "fused" else 0}
@@ -55,8 +57,8 @@ def main():
         s.solveEE(x, b, 0.1, sp, histcap=80)
         r["hist"], r["x"], r["its"] = np.array(sp.r2hist), x.copy(), int(sp.iterations)
         res[lossless] = r
-    out["storage"], out["storage_ref"], out["form"] = res[1]["storage"], res[0]["storage"], res[1]["form"]
-    out["equal"] = {k: bool(np.array_equal(res[1][k], res[0][k])) for k in ("D", "stagD2ee", "hist", "x", "its")}
+    out["storage"], out["storage_ref"], out["form"] = res[form]["storage"], res[0]["storage"], res[form]["form"]
+    out["equal"] = {k: bool(np.array_equal(res[form][k], res[0][k])) for k in ("D", "stagD2ee", "hist", "x", "its")}
     sys.stdout.write("\nLOSSLESS rank %d %s\n" % (rank, json.dumps(out)))
     sys.stdout.flush()
     os._exit(0)

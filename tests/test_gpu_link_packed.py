@@ -7,75 +7,16 @@ must be BITWISE the one of the 18-real links (option lossless = 0) -- the format
   injected escapes                       a rows-0,1 entry outside the window escapes the link (read whole from the 18 reals) and keeps
                                          the bits; above 1 % escaped the choice falls to the 108-byte format under its own rule, then
                                          to 18 reals
-  two ranks sharing one device           t-sharded, peer transport, the fused sweep forced (tests/link_packed_rank_worker.py)
+  two ranks sharing one device           t-sharded, peer transport, the fused sweep forced (tests/lossless_rank_worker.py 2)
   lock-step batch                        solveXX_batch, 1..4 systems: it keeps reading the 18 reals, the results are those of lossless = 0
 """
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from oracle import oracle as o
+from lossless_links import OPS, _ctx, _gauge, _ops, _ref, two_ranks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-
-OPS = ("D", "stagD2ee", "stagD2oo", "stagD_even", "stagD_odd")
-_cache = {}
-
-
-def _gauge(lat, seed=987654321):
-    key = ("g", tuple(lat), seed)
-    if key not in _cache:
-        lo = o.Layout(lat)
-        rf = o.RngField(lo, o.RNG_MILC6, seed)
-        g = o.gauge_random(lo, rf)
-        o.rephase(lo, g)
-        x = o.vector_gaussian(lo, rf)
-        _cache[key] = (lo, g, x)
-    return _cache[key]
-
-
-def _ctx(lat):
-    import qex_amd as q
-
-    key = ("ctx", tuple(lat))
-    if key not in _cache:
-        _cache[key] = q.Context(lat)
-    return _cache[key]
-
-
-def _ops(ctx, g, x, lossless):
-    """Everything the sweeps compute on these links, with option lossless as given."""
-    import qex_amd as q
-
-    ctx.set_option("lossless", lossless)
-    s = q.newStag(ctx, g)
-    out = {"info": s.links_info(), "storage": s.links_storage()}
-    r = np.zeros_like(x)
-    s.D(r, x, 0.1)
-    out["D"] = r.copy()
-    for name in ("stagD2ee", "stagD2oo"):
-        r = np.zeros_like(x)
-        getattr(s, name)(r, x, 0.01)
-        out[name] = r.copy()
-    for par in ("even", "odd"):
-        r = np.zeros_like(x)
-        s.stagD(r, x, par, 0.1)
-        out["stagD_" + par] = r.copy()
-    return s, out
-
-
-def _ref(lat, seed=987654321):
-    """the 18-real results on the unmodified links of (lat, seed): computed once"""
-    key = ("ref", tuple(lat), seed)
-    if key not in _cache:
-        _, g, x = _gauge(lat, seed)
-        _cache[key] = _ops(_ctx(lat), g, x, 0)[1]
-    return _cache[key]
 
 
 @pytest.mark.parametrize("lat", [[8, 8, 8, 8], [4, 6, 10, 6], [16, 16, 16, 16]])
@@ -196,20 +137,7 @@ def test_packed_above_one_percent_lands_on_the_108_byte_format():
 
 
 def test_two_ranks_sharing_one_device_fused_sweep():
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
-    import socket
-
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "link_packed_rank_worker.py"), "16", "16", "16", "32"]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT, env=env)
-    ok = [json.loads(ln.split(" ", 3)[3]) for ln in p.stdout.splitlines() if ln.startswith("PACKED rank")]
-    if p.returncode != 0 or len(ok) != 2:
-        print(p.stdout[-3000:])
-        print(p.stderr[-6000:])
-    assert p.returncode == 0 and len(ok) == 2
+    ok = two_ranks(2)
     for r in ok:
         assert r["form"] == 2 and r["storage"][0] == 100 and r["storage_ref"][0] == 144, r
         assert r["equal"] == {"D": True, "stagD2ee": True, "hist": True, "x": True, "its": True}, r

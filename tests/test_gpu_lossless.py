@@ -4,52 +4,17 @@
   D, stagD2ee / stagD2oo                 8^4 and 32^4 QEX g.random, both parities
   CG (solveEE)                           32^4: residual history, solution and iteration count; the history checks the sweeps'
                                          DOT partial sums (<p, Ap> of every iteration comes from them)
-  two ranks sharing one device           t-sharded, peer transport, the fused sweep forced (tests/lossless_rank_worker.py)
+  two ranks sharing one device           t-sharded, peer transport, the fused sweep forced (tests/lossless_rank_worker.py 1)
   injected defects                       escaped links (row 2 read from the 18 reals) keep the bits; above 1 % escaped the choice
                                          falls back to 18 reals
 """
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from oracle import oracle as o
+from lossless_links import _gauge, _ops, two_ranks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-
-
-def _gauge(lat, seed=987654321):
-    lo = o.Layout(lat)
-    rf = o.RngField(lo, o.RNG_MILC6, seed)
-    g = o.gauge_random(lo, rf)
-    o.rephase(lo, g)
-    x = o.vector_gaussian(lo, rf)
-    return lo, g, x
-
-
-def _ops(ctx, g, x, lossless):
-    """Everything the sweeps compute on these links, with option lossless as given."""
-    import qex_amd as q
-
-    ctx.set_option("lossless", lossless)
-    s = q.newStag(ctx, g)
-    out = {"info": s.links_info(), "storage": s.links_storage()}
-    r = np.zeros_like(x)
-    s.D(r, x, 0.1)
-    out["D"] = r.copy()
-    for name in ("stagD2ee", "stagD2oo"):
-        r = np.zeros_like(x)
-        getattr(s, name)(r, x, 0.01)
-        out[name] = r.copy()
-    for par in ("even", "odd"):
-        r = np.zeros_like(x)
-        s.stagD(r, x, par, 0.1)
-        out["stagD_" + par] = r.copy()
-    return s, out
 
 
 @pytest.mark.parametrize("lat", [[8, 8, 8, 8], [32, 32, 32, 32]])
@@ -143,20 +108,7 @@ def test_recon_0_keeps_the_format_off_and_compressible_links_keep_theirs():
 
 
 def test_two_ranks_sharing_one_device_fused_sweep():
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
-    import socket
-
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "lossless_rank_worker.py"), "16", "16", "16", "32"]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT, env=env)
-    ok = [json.loads(ln.split(" ", 3)[3]) for ln in p.stdout.splitlines() if ln.startswith("LOSSLESS rank")]
-    if p.returncode != 0 or len(ok) != 2:
-        print(p.stdout[-3000:])
-        print(p.stderr[-6000:])
-    assert p.returncode == 0 and len(ok) == 2
+    ok = two_ranks(1)
     for r in ok:
         assert r["form"] == 2 and r["storage"][0] == 108 and r["storage_ref"][0] == 144, r
         assert r["equal"] == {"D": True, "stagD2ee": True, "hist": True, "x": True, "its": True}, r
