@@ -14,14 +14,12 @@ Exit status 0 and one line `DEFL_BATCH_RANKS_OK [json per rank]` from rank 0, no
 """
 import ctypes as C
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ranks
+
 NEV, NVECS, R2REQ = 8, 24, 1e-20
 MS = [0.01, 0.01, 0.02, 0.05]
 OPTS = dict(relerr=0.0, abserr=1e-9, cheb_degree=8, cheb_lo=0.3, cheb_hi=0.0, max_restarts=60)     # those of eig_rank_worker.py
@@ -29,11 +27,7 @@ OPTS = dict(relerr=0.0, abserr=1e-9, cheb_degree=8, cheb_lo=0.3, cheb_hi=0.0, ma
 
 def main():
     glat = tuple(int(v) for v in sys.argv[1:5])
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
     import eig_ref as R
     from oracle import oracle as o
@@ -42,17 +36,8 @@ def main():
     rf = o.RngField(lo, o.RNG_MILC6, 4242)
     bs = [np.ascontiguousarray(b)] + [o.vector_gaussian(lo, rf) for _ in range(3)]
     glo = q.Layout(list(glat))
-    loc, idx = glo.shard_indices(world, rank)
-
-    def sl(a):
-        return np.ascontiguousarray(a[idx])
-
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
     ctx.force_halo(True)                                              # (t is sharded: the halo is on already)
-    assert ctx.comm_transport()[0] == "peer" and ctx.sweep_info()["halo"]
+    assert ctx.sweep_info()["halo"]
     ref = q.Context(list(glat), device=0)
     s, s1 = q.newStag(ctx, sl(g)), q.newStag(ref, g)
     B = s.eigs(NEV, nvecs=NVECS, **OPTS)
@@ -89,13 +74,10 @@ def main():
     assert mine["sloppy_rc"] == -1, mine["sloppy_rc"]
     assert np.array_equal(ctx.field_download(xid[0]), before)         # nothing was launched
     print("rank %d: %s" % (rank, json.dumps(mine)), file=sys.stderr, flush=True)
-    allr = [None] * world
-    dist.all_gather_object(allr, mine)
+    allr = ranks.gather(rk, mine)
     for name in ("even", "odd"):
         assert len({(tuple(a[name]["its"]), tuple(a[name]["r2"])) for a in allr}) == 1, allr
-    if rank == 0:
-        print("DEFL_BATCH_RANKS_OK %s" % json.dumps(allr), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "DEFL_BATCH_RANKS_OK", mine)
     B.free()
     B1.free()
     return 0

@@ -12,42 +12,27 @@ usage: python -m torch.distributed.run --nproc-per-node N eig_rank_worker.py LX 
 Exit status 0 and one line `EIG_RANKS_OK [json per rank]` from rank 0, non-zero on the first failed check.
 """
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ranks
+
 NEV, NVECS, MASS, R2REQ = 8, 24, 0.01, 1e-20
 OPTS = dict(relerr=0.0, abserr=1e-9, cheb_degree=8, cheb_lo=0.3, cheb_hi=0.0, max_restarts=60)     # (a numpy model: 9 restarts)
 
 
 def main():
     glat = tuple(int(v) for v in sys.argv[1:5])
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
     import eig_ref as R
 
     lo, g, _, b = R.inputs(glat)
     _, w, _ = R.dense(glat)
     vh = lo.vol // 2
-    loc, idx = q.Layout(list(glat)).shard_indices(world, rank)
-
-    def sl(a):
-        return np.ascontiguousarray(a[idx])
-
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
     ctx.force_halo(True)                                              # (t is sharded: the halo is on already)
-    assert ctx.comm_transport()[0] == "peer" and ctx.sweep_info()["halo"]
+    assert ctx.sweep_info()["halo"]
     ref = q.Context(list(glat), device=0)
     s, s1 = q.newStag(ctx, sl(g)), q.newStag(ref, g)
     B = s.eigs(NEV, nvecs=NVECS, **OPTS)
@@ -83,14 +68,11 @@ def main():
     mine.update({"deflated_its": its, "plain_its": its0, "one_rank_deflated_its": its1, "r2": r2, "one_rank_r2": r21,
                  "oracle_resid_max": worst, "orth": orth, "max_eval_dev": float(np.abs(B.evals - w[:NEV]).max())})
     print("rank %d: %s" % (rank, json.dumps(mine)), file=sys.stderr, flush=True)
-    allr = [None] * world
-    dist.all_gather_object(allr, mine)
+    allr = ranks.gather(rk, mine)
     assert len({(a["deflated_its"], a["r2"]) for a in allr}) == 1, allr
     assert abs(its - its1) <= max(2, 0.02 * its1), (its, its1)
     assert r2 <= R2REQ * (1 + 1e-3), r2
-    if rank == 0:
-        print("EIG_RANKS_OK %s" % json.dumps(allr), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "EIG_RANKS_OK", mine)
     B.free()
     B1.free()
     return 0

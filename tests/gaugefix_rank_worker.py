@@ -13,36 +13,24 @@ usage: python -m torch.distributed.run --nproc-per-node N gaugefix_rank_worker.p
 Exit status 0 and one line `GAUGEFIX_RANKS_OK [json per rank]` from rank 0, non-zero on the first failed check.
 """
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ranks
+
 GSTOP = 1e-8
 
 
 def main():
     glat = [int(v) for v in sys.argv[1:5]]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
     from oracle import oracle as o
     import gaugefix_ref as R
 
     o.build()
     glo, g = R.warm_rotated(o, tuple(glat))
-    loc, idx = glo.shard_indices(world, rank)
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     ref = q.Context(glat, device=0)
     res = {"rank": rank}
 
@@ -86,11 +74,7 @@ def main():
         assert np.abs(pl - p1).max() < 1e-13 and abs(ltl - lt1) < 1e-13 and abs(ltl - il["met"]) < 1e-13, (name, pl, p1, ltl, lt1)
         res[name] = mine
 
-    allres = [None] * world
-    dist.all_gather_object(allres, res)
-    if rank == 0:
-        print("GAUGEFIX_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "GAUGEFIX_RANKS_OK", res)
     return 0
 
 

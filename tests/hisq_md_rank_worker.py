@@ -14,38 +14,25 @@ usage: python -m torch.distributed.run --nproc-per-node N hisq_md_rank_worker.py
 Exit status 0 and one line `HISQ_MD_RANKS_OK [json per rank]` from rank 0, non-zero on the first failed check.
 """
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ranks
+
 SCALES = [0.7, -1.3, 0.45]
 DT, T = 0.05, -0.37
 
 
 def main():
     glat = [int(v) for v in sys.argv[1:5]]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
 
-    glo = q.Layout(glat)
     rng = q.RngField(glat, q.RngMilc6, 4711)
     g, p = rng.warm(0.3), rng.randomTAH()
     v = [rng.gaussian_vector() for _ in range(3)]
-    loc, idx = glo.shard_indices(world, rank)
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     ref = q.Context(glat, device=0)
-    sl = lambda a: np.ascontiguousarray(a[idx])
 
     def same(what, mine, whole):
         if not np.array_equal(mine, whole[idx]):
@@ -73,12 +60,9 @@ def main():
     dev = float(np.abs(fsl - fs1[idx]).max() / np.abs(fs1).max())
     mine = {"rank": rank, "iters": itsl, "one_rank_iters": its1, "solve_force_dev": dev}
     print("rank %d solve + force: %s" % (rank, json.dumps(mine)), file=sys.stderr, flush=True)
-    allres = [None] * world
-    dist.all_gather_object(allres, mine)
+    allres = ranks.gather(rk, mine)
     assert len({tuple(a["iters"]) for a in allres}) == 1, allres
-    if rank == 0:
-        print("HISQ_MD_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "HISQ_MD_RANKS_OK", mine)
     return 0
 
 

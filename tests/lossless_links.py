@@ -3,15 +3,12 @@ Context per lattice, everything the sweeps compute on a set of links under a giv
 (computed once per lattice and seed, never changed) and the two-rank launch of tests/lossless_rank_worker.py."""
 import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 
 from oracle import oracle as o
+from ranks import ROOT, launch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPS = ("D", "stagD2ee", "stagD2oo", "stagD_even", "stagD_odd")
 _cache = {}
 
@@ -75,13 +72,7 @@ def _stored(g):
 
 def two_ranks(form, lat=(16, 16, 16, 32)):
     """tests/lossless_rank_worker.py on two ranks sharing one device: the two `LOSSLESS rank r {...}` records"""
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        port = so.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "tests", "lossless_rank_worker.py"), str(form)] + [str(v) for v in lat]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, cwd=ROOT, env=env)
+    p = launch(2, [os.path.join(ROOT, "tests", "lossless_rank_worker.py"), form] + list(lat), 300)
     ok = [json.loads(ln.split(" ", 3)[3]) for ln in p.stdout.splitlines() if ln.startswith("LOSSLESS rank")]
     if p.returncode != 0 or len(ok) != 2:
         print(p.stdout[-3000:])

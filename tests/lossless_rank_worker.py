@@ -13,33 +13,23 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ranks
 
 
 def main():
     form = int(sys.argv[1])
     lat = [int(v) for v in sys.argv[2:6]]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    os.environ["QEXHIP_TRANSPORT"] = "peer"           # insisted on, not found out by comparing devices
+    rk = ranks.shard(lat)
+    rank, ctx = rk.rank, rk.ctx
     import qex_amd as q
     from oracle import oracle as o
 
-    loc = list(lat)
-    loc[3] //= world
-    lo = o.Layout(loc)
+    lo = o.Layout(rk.loc.lat)
     rf = o.RngField(lo, o.RNG_MILC6, 987654321 + rank)
     g = o.gauge_random(lo, rf)
     o.rephase(lo, g)
     b = o.vector_gaussian(lo, rf)
-    ctx = q.Context(loc, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    ctx.set_option("transport", 2)
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
     ctx.set_option("overlap", 1)
     ctx.set_option("hop_split", 2)
     res, out = {}, {"rank": rank}

@@ -15,9 +15,8 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ranks
+
 SEED = 987654321
 
 
@@ -25,12 +24,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lat", type=int, nargs=4)
     args = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    # (one rank: a context without a communicator; the transport is not asserted here)
+    rank, world, dist, ctx, loc, idx, sl = ranks.shard(args.lat, peer=False, comm=int(os.environ["WORLD_SIZE"]) > 1)
     import qex_amd as q
     import meson_ref as mr
     from oracle import oracle as o
@@ -42,15 +37,7 @@ def main():
     o.rephase(olo, g)
     rng = np.random.default_rng(7)
     fs = [rng.standard_normal((glo.vol, 3, 2)) for _ in range(6)]
-    loc, idx = glo.shard_indices(world, rank)
     lt = glat[3] // world
-    if world > 1:
-        ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-        uid = [q.Context.unique_id() if rank == 0 else None]
-        dist.broadcast_object_list(uid, src=0)
-        ctx.comm_init(uid[0], world, rank)
-    else:
-        ctx = q.Context(loc.lat)
     ids = [ctx.field_new(np.ascontiguousarray(f[idx])) for f in fs]
     tables = {}
     for name, xs, ys, t0 in (("pairs3", ids[:3], ids[3:6], 3), ("one_wrap", ids[:1], ids[1:2], glat[3] - 1), ("norm", ids[:1], ids[:1], 0)):

@@ -14,14 +14,12 @@ usage: python -m torch.distributed.run --nproc-per-node N rational_rank_worker.p
 Exit status 0 and one line `RATIONAL_RANKS_OK [json per rank]` from rank 0, non-zero on the first failed check.
 """
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ranks
+
 MASS, F0 = 0.3, 0.37
 ALPHA, BETA = [0.3, -0.5, 0.9, 1.7, 0.6], [0.4, 0.05, 6.0, 1.5, 0.0]
 T, MAXITS = -0.37, 5000
@@ -29,29 +27,17 @@ T, MAXITS = -0.37, 5000
 
 def main():
     glat = [int(v) for v in sys.argv[1:5]]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
     import rational_ref as RR
     from oracle import oracle as o
 
-    glo = q.Layout(glat)
     rng = q.RngField(glat, q.RngMilc6, 4711)
     g, p = rng.warm(0.3), rng.randomTAH()
     b = rng.gaussian_vector()
     phi = b.copy()
     phi[phi.shape[0] // 2:] = 0
-    loc, idx = glo.shard_indices(world, rank)
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     ref = q.Context(glat, device=0)
-    sl = lambda a: np.ascontiguousarray(a[idx])
 
     out = []
     for c, cut in ((ref, lambda a: a), (ctx, sl)):
@@ -94,12 +80,9 @@ def main():
     assert nr > 0 and np.abs(f1).max() > 1e-3
     assert dn <= 4.0 * do + 1e-15 * nr, (rank, dn / nr, do / nr)
     assert fdev <= 2e-11, (rank, fdev)
-    allres = [None] * world
-    dist.all_gather_object(allres, mine)
+    allres = ranks.gather(rk, mine)
     assert len({(a["iters"], a["force_iters"]) for a in allres}) == 1, allres
-    if rank == 0:
-        print("RATIONAL_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "RATIONAL_RANKS_OK", mine)
     return 0
 
 

@@ -15,36 +15,24 @@ usage: python -m torch.distributed.run --nproc-per-node N scalar_trace_rank_work
 Exit status 0 and one line `SCALAR_TRACE_RANKS_OK [json per rank]` from rank 0, non-zero on the first failed check.
 """
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ranks
+
 SEED = 987654321
 
 
 def main():
     glat = [int(v) for v in sys.argv[1:5]]
     e2e = len(sys.argv) > 5 and sys.argv[5] == "e2e"
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
     import scalar_trace_ref as R
 
     glo = q.Layout(glat)
-    loc, idx = glo.shard_indices(world, rank)
     lt = loc.lat[3]
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     ref = q.Context(glat, device=0)
     res = {"rank": rank}
 
@@ -104,11 +92,7 @@ def main():
         print("rank %d e2e: %s" % (rank, json.dumps(res["e2e"])), file=sys.stderr, flush=True)
         assert de < 1e-9 and dt < 1e-9, res["e2e"]
 
-    allres = [None] * world
-    dist.all_gather_object(allres, res)
-    if rank == 0:
-        print("SCALAR_TRACE_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "SCALAR_TRACE_RANKS_OK", res)
     ctx.close()
     ref.close()
     return 0

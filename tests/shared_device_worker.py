@@ -16,8 +16,7 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ranks
 
 
 def main():
@@ -28,23 +27,14 @@ def main():
     ap.add_argument("--forms", type=int, nargs="+", default=[0, 2], help="hop_split values to run, in order")
     ap.add_argument("--distinct-devices", action="store_true", help="rank r binds device LOCAL_RANK instead of device 0 (scratch/first_contact.sh)")
     args = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    sys.path.insert(0, ranks.ROOT)
     import qex_amd as q
 
-    loc = list(args.lat)
-    loc[3] //= world
+    dev = int(os.environ.get("LOCAL_RANK", os.environ["RANK"])) % max(q.device_count(), 1) if args.distinct_devices else 0
+    rk = ranks.shard(args.lat, device=dev, peer=False)
+    rank, ctx, loc = rk.rank, rk.ctx, rk.loc.lat
     vol = int(np.prod(loc))
     rng = np.random.default_rng(1234 + rank)
-    dev = int(os.environ.get("LOCAL_RANK", rank)) % max(q.device_count(), 1) if args.distinct_devices else 0
-    ctx = q.Context(loc, device=dev, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
     ctx.set_option("overlap", 1)
     g = (0.35 * rng.standard_normal((vol, 4, 3, 3, 2))).astype(np.float64)
     g3 = (0.1 * rng.standard_normal((vol, 4, 3, 3, 2))).astype(np.float64) if args.naik else None

@@ -11,13 +11,12 @@ Exit status 0 and one line `SLOPPY_MULTI_RANKS_OK [json per rank]` from rank 0, 
 """
 import argparse
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ranks
+
 SEED = 987654321
 MASSES = [0.05, 0.1, 0.2, 0.4]
 R2REQ = 1e-14
@@ -27,11 +26,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lat", type=int, nargs=4)
     args = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(args.lat)
     import qex_amd as q
     from oracle import oracle as o
 
@@ -43,16 +38,6 @@ def main():
     lng = o.gauge_random(olo, rf)
     o.rephase(olo, lng)
     b = o.vector_gaussian(olo, rf)
-    loc, idx = q.Layout(glat).shard_indices(world, rank)
-
-    def sl(a):
-        return np.ascontiguousarray(a[idx])
-
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     sh = [MASSES[0]] + [4.0 * (m * m - MASSES[0] ** 2) for m in MASSES[1:]]
     h = olo.vol // 2
     res = {"rank": rank}
@@ -90,11 +75,7 @@ def main():
                 assert abs(fin[k] - oracle_r2[k]) <= 1e-4 * oracle_r2[k], (key, k, mine)
             res[key] = mine
 
-    allres = [None] * world
-    dist.all_gather_object(allres, res)
-    if rank == 0:                                                     # (one line: the ranks' stdout interleaves)
-        print("SLOPPY_MULTI_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "SLOPPY_MULTI_RANKS_OK", res)
     return 0
 
 

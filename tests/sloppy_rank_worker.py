@@ -17,13 +17,12 @@ Exit status 0 and one line `SLOPPY_RANKS_OK [json per rank]` from rank 0, non-ze
 """
 import argparse
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ranks
+
 SEED = 987654321
 FORMS = (("exchange_first", 0, 0), ("by_sites", 1, 0), ("fused_requested", 1, 2))     # (name, overlap, hop_split)
 
@@ -34,11 +33,7 @@ def main():
     ap.add_argument("--op", action="store_true")
     ap.add_argument("--solve", action="store_true")
     args = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(args.lat)
     import qex_amd as q
     from oracle import oracle as o
 
@@ -56,16 +51,6 @@ def main():
         o.rephase(olo, hfat)
         o.rephase(olo, hlng)
         links["hisq"] = (hfat, hlng, 0)
-    loc, idx = q.Layout(glat).shard_indices(world, rank)
-
-    def sl(a):
-        return np.ascontiguousarray(a[idx])
-
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     ref = q.Context(glat, device=0)                                   # the one-rank operator / solve on the whole lattice
     res = {"rank": rank}
 
@@ -154,11 +139,7 @@ def main():
                 assert abs(sp.iterations - sp1.iterations) <= max(5, sp1.iterations // 20), (res_key, mine)
                 res["solve"][res_key] = mine
 
-    allres = [None] * world
-    dist.all_gather_object(allres, res)
-    if rank == 0:                                                     # (one line: the ranks' stdout interleaves)
-        print("SLOPPY_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "SLOPPY_RANKS_OK", res)
     return 0
 
 

@@ -12,24 +12,18 @@ usage: python -m torch.distributed.run --nproc-per-node N stout_rank_worker.py L
 Exit status 0 and one line `STOUT_RANKS_OK [json per rank]` from rank 0, non-zero on the first failed check.
 """
 import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ranks
+
 ALPHAS = (0.1, 0.09, 0.12)
 
 
 def main():
     glat = [int(v) for v in sys.argv[1:5]]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, gathers)
+    rank, world, dist, ctx, loc, idx, sl = rk = ranks.shard(glat)
     import qex_amd as q
     from oracle import oracle as o
     import stout_ref as R
@@ -40,15 +34,8 @@ def main():
     g = R.reference_config(olo, 0.1)
     rf = o.RngField(olo, o.RNG_MILC6, 21)
     chain = o.gauge_random_tah(olo, rf) + 0.3 * o.gauge_random(olo, rf)
-    loc, idx = glo.shard_indices(world, rank)
-    ctx = q.Context(loc.lat, device=0, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    assert ctx.comm_transport()[0] == "peer"
     ref = q.Context(glat, device=0)
     res = {"rank": rank}
-    sl = lambda a: np.ascontiguousarray(a[idx])
 
     def same(what, mine, whole):
         if not np.array_equal(mine, whole[idx]):
@@ -98,11 +85,7 @@ def main():
     assert abs(itl - it1) <= 1 and d2 <= 1e-24, mine
     res["inverse"] = mine
 
-    allres = [None] * world
-    dist.all_gather_object(allres, res)
-    if rank == 0:
-        print("STOUT_RANKS_OK %s" % json.dumps(allres), flush=True)
-    dist.barrier()
+    ranks.finish(rk, "STOUT_RANKS_OK", res)
     return 0
 
 

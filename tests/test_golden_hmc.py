@@ -167,14 +167,9 @@ def test_gpu_replays_reference_trajectory_over_real_ranks(run, resident):
     nHYP closure and force chain, fermion forces with their Hasenbusch solves, adjoint-plaquette gauge force, force-gradient
     updates (run 1, MD loop resident on the device), all t-sharded with faces and sums crossing between processes
     (tests/golden_rank_worker.py)."""
-    import subprocess
-    import sys
+    from ranks import ROOT, launch
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4", QEXHIP_PEER_TIMEOUT="60")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(29581 + run), os.path.join(root, "tests", "golden_rank_worker.py"), str(run), str(int(resident))]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=root, env=env)
+    p = launch(2, [os.path.join(ROOT, "tests", "golden_rank_worker.py"), run, int(resident)], 900, env={"QEXHIP_PEER_TIMEOUT": "60"})
     ok = [ln for ln in p.stdout.splitlines() if ln.startswith("GOLDEN_RANK_OK")]
     if p.returncode != 0 or len(ok) != 2:
         print(p.stdout[-3000:])

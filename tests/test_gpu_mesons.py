@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import qex_amd as q  # noqa: E402
 import meson_ref as mr  # noqa: E402
 from oracle import oracle as o  # noqa: E402
+from ranks import launch  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SEED = 987654321
@@ -187,24 +188,8 @@ def test_tables_are_gauge_invariant():
 
 
 # ---- ranks: every rank its own process (torch.distributed.run), all sharing the one device, as tests/test_gpu_two_ranks.py ----
-def _free_port():
-    import socket
-
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        return so.getsockname()[1]
-
-
-def _launch(nranks, script_args, timeout=600):
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", QEXHIP_PEER_TIMEOUT="60",
-               OMP_NUM_THREADS=str(max(1, min(16, len(os.sched_getaffinity(0))) // nranks)))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port())] + script_args
-    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, cwd=ROOT, env=env)
-
-
 def _worker(nranks, lat):
-    p = _launch(nranks, [os.path.join(ROOT, "tests", "meson_rank_worker.py")] + [str(v) for v in lat])
+    p = launch(nranks, [os.path.join(ROOT, "tests", "meson_rank_worker.py")] + lat, 600, env={"QEXHIP_PEER_TIMEOUT": "60"})
     # (the launcher multiplexes the ranks' output and may join two records on one line: match records, not lines)
     ok = re.findall(r"MESON_RANK_OK \d+ (\{[^{}]*\})", p.stdout)
     if p.returncode != 0 or len(ok) != nranks:
@@ -244,7 +229,7 @@ def test_example_on_one_and_two_ranks():
     ex = os.path.join(ROOT, "examples", "stag_mesons.py")
     p1 = subprocess.run([sys.executable, ex] + lat, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
     assert p1.returncode == 0, p1.stderr[-4000:]
-    p2 = _launch(2, [ex] + lat)
+    p2 = launch(2, [ex] + lat, 600, env={"QEXHIP_PEER_TIMEOUT": "60"})
     if p2.returncode != 0:
         print(p2.stdout[-4000:])
         print(p2.stderr[-8000:])

@@ -181,19 +181,15 @@ def test_bench_two_ranks_share_one_gpu(nranks):
     other process: the self-verification against the committed single-GPU numbers must pass (round 4 could only rehearse the
     control flow here, each rank wrapping its own slab).  One parsable line that carries both ranks."""
     import json
-    import os
-    import subprocess
-    import sys
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from ranks import ROOT, launch
+
     # QEXHIP_OVERLAP=1 QEXHIP_HOP_SPLIT=2 (left to itself set_links finds that overlapping does not pay between two processes on ONE
     # chip and posts the exchange first): the fused self-pushing sweep -- what 8 GPUs run -- on BOTH legs, the 48^3 x 96 one included (its HISQ Naik
     # multi-shift self-check has 1 296 boundary workgroups per sweep: the case that ran round 5's build into the wait bound,
     # profiles/r06_notes.md section 1)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4", QEX_BENCH_FORCE_CANARY="1", QEXHIP_HOP_SPLIT="2", QEXHIP_OVERLAP="1", QEXHIP_PEER_TIMEOUT="20")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(29531 + nranks), os.path.join(root, "bench.py"), "--gpus", str(nranks), "--steps", "20", "--warmup", "5", "--full"]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root, env=env)
+    p = launch(nranks, [os.path.join(ROOT, "bench.py"), "--gpus", nranks, "--steps", "20", "--warmup", "5", "--full"], 600,
+               env={"QEX_BENCH_FORCE_CANARY": "1", "QEXHIP_HOP_SPLIT": "2", "QEXHIP_OVERLAP": "1", "QEXHIP_PEER_TIMEOUT": "20"})
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2000:])
     lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1

@@ -5,39 +5,13 @@ The ranks are started by torch.distributed.run as fresh processes that all bind 
 (tests/sloppy_rank_worker.py checks every rank's slab against a one-rank context of the whole lattice).  The one-rank halo path --
 ghost zones filled by the periodic wrap, exchanges delayed by the transport emulation -- runs in this process.  Observed values are
 printed (pytest -s)."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
+from ranks import launch_ok
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 987654321
-
-
-def _free_port():
-    import socket
-
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        return so.getsockname()[1]
-
-
-def _launch(nranks, script_args, timeout=600):
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", QEXHIP_PEER_TIMEOUT="60",
-               OMP_NUM_THREADS=str(max(1, min(16, len(os.sched_getaffinity(0))) // nranks)))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "sloppy_rank_worker.py")] + script_args
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, cwd=ROOT, env=env)
-    ok = [ln for ln in p.stdout.splitlines() if ln.startswith("SLOPPY_RANKS_OK ")]
-    print(p.stderr[-6000:] if (p.returncode != 0 or len(ok) != 1) else "\n".join(ln for ln in p.stderr.splitlines() if ln.startswith("rank ")))
-    assert p.returncode == 0 and len(ok) == 1, (p.returncode, p.stdout[-2000:])
-    res = json.loads(ok[0].split(" ", 1)[1])
-    assert [r["rank"] for r in res] == list(range(nranks))
-    return res
 
 
 @pytest.mark.parametrize("nranks,lat", [(2, [8, 8, 8, 8]), (2, [16, 16, 16, 32]), (4, [8, 8, 8, 16])])
@@ -45,7 +19,7 @@ def test_sharded_fp32_operator_is_the_one_rank_operator_bit_for_bit(nranks, lat)
     """dev_op_xx_sloppy on every rank's slab == the slab of the one-rank dev_op_xx_sloppy (np.array_equal): g.random links (sign
     format), g.random + Naik (ghost depth 3), HISQ (18 reals); exchange-first, split by sites, and hop_split 2 (the fp32 sweep has no
     fused form and runs split by sites there: the worker counts its boundary launches)."""
-    res = _launch(nranks, [str(v) for v in lat] + ["--op"])
+    res = launch_ok(nranks, "sloppy_rank_worker.py", lat + ["--op"], "SLOPPY_RANKS_OK", 600, env={"QEXHIP_PEER_TIMEOUT": "60"})
     for r in res:
         assert len(r["op"]) == 9, r["op"].keys()
         assert r["op"]["random/fused_requested"]["launches"][1] == 4 and r["op"]["hisq/fused_requested"]["fmt"] == 0
@@ -55,7 +29,7 @@ def test_sharded_fp32_operator_is_the_one_rank_operator_bit_for_bit(nranks, lat)
 def test_sharded_sloppy_solve_converges_on_the_true_residual(nranks, lat):
     """solveEE and solve (ReconL / ReconR) at r2req 1e-8 and 1e-14: true residual of the gathered solution <= r2req (oracle, fp64),
     the same iterations and reliable updates on every rank, within a few iterations of the one-rank sloppy solve."""
-    res = _launch(nranks, [str(v) for v in lat] + ["--solve"])
+    res = launch_ok(nranks, "sloppy_rank_worker.py", lat + ["--solve"], "SLOPPY_RANKS_OK", 600, env={"QEXHIP_PEER_TIMEOUT": "60"})
     for key, v in res[0]["solve"].items():
         print(f"{nranks} ranks {lat} {key}: {v['its']} its / {v['nupd']} updates (one rank: {v['one_rank_its']} / {v['one_rank_nupd']}), "
               f"true r2/b2 {v['oracle_r2']:.2e}")

@@ -8,12 +8,13 @@ import ctypes as C
 import json
 import os
 import re
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from ranks import free_port, launch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -141,18 +142,10 @@ def test_shard_indices_roundtrip():
     assert np.all(seen == 1)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 @pytest.mark.parametrize("naik", [0, 1])
 def test_sharded_dslash_two_ranks_gloo(naik):
     """world_size 2, gloo, CPU: t-sharded stagD2 == global stagD2 on every slab."""
-    port = _free_port()
+    port = free_port()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), OMP_NUM_THREADS="2")
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "sharded_rehearsal.py"),
                                str(r), "2", str(naik)], env=env, stdout=subprocess.PIPE,
@@ -227,10 +220,7 @@ def test_repeated_block_configuration_is_the_periodic_one():
 
 
 def _torchrun_bench(nproc, extra, timeout=180):
-    port = _free_port()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "5", "--warmup", "1"] + extra
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, cwd=ROOT)
+    p = launch(nproc, [os.path.join(ROOT, "bench.py"), "--gpus", nproc, "--steps", "5", "--warmup", "1"] + extra, timeout)
     lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p.returncode, lines, p.stderr
 

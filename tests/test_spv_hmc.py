@@ -69,14 +69,11 @@ def test_gpu_spv_trajectory_over_real_ranks(nranks):
     the one GPU (peer transport) -- per-site random streams seeded by global index, so the fields are those of the single-rank
     run -- must give the single-rank energies, sector by sector, and the same end links on every slab."""
     import json
-    import subprocess
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from ranks import ROOT, launch
+
     hr, br, er = _traj(resident=True)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4", QEXHIP_PEER_TIMEOUT="60")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
-           "--master-port", "29577", os.path.join(root, "tests", "spv_rank_worker.py")] + [str(v) for v in LAT] + [json.dumps(PRM)]
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root, env=env)
+    p = launch(nranks, [os.path.join(ROOT, "tests", "spv_rank_worker.py")] + list(LAT) + [json.dumps(PRM)], 600, env={"QEXHIP_PEER_TIMEOUT": "60"})
     rows = [json.loads(ln.split(" ", 1)[1]) for ln in p.stdout.splitlines() if ln.startswith("SPV_RANK ")]
     if p.returncode != 0 or len(rows) != nranks:
         print(p.stdout[-3000:])

@@ -23,8 +23,8 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import ranks
+
 SEED = 987654321
 
 
@@ -49,13 +49,14 @@ def main():
     ap.add_argument("--share-device", action="store_true", help="every rank binds device 0: the peer-memory transport between processes "
                     "that share one GPU (RCCL refuses that), i.e. real neighbours on a one-GPU box")
     args = ap.parse_args()
-    rank, world, local_rank = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), int(os.environ["LOCAL_RANK"])
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     os.environ.setdefault("NCCL_DEBUG", "WARN")
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    import torch.distributed as dist
-
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (unique id, final barrier)
+    # (one rank is the one-GPU rehearsal of this script: the sharded code path ...)
+    rank, world, dist, ctx, loc, idx, sl = ranks.shard(args.lat, device=0 if args.share_device else int(os.environ["LOCAL_RANK"]), peer=False)
+    if world == 1:
+        ctx.force_halo(True)                                           # ... ghost zones filled through a one-rank communicator,
+        ctx.set_option("multi_reduce", 1)                              # reductions through real (one-rank) all-reduces
+        ctx.set_option("batch_multi", 1)                               # ... in the lock-step batched CG too
+    tick("context + comm_init done")
     import qex_amd as q
     from oracle import oracle as o
 
@@ -70,22 +71,7 @@ def main():
     g3 *= 0.3
     x, y = o.vector_gaussian(olo, rf), o.vector_gaussian(olo, rf)
     tick("imports + oracle inputs done")
-    loc, idx = q.Layout(glat).shard_indices(world, rank)
     vh = loc.vol // 2
-    dev = 0 if args.share_device else local_rank
-
-    if world > 1:
-        ctx = q.Context(loc.lat, device=dev, rank_geom=(1, 1, 1, world), rank_coord=(0, 0, 0, rank))
-    else:
-        ctx = q.Context(loc.lat, device=dev)                    # one-GPU rehearsal of this script: the sharded code path ...
-    uid = [q.Context.unique_id() if rank == 0 else None]
-    dist.broadcast_object_list(uid, src=0)
-    ctx.comm_init(uid[0], world, rank)
-    if world == 1:
-        ctx.force_halo(True)                                           # ... ghost zones filled through a one-rank communicator,
-        ctx.set_option("multi_reduce", 1)                              # reductions through real (one-rank) all-reduces
-        ctx.set_option("batch_multi", 1)                               # ... in the lock-step batched CG too
-    tick("context + comm_init done")
     info = ctx.comm_info()
     assert info[0] == world and info[1] == rank, info                  # RCCL's own count and rank
     transport = ctx.comm_transport()[0]
@@ -104,9 +90,6 @@ def main():
     if args.fused_spin_us != -1:
         ctx.set_option("fused_spin_us", args.fused_spin_us)
     res = {"rank": rank, "device": info[2], "pci_bus": info[3], "comms": ctx.comm_count(), "transport": transport}
-
-    def sl(a):
-        return np.ascontiguousarray(a[idx])
 
     # ---- one-hop operator ----
     s = q.newStag(ctx, sl(g))
