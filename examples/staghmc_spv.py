@@ -2,7 +2,7 @@
 """src/stagg_pv_hmc/staghmc_spv.nim -- the fork's HMC with nHYP-smeared staggered fermions, Pauli-Villars bosons and an
 optional gauge action on the smeared links -- with every field operation in libqexhip.
 
-    python examples/staghmc_spv.py [-lat 8 8 8 16] [-trajs 2] [-host-fields] [-halo] [-time]
+    python examples/staghmc_spv.py [-lat 8 8 8 16] [-trajs 2] [-host-fields] [-halo] [-time] [-sloppy 0] [-half 0]
     python -m torch.distributed.run --nproc-per-node N examples/staghmc_spv.py ...     # t-sharded over N ranks (one GPU each, or sharing one)
 
 The driver below follows the reference's procs one to one (file:line in the docstrings); the parameters are those of
@@ -35,6 +35,7 @@ DEFAULTS = dict(
     alpha=(0.4, 0.5, 0.5), a_tol=1e-20, f_tol=1e-12, maxits=10000,           # :80-92
     seed=987654321, start="cold",
     sloppy=0,                                                                 # SolverParams.sloppySolve of every solve (-sloppy)
+    half=0,                                                                   # context option "half": -sloppy 2 on 16-bit storage (-half)
 )
 
 
@@ -72,6 +73,8 @@ class Spv:
             self.ctx = q.Context(self.lat)
         if halo:
             self.ctx.force_halo(True)
+        if P["half"]:
+            self.ctx.set_option("half", 1)              # (t-sharded too: the faces travel in the 16-bit format)
         self.md = q.ResidentMD(self.ctx)
         self.hc = q.HypCoefs(*P["alpha"])
         self.rng = q.RngField(self.lat, q.RngMilc6, P["seed"], glat=self.glat, t_offset=self.rank * lt) if self.world > 1 \
@@ -242,7 +245,8 @@ def main():
     ap.add_argument("-halo", action="store_true", help="every kernel in its t-sharded form on one GPU")
     ap.add_argument("-time", action="store_true")
     ap.add_argument("-start", default="cold", help="cold, or the spread of a warm start (e.g. 0.3)")
-    ap.add_argument("-sloppy", type=int, default=0, help="SolverParams.sloppySolve of every solve: 0 fp64, 1 mixed precision")
+    ap.add_argument("-sloppy", type=int, default=0, help="SolverParams.sloppySolve of every solve: 0 fp64, 1 mixed precision, 2 SloppyHalf")
+    ap.add_argument("-half", type=int, default=0, choices=[0, 1], help="1: -sloppy 2 iterates on 16-bit storage (option half), sharded or not")
     a = ap.parse_args()
     ranks = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -251,7 +255,7 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("gloo")
         ranks = (dist.get_world_size(), dist.get_rank(), dist)
-    hmc = Spv(a.lat, resident=not a.host_fields, halo=a.halo, start=a.start, ranks=ranks, sloppy=a.sloppy)
+    hmc = Spv(a.lat, resident=not a.host_fields, halo=a.halo, start=a.start, ranks=ranks, sloppy=a.sloppy, half=a.half)
     if hmc.rank != 0:
         sys.stdout = open(os.devnull, "w")            # one log, rank 0's (QEX: echo prints on rank 0)
     print(hmc.ctx.info(), "transport", hmc.ctx.comm_transport()[0])

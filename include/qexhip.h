@@ -233,8 +233,11 @@ int qexhip_stag_solve_prev(qexhip_handle h, double *x, const double *b, double m
  *                             same 16-bit solve for up to four systems in lock-step on one stream of the int16 links: every
  *                             system returns the bits of its single-system 16-bit solve, stall guard and fp32 finish included
  *                             (qexhip_stag_sloppy_last_batch).  With "half_batch" = 0 the batches run single for sloppy = 2;
- *                             multi-shift solves and t-sharded contexts (or ghost zones forced on one rank) run single for
- *                             sloppy = 2 whatever the options say
+ *                             multi-shift solves run single for sloppy = 2 whatever the options say.  t-sharded contexts (or
+ *                             ghost zones forced on one rank): the single-system 16-bit solve runs there as on one rank -- the
+ *                             faces travel in the 16-bit format, 16 B per site; the int16 links are scaled by the largest
+ *                             |entry| of the whole lattice; every rank takes the same updates, the same stall decision and the
+ *                             same fp32 finish --, the sloppy batches stay refused
  * The solve stops on the TRUE (fp64) residual: r2_over_b2 is |b - A x|^2/|b|^2 of the returned x (solveXX); iters counts fp32
  * iterations; nupdates (may be NULL) receives the number of reliable updates, the last one that confirmed convergence included
  * (0 for sloppy = 0).  iters == maxits is not an error.  QEXHIP_ERR_ARG for sloppy outside 0..2.
@@ -337,7 +340,8 @@ int qexhip_dev_op_xx_sloppy(qexhip_handle h, int r_id, int x_id, double m2, int 
  * the maximum over the ranks, and collective when the copy is rebuilt */
 int qexhip_stag_links_info_f32(qexhip_handle h, int *format, double *max_dev);
 /* the 16-bit counterpart of qexhip_dev_op_xx_sloppy: x[par] rounded to the 16-bit vector format, the two 16-bit sweeps (their
- * intermediate and result stored in the format), the result back in fp64.  One rank without ghost zones */
+ * intermediate and result stored in the format), the result back in fp64.  t-sharded: collective, each rank's slab of the one-rank
+ * result bit for bit */
 int qexhip_dev_op_xx_half(qexhip_handle h, int r_id, int x_id, double m2, int par_even);
 /* the batched form: n <= 4 fields x_ids[j][par] rounded to the format, ONE batched operator (two multi-right-hand-side 16-bit sweeps that
  * stream the links once for all systems) at m2[j], the results back in fp64 in r_ids[j][par]; per system the bits of qexhip_dev_op_xx_half */
@@ -345,7 +349,8 @@ int qexhip_dev_op_xx_half_batch(qexhip_handle h, int n, const int *r_ids, const 
 /* the 16-bit link copy (building it if stale, behind the fp32 copy whose format decision it shares): format 1 = rows 0,1 as int16
  * of u 32767 (clamped) + the fp32 copy's sign masks, 48 B per forward/backward pair; format 0 = 18 reals as int16 of u 32767 / s,
  * 72 B per pair, s = *s_fat for the one-hop links and *s_long for the Naik links: the largest |entry| of each kind (reported in
- * either format; 0 without Naik links).  max_dev as qexhip_stag_links_info_f32 */
+ * either format; 0 without Naik links).  max_dev as qexhip_stag_links_info_f32.  t-sharded: format, *s_fat and *s_long are those of
+ * the whole lattice (maxima over the ranks), and the call is collective when the copy is rebuilt */
 int qexhip_stag_links_info_half(qexhip_handle h, int *format, double *s_fat, double *s_long, double *max_dev);
 /* Re-entry of the CG on the state the last qexhip_dev_solve_xx (or re-entry) on x_id left behind -- CgState.solve called
  * again with b2 >= 0 (src/solvers/cg.nim:21-27,85,133,155-161,256-261): no set-up, r / p / rzold kept, the stopping
@@ -720,8 +725,8 @@ int qexhip_link_ortho_host(const double *links, int n, unsigned char *escaped, d
  *                  next set_links
  *   "sloppy_check" the sloppy solves post their (device-gated) reliable-update launches every this many fp32 iterations, and
  *                  at maxits (default 4; 1: in the iteration that calls for an update)
- *   "half"         1: sloppy = 2 (SloppyHalf) iterates on 16-bit storage in the single-system solves of a one-rank context;
- *                  0 (default): it runs single.  Other values are refused
+ *   "half"         1: sloppy = 2 (SloppyHalf) iterates on 16-bit storage in the single-system solves, on one rank and on t-sharded
+ *                  contexts (set it on every rank); 0 (default): it runs single.  Other values are refused
  *   "half_batch"   1: sloppy = 2 on the lock-step batched entries (the deflated batches included) iterates on 16-bit storage, up to
  *                  four systems per stream of the int16 links, on a one-rank context without ghost zones; 0 (default): those
  *                  batches run single.  Independent of "half".  Other values are refused

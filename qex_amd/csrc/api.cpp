@@ -750,7 +750,6 @@ extern "C" int qexhip_stag_sloppy_last_batch(qexhip_handle c, int n_max, int *n,
 }
 extern "C" int qexhip_stag_links_info_half(qexhip_handle c, int *format, double *s_fat, double *s_long, double *max_dev) {
   if (!c) return QEXHIP_ERR_ARG;
-  if (c->nranks > 1 || c->g.halo) { qexhip_set_error("the 16-bit links exist on one rank without ghost zones"); return QEXHIP_ERR_ARG; }
   HIPCHK(hipSetDevice(c->device));
   return half_links(c, format, s_fat, s_long, max_dev);
 }

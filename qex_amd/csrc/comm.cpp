@@ -244,23 +244,25 @@ static int emu_exchange(qexhip_ctx *c, hipStream_t st, size_t bytes) {
 static inline int upper(const qexhip_ctx *c) { return (c->rank + 1) % c->nranks; }
 static inline int lower(const qexhip_ctx *c) { return (c->rank - 1 + c->nranks) % c->nranks; }
 
-// Exchange the t-faces of one parity half of a field whose complex entries are `esz` bytes (16: DevField, 8: DevFieldF).  Runs on the
-// comm stream after ev_ready (the producer of the field on the compute stream); the caller joins (devjoin_signal / devjoin_wait) behind
+// Exchange the t-faces of one parity half of a field that stores a site in `site_bytes` bytes (48: DevField, 24: DevFieldF, 16: DevFieldH)
+// and whose ghost zones begin `ghost_off` bytes behind `base` (the body's ntile * 64 sites): a face is the contiguous byte range of
+// depth * F sites in all three layouts, and the emulated transport delay sees the true byte count.  Runs on the comm stream after ev_ready (the producer of the field on the compute stream); the caller joins (devjoin_signal / devjoin_wait) behind
 // whatever it posts after the exchange.  Message order is the same on every rank -- sends {bottom->lower, top->upper}, receives
 // {ghost_hi<-upper, ghost_lo<-lower} -- so that with two ranks (upper == lower) or one rank (self) the k-th send pairs with the k-th recv.
-static int halo_exchange(qexhip_ctx *c, char *base, size_t esz, int overlap, bool wait_ready) {
+static int halo_exchange(qexhip_ctx *c, char *base, size_t site_bytes, size_t ghost_off, int overlap, bool wait_ready) {
   // overlap == 0: post the exchange on the compute stream itself (no cross-stream events).  Used
   // when the interior sweep is too short to hide the exchange: two cross-stream dependencies
   // cost more than they buy there.
   CHK(need_comm(c));
   hipStream_t cs = overlap ? c->cstream : c->stream;
   const Geom &g = c->g;
-  const size_t bytes = (size_t)g.depth * g.F * 3 * esz;         // per face
-  const size_t nd = bytes / (esz / 2);                           // reals per face
-  const ncclDataType_t type = esz == 16 ? ncclDouble : ncclFloat;
+  const size_t bytes = (size_t)g.depth * g.F * site_bytes;       // per face
+  // RCCL's element: the field's own real type, or 32-bit words for the 16-bit sites (six int16 and an fp32 norm)
+  const ncclDataType_t type = site_bytes == 48 ? ncclDouble : (site_bytes == 24 ? ncclFloat : ncclUint32);
+  const size_t nd = bytes / (site_bytes == 48 ? 8 : 4);          // elements per face
   char *bottom = base;                                           // t = 0 .. depth-1
-  char *top = base + (size_t)g.ntile * 192 * esz - bytes;        // t = Xt-depth .. Xt-1
-  char *ghost_hi = base + (size_t)g.ntile * 192 * esz;
+  char *top = base + ghost_off - bytes;                          // t = Xt-depth .. Xt-1
+  char *ghost_hi = base + ghost_off;
   char *ghost_lo = ghost_hi + bytes;
   if (overlap && wait_ready) HIPCHK(hipStreamWaitEvent(c->cstream, c->ev_ready, 0));     // (not when the comm stream produced the faces itself)
   ScopedTimer tm(c, "exchange", cs);            // on the stream the group is posted on: transport + waiting for the neighbours
@@ -287,11 +289,16 @@ static int halo_exchange(qexhip_ctx *c, char *base, size_t esz, int overlap, boo
   return 0;
 }
 int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready) {
-  return halo_exchange(c, (char *)f.par(parity), sizeof(double2), overlap, wait_ready);
+  return halo_exchange(c, (char *)f.par(parity), 3 * sizeof(double2), (size_t)c->g.ntile * 192 * sizeof(double2), overlap, wait_ready);
 }
 // the fp32 fields of the mixed-precision CG (dslash_f32.hip): the same messages in the same order, half the bytes
 int comm_halo_exchange_f32(qexhip_ctx *c, DevFieldF &f, int parity, int overlap) {
-  return halo_exchange(c, (char *)f.par(parity), sizeof(float2), overlap, true);
+  return halo_exchange(c, (char *)f.par(parity), 3 * sizeof(float2), (size_t)c->g.ntile * 192 * sizeof(float2), overlap, true);
+}
+// the 16-bit fields of the SloppyHalf CG (dslash_half.hip): a site is one 16-byte element at its position, so the faces are the ranges
+// [0, depth F) and [Vh - depth F, Vh) of the parity half and the ghost zones follow the body (Vh = ntile * 64 on a halo context)
+int comm_halo_exchange_half(qexhip_ctx *c, DevFieldH &f, int parity, int overlap) {
+  return halo_exchange(c, (char *)f.par(parity), 16, (size_t)c->g.ntile * 64 * 16, overlap, true);
 }
 
 // Peer transport, the fused sweeps: the faces of one parity half of n fields (fused_sweep_setup: n = 1 for dslash_sweep, up to 4 for the lock-step batch) will be

@@ -570,7 +570,7 @@ int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const De
   HIPCHK(hipGetLastError());
   return 0;
 }
-// the close of an iteration whose update kernel is another file's (dslash_half.hip): one rank, nparts |r_s|^2 partials in r2p
+// the close of an iteration whose update kernel is another file's (dslash_half.hip): nparts rank-global |r_s|^2 partials in r2p
 int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts) {
   k_slp_close<<<1, 256, 0, c->stream>>>(s, r2p, nparts, SLP_DELTA * SLP_DELTA);
   HIPCHK(hipGetLastError());

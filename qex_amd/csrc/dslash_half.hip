@@ -1,12 +1,15 @@
 // dslash_half.hip -- 16-bit storage for the mixed-precision CG (SolverParams.sloppySolve = SloppyHalf with option "half" = 1;
 // QUDA's half precision behind qudaWrapperImpl.nim:197): a 16-bit copy of the operator's links, the Dslash sweep on 16-bit
 // vectors, and the BLAS kernels of the reliable-update CG whose host control is solve_xx_half_dev (solver.cpp).  Whole lattice on
-// one GPU, no ghost zones, one system.  Arithmetic is fp32 (dslash_f32_core.h); only what lies in HBM between kernels is 16-bit.
+// one GPU, or a t-sharded slab with ghost zones filled by the 16-bit face exchange (comm_halo_exchange_half); one system; no fused
+// (self-pushing) form.  Arithmetic is fp32 (dslash_f32_core.h); only what lies in HBM between kernels is 16-bit.
 //
 // Vectors: fixed point, not IEEE half.  One site is 16 bytes, six int16 (re, im of the three colours) and one fp32 norm = the
 // largest |component| of the site: q = rint(v 32767 / norm), v ~ q norm / 32767; a zero site (norm below FLT_MIN) is all zeros.
 // Per parity the field is [tile][64] such elements in the fp64 field's site order: element c of a parity is site c (vec_off's
-// tile and lane), a neighbour is one 16-byte load and a wavefront reads 1 KiB contiguously.  half_pack_host / half_unpack_host
+// tile and lane), a neighbour is one 16-byte load and a wavefront reads 1 KiB contiguously.  With g.halo the ghost zones follow
+// the body at the positions nbr_pos<true> gives them (DevFieldH), and a t-face is a contiguous element range: 16 B per site on the
+// wire, against 24 B in fp32 and 48 B in fp64, without a pack kernel.  The BLAS kernels run over the body only.  half_pack_host / half_unpack_host
 // restate the format on the host in double.
 //
 // Links: int16, q = rint(u 32767 / s), built on the device from the resident fp64 links (c->W) whenever c->links_gen has moved,
@@ -14,7 +17,8 @@
 // (forward link 2pr, backward link 2pr+1), one 32-bit word per complex entry (re low, im high):
 //   format 1 (48 B/pair): rows 0,1 of both links, s = 1, values clamped; [3][64] 16-byte elements per row, row 2 rebuilt in
 //             registers with the fp32 copy's sign masks;
-//   format 0 (72 B/pair): 18 reals of both links, s = the largest |entry| of the link kind (fat: pairs 0..3, long: pairs 4..7);
+//   format 0 (72 B/pair): 18 reals of both links, s = the largest |entry| of the link kind (fat: pairs 0..3, long: pairs 4..7) over
+//             the whole lattice (max-reduced over the ranks of a sharded one);
 //             a row is [4][64] 16-byte elements followed by [64] 8-byte elements (4608 B).
 // Every reduction (<p,Ap>, |r|^2) is formed from the values as stored and accumulates in double.
 #include "qexhip_internal.h"
@@ -166,6 +170,13 @@ int half_links(qexhip_ctx *c, int *fmt_out, double *s_fat, double *s_long, doubl
     HIPCHK(hipStreamSynchronize(c->stream));
     double s[2];
     memcpy(s, bits, sizeof s);
+    // t-sharded: format 0 divides by the largest |entry| of the WHOLE lattice, so that a slab's int16 links are the one-rank copy's.
+    // c->W holds the body tiles only (backward links arrive shifted and adjointed at set_links), so there are no ghost link tiles to
+    // exclude: a slab's rows are exactly the links its sites apply, and the ranks' slabs together are the lattice.  Reduced in
+    // format 1 as well (s = 1 there): links_info_half reports rank-global maxima.
+    // INVARIANT: this makes the lazily built copy a collective.  Every rank reaches it at the same call -- slph_begin, the operator
+    // probe, links_info_half -- behind the same (collective) writer of the links, as with f32_links above.
+    if (c->nranks > 1 && comm_ready(c)) CHK(comm_allreduce_max(c, s, 2));
     if (fmt == 1) {
       k_links_half<1><<<nblk, 256, 0, c->stream>>>(nrows, npair, c->W, S->W, 32767.0, 32767.0);
     } else {
@@ -183,8 +194,9 @@ int half_links(qexhip_ctx *c, int *fmt_out, double *s_fat, double *s_long, doubl
   return 0;
 }
 
+// etile = ntile without a halo (f32_field_ensure): the lock-step batch, which runs on such contexts only, sees the size it always saw
 int half_field_ensure(qexhip_ctx *c, DevFieldH &F) {
-  const size_t half = nsite_h(c);
+  const size_t half = (size_t)c->g.etile * 64;
   if (F.d && F.half != half) {
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipFree(F.d));
@@ -205,9 +217,15 @@ static int half_field(qexhip_ctx *c, int slot, DevFieldH **f) {
 }
 
 // ---- 16-bit Dslash sweep ------------------------------------------------------------------------------------------------
-// out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)]) as k_dslash_f32 without a halo: one lane per site, links streamed
+// out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)]) as k_dslash_f32: one lane per site, links streamed
 // non-temporally, fp32 FMAs on the integer link entries with one scale s norm_nbr / 32767^2 per hop on the neighbour's 3-vector,
 // the site normed, rounded and written with one 16-byte store; <xs,out> partials in double from the stored values.
+//   HALO = false  the whole lattice on one GPU (t-hops wrap)
+//   HALO = true   a t-sharded slab (or a one-rank context with a halo): t-hops that leave the slab read the ghost zones (nbr_pos<true>),
+//                 over the site range [c0,c1) plus [d0,d1) for workgroups >= nb1 (both faces in one launch), as k_dslash_f32<.., HALO, ..>.
+//                 Every site runs the operations of the HALO = false kernel in the same order -- the same hop order, one scale per hop on
+//                 the unpacked neighbour, pack_site on the result, the dot from the values as stored; only the positions its t-hops
+//                 read differ --, so a slab's output is the one-rank operator's bits site for site.
 struct DslashHalfArgs {
   Geom g;
   const void *W;                   // links of the output parity
@@ -220,13 +238,23 @@ struct DslashHalfArgs {
   double *partials;
   const int *done;
 };
+struct DslashHalfHaloArgs {        // (a type of its own: the HALO = false kernels keep their kernel arguments and code)
+  DslashHalfArgs a;
+  SweepRanges r;
+};
+template <bool HALO> struct HalfSweepArgs { using T = DslashHalfArgs; };
+template <> struct HalfSweepArgs<true> { using T = DslashHalfHaloArgs; };
+__device__ __forceinline__ const DslashHalfArgs &half_args(const DslashHalfArgs &P) { return P; }
+__device__ __forceinline__ const DslashHalfArgs &half_args(const DslashHalfHaloArgs &P) { return P.a; }
 
-template <int NDIR, bool INIT, bool DOT, int RECON>
-__global__ void __launch_bounds__(256) k_dslash_half(DslashHalfArgs A) {
+template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON>
+__global__ void __launch_bounds__(256) k_dslash_half(typename HalfSweepArgs<HALO>::T P) {
+  const DslashHalfArgs &A = half_args(P);
   if (A.done && *A.done) return;
   const Geom &g = A.g;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  const bool active = c < g.Vh;
+  int c = blockIdx.x * 256 + threadIdx.x, clim = g.Vh;
+  if constexpr (HALO) sweep_site(P.r, blockIdx.x, c, clim);
+  const bool active = c < clim;
   double dotv = 0;
   if (active) {
     const SiteXYZT s = site_coord(g, c, A.parity);
@@ -241,8 +269,8 @@ __global__ void __launch_bounds__(256) k_dslash_half(DslashHalfArgs A) {
     for (int pr = 0; pr < NDIR / 2; pr++) {
       const int mu = pr & 3;
       const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<false>(g, c, s, mu, hop);
-      const int pb = nbr_pos<false>(g, c, s, mu, -hop);
+      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
+      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
       const u4v hf = A.in[pf], hb = A.in[pb];
       float2 U[9], W[9], vf[3], vb[3];
       L.fetch(pr, U, W);
@@ -267,12 +295,42 @@ __global__ void __launch_bounds__(256) k_dslash_half(DslashHalfArgs A) {
   }
 }
 
-// one 16-bit sweep; *nparts <- how many <xs,out> partials it left in c->partials
+// one launch of the halo kernel over [c0,c1) (+ [d0,d1) behind it) on stream st, dot partials from A.partials + part_off
+static int launch_half_halo(qexhip_ctx *c, int fmt, const DslashHalfArgs &A, int c0, int c1, int d0, int d1, bool init, bool dot,
+                            int part_off, const char *tname, hipStream_t st) {
+  DslashHalfHaloArgs P;
+  memset(&P, 0, sizeof P);
+  const int nb = sweep_ranges(P.r, c0, c1, d0, d1);
+  if (!nb) return 0;
+  P.a = A;
+  P.a.partials = A.partials + part_off;
+  const dim3 grid(nb), block(256);
+  ScopedTimer tm(c, tname, st);
+#define QX_HH(ND, R)                                                                                      \
+  do {                                                                                                    \
+    if (init && dot) hipLaunchKernelGGL((k_dslash_half<ND, true, true, true, R>), grid, block, 0, st, P);    \
+    else if (init) hipLaunchKernelGGL((k_dslash_half<ND, true, true, false, R>), grid, block, 0, st, P);     \
+    else if (dot) hipLaunchKernelGGL((k_dslash_half<ND, true, false, true, R>), grid, block, 0, st, P);      \
+    else hipLaunchKernelGGL((k_dslash_half<ND, true, false, false, R>), grid, block, 0, st, P);              \
+  } while (0)
+  if (c->ndir == 8) { if (fmt == 1) QX_HH(8, 1); else QX_HH(8, 0); }
+  else { if (fmt == 1) QX_HH(16, 1); else QX_HH(16, 0); }
+#undef QX_HH
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// One 16-bit sweep; *nparts <- how many <xs,out> partials it left in c->partials.  With g.halo in sweep_f32's two forms, chosen by the
+// same sweep_plan: exchange-first (the 16-byte-per-site faces on the compute stream, one launch over all sites with the one-rank
+// workgroup partition) or split by sites (interior launch on the compute stream; exchange and both faces' launch on the comm stream;
+// device-side join).  There is no fused 16-bit kernel: where sweep_form picks the fused form, the 16-bit sweep is split by sites.
+// dot: the caller's next operation on the compute stream is comm_allreduce_parts (slph_iterate), which takes the join of a split sweep
+// with it where the mailboxes carry the sum.
 static int sweep_half(qexhip_ctx *c, DevFieldH &out, DevFieldH &in, int parity, const DevFieldH *xs, double cb, bool neg, bool dot,
                       const int *done, int *nparts) {
   const Geom &g = c->g;
   HalfState *S = hs_of(c);
-  if (S->fmt < 0 || g.halo) { qexhip_set_error("internal: 16-bit sweep without its links, or on a lattice with ghost zones"); return -3; }
+  if (S->fmt < 0) { qexhip_set_error("internal: 16-bit sweep without its links"); return -3; }
   DslashHalfArgs A;
   memset(&A, 0, sizeof A);
   A.g = g;
@@ -296,14 +354,36 @@ static int sweep_half(qexhip_ctx *c, DevFieldH &out, DevFieldH &in, int parity, 
   A.done = done;
   const bool init = cb != 0.0;
   c->bnd_out_on_cstream = nullptr;
+  if (g.halo) {
+    int lo_end, hi_beg, overlap;
+    sweep_plan(c, &lo_end, &hi_beg, &overlap);
+    CHK(devjoin_flush(c));
+    if (!overlap) {
+      CHK(comm_halo_exchange_half(c, in, 1 - parity, 0));
+      CHK(launch_half_halo(c, fmt, A, 0, g.Vh, 0, 0, init, dot, 0, "dslash_half", c->stream));
+      *nparts = (g.Vh + 255) / 256;
+    } else {
+      // split by sites (also where sweep_form(c, overlap) == 2: there is no fused 16-bit sweep)
+      const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
+      HIPCHK(hipEventRecord(c->ev_ready, c->stream));
+      CHK(comm_halo_exchange_half(c, in, 1 - parity, 1));
+      CHK(launch_half_halo(c, fmt, A, lo_end, hi_beg, 0, 0, init, dot, 0, "dslash_half", c->stream));
+      CHK(launch_half_halo(c, fmt, A, 0, lo_end, hi_beg, g.Vh, init, dot, nb_int, "dslash_half_bnd", c->cstream));
+      CHK(devjoin_signal(c, c->cstream));
+      if (dot && c->peer) CHK(devjoin_defer(c));
+      else CHK(devjoin_wait(c, c->stream, c->cstream));
+      *nparts = nb_int + nb_lo + nb_hi;
+    }
+    return 0;
+  }
   const dim3 grid((g.Vh + 255) / 256), block(256);
   ScopedTimer tm(c, "dslash_half", c->stream);
 #define QX_H(ND, R)                                                                                      \
   do {                                                                                                   \
-    if (init && dot) hipLaunchKernelGGL((k_dslash_half<ND, true, true, R>), grid, block, 0, c->stream, A);   \
-    else if (init) hipLaunchKernelGGL((k_dslash_half<ND, true, false, R>), grid, block, 0, c->stream, A);    \
-    else if (dot) hipLaunchKernelGGL((k_dslash_half<ND, false, true, R>), grid, block, 0, c->stream, A);     \
-    else hipLaunchKernelGGL((k_dslash_half<ND, false, false, R>), grid, block, 0, c->stream, A);             \
+    if (init && dot) hipLaunchKernelGGL((k_dslash_half<ND, false, true, true, R>), grid, block, 0, c->stream, A);   \
+    else if (init) hipLaunchKernelGGL((k_dslash_half<ND, false, true, false, R>), grid, block, 0, c->stream, A);    \
+    else if (dot) hipLaunchKernelGGL((k_dslash_half<ND, false, false, true, R>), grid, block, 0, c->stream, A);     \
+    else hipLaunchKernelGGL((k_dslash_half<ND, false, false, false, R>), grid, block, 0, c->stream, A);             \
   } while (0)
   if (c->ndir == 8) { if (fmt == 1) QX_H(8, 1); else QX_H(8, 0); }
   else { if (fmt == 1) QX_H(16, 1); else QX_H(16, 0); }
@@ -359,10 +439,9 @@ int half_to_f64(qexhip_ctx *c, double2 *y, const u4v *x) {
   return 0;
 }
 
-// fr[px] = the 16-bit operator on fx[px] rounded to 16 bits, back in fp64 (qexhip_dev_op_xx_half)
+// fr[px] = the 16-bit operator on fx[px] rounded to 16 bits, back in fp64 (qexhip_dev_op_xx_half); on a slab, the slab of it
 int half_op_xx_probe(qexhip_ctx *c, DevField &fr, const DevField &fx, double m2, int par_even) {
-  if (c->nranks > 1 || c->g.halo) { qexhip_set_error("the 16-bit operator runs on one rank without ghost zones"); return -1; }
-  CHK(half_links(c, nullptr, nullptr, nullptr, nullptr));
+  CHK(half_links(c, nullptr, nullptr, nullptr, nullptr));      // (sharded: collective, see half_links)
   DevFieldH *xi, *ro;
   CHK(half_field(c, HALF_IN, &xi));
   CHK(half_field(c, HALF_AP, &ro));
@@ -461,7 +540,11 @@ int slph_begin(qexhip_ctx *c, SlpScal *s) {
   HIPCHK(hipGetLastError());
   return 0;
 }
-// one 16-bit iteration: xpay, the two sweeps, the update and its close (k_slp_close: slp_close)
+// one 16-bit iteration: xpay, the two sweeps, the update and its close (k_slp_close: slp_close).  Sharded, the <p,Ap> partials are
+// summed over the ranks before k_slph_update and the |r_s|^2 partials before the close, exactly as slp_update does (its INVARIANT holds
+// here too: every rank sets the same `upd` / `done` / `stalled` at the same iteration -- k_slph_stall decides from the rank-global r2t
+// and the rank-global counters alone --, and solve_xx_half_dev checks the agreement at the end of every chunk).  One rank:
+// comm_allreduce_parts changes nothing, the bits are the one-rank solve's.
 int slph_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, const DevField &r, double m2, int par_even) {
   DevFieldH *rs, *ps, *aps;
   CHK(half_field(c, HALF_R, &rs));
@@ -475,18 +558,20 @@ int slph_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, const DevField &r, do
   int ndot = 0;
   CHK(half_op_xx(c, *aps, *ps, m2, par_even, 1, &s->done, &ndot));
   double *r2p = c->partials + c->part2_off;
+  if (ndot > 0) CHK(comm_allreduce_parts(c, c->partials, ndot, &ndot));
+  CHK(devjoin_flush(c));              // (no-op when the all-reduce has taken the second sweep's join with it)
   k_slph_update<<<nb, 256, 0, c->stream>>>(xs.par(par), rs->par(par), ps->par(par), aps->par(par), n, s, c->partials, ndot, r2p);
   HIPCHK(hipGetLastError());
-  return slp_close(c, s, r2p, nb);
+  int nr2 = nb;
+  CHK(comm_allreduce_parts(c, r2p, nb, &nr2));
+  return slp_close(c, s, r2p, nr2);
 }
 int slph_stall(qexhip_ctx *c, SlpScal *s, int limit) {
   k_slph_stall<<<1, 1, 0, c->stream>>>(hs_of(c)->stall, s, limit);
   HIPCHK(hipGetLastError());
   return 0;
 }
-int slph_stalled(qexhip_ctx *c, int *stalled) {     // after the stream was synchronised
-  HalfStall h;
-  HIPCHK(hipMemcpy(&h, hs_of(c)->stall, sizeof h, hipMemcpyDeviceToHost));
-  *stalled = h.stalled;
+int slph_stalled_async(qexhip_ctx *c, int *pinned) {     // the guard's flag -> pinned host memory, on the compute stream
+  HIPCHK(hipMemcpyAsync(pinned, &hs_of(c)->stall->stalled, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   return 0;
 }

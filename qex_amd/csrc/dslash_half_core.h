@@ -7,18 +7,11 @@
 #include "dslash_f32_core.h"
 #include <cfloat>
 
-typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 typedef unsigned int u2v __attribute__((ext_vector_type(2)));
 
 static constexpr float HQ = 32767.f;
 static constexpr float HQ_INV = 1.f / 32767.f;
 static constexpr int HALF_ROW0 = 4608;            // bytes of one format-0 pair row
-
-struct DevFieldH {   // 16-bit colour vector: u4v v[tile][64] per parity, body tiles only
-  u4v *d = nullptr;
-  size_t half = 0;   // elements per parity (= ntile*64)
-  u4v *par(int p) const { return d + (size_t)p * half; }
-};
 
 struct HalfStall {   // the stall guard's device state (k_slph_stall)
   double best;       // the smallest true |r|^2 seen

@@ -58,6 +58,16 @@ struct DevFieldF {  // fp32 colour vector of the mixed-precision CG: float2 v[ti
   float2 *par(int p) const { return d + (size_t)p * half; }
 };
 
+// 16-bit colour vector of the SloppyHalf CG (dslash_half.hip): one 16-byte element per site, u4v v[tile][64] per parity, the site at
+// position pos is element pos.  With g.halo the ghost zones continue the positions as nbr_pos<true> numbers them: ghost_hi at
+// [Vh, Vh + depth F), ghost_lo behind it (room for depth 3 each, as DevField); a t-face is a contiguous element range.
+typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+struct DevFieldH {
+  u4v *d = nullptr;
+  size_t half = 0;   // elements per parity (= etile*64: ntile*64 without a halo)
+  u4v *par(int p) const { return d + (size_t)p * half; }
+};
+
 struct DevCField {  // complex site field (trace.hip): double2 d[parity][ntile*64], site c of a parity at index c; no ghost slices
   double2 *d = nullptr;
   size_t half = 0;  // double2 elements per parity half (= ntile*64)
@@ -249,7 +259,7 @@ struct qexhip_ctx {
   int md_src1_stout = 0;                             // MD force source 1 is the stout chain's force (the closure that wrote last), else the nHYP closure's
   int opt_stout_check = 8;                           // option "stout_check": inverse iterations posted between two read-backs of the loop state
   void *half = nullptr;                              // HalfState (dslash_half.hip): 16-bit links + fields + stall guard of the SloppyHalf CG
-  int opt_half = 0;                                  // option "half": 1 = sloppy = 2 runs the 16-bit path (single-system solves on one rank)
+  int opt_half = 0;                                  // option "half": 1 = sloppy = 2 runs the 16-bit path (single-system solves, sharded or not)
   int opt_half_stall = 2;                            // option "half_stall": failed reliable updates in a row before the 16-bit solve finishes in fp32
   struct { int precision = 0, half_iters = 0, f32_iters = 0, fell_back = 0; } slp_last;   // the last sloppy solve (qexhip_stag_sloppy_last)
   void *batch_half = nullptr;                        // BatchHalfState (batch_half.hip): 16-bit fields, x_s, SlpScal[4] and stall guards of the 16-bit lock-step batch
@@ -351,6 +361,7 @@ int comm_halo_push_only_multi(qexhip_ctx *c, int n, DevField *const *f, int pari
 int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready = true);  // overlap: on cstream after ev_ready (wait_ready);
                                                                               // the caller joins behind what it posts next
 int comm_halo_exchange_f32(qexhip_ctx *c, DevFieldF &f, int parity, int overlap);  // the same for an fp32 field (half the bytes)
+int comm_halo_exchange_half(qexhip_ctx *c, DevFieldH &f, int parity, int overlap); // and for a 16-bit field (16 B per site, a third of fp64's)
 int comm_halo_exchange_multi(qexhip_ctx *c, int n, DevField *const *f, int parity, int overlap);   // n fields, one RCCL group
 int comm_allreduce(qexhip_ctx *c, double *dptr, int n);          // on stream
 int comm_allreduce_parts(qexhip_ctx *c, double *parts, int n, int *n_out);   // workgroup partials -> *n_out values whose sum is the rank-global dot product
@@ -435,18 +446,19 @@ int slp_xpay(qexhip_ctx *c, SlpScal *s, DevFieldF &p, DevFieldF &rs, const DevFi
 int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const DevFieldF &p, const DevFieldF &Ap, int parity, int ndot);
 int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity);
 int slp_resid(qexhip_ctx *c, SlpScal *s, DevField &r, const DevField &b, const DevField &Ax, int parity);
-int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts);     // k_slp_close alone (one rank)
+int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts);     // k_slp_close alone, on rank-global partials
 
-// ---- dslash_half.hip (16-bit storage for the sloppy CG: one rank, no ghost zones, one system) ----
+// ---- dslash_half.hip (16-bit storage for the sloppy CG: whole lattice or t-sharded slab, one system) ----
 enum { HALF_T = 0, HALF_R, HALF_P, HALF_AP, HALF_IN, HALF_NF };   // 16-bit work fields
 int half_pack_host(const double *v, size_t nsites, int16_t *q, float *norm);       // the vector format on the host
 int half_unpack_host(const int16_t *q, const float *norm, size_t nsites, double *v);
 int half_links(qexhip_ctx *c, int *fmt, double *s_fat, double *s_long, double *dev);   // the 16-bit copy of the links, rebuilt when links_gen moved
+                                                                                       // (sharded: collective; the values are rank-global)
 int half_op_xx_probe(qexhip_ctx *c, DevField &fr, const DevField &fx, double m2, int par_even);
 int slph_begin(qexhip_ctx *c, SlpScal *s);               // links + the stall guard's state, behind slp_init
 int slph_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, const DevField &r, double m2, int par_even);   // one 16-bit iteration
 int slph_stall(qexhip_ctx *c, SlpScal *s, int limit);    // behind a gated reliable update: the stall guard
-int slph_stalled(qexhip_ctx *c, int *stalled);           // (stream synchronised)
+int slph_stalled_async(qexhip_ctx *c, int *pinned);      // the guard's `stalled` flag -> pinned host memory, on the compute stream
 void half_state_free(qexhip_ctx *c);
 
 // ---- multishift_f32.hip: the fp32 iteration of the mixed-precision multi-shift CG ----
@@ -496,7 +508,7 @@ int solve_full_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double 
 int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                         int *iters, double *r2_over_b2, int *nupdates);
 // the 16-bit solve (option "half"), and the single-system sloppy solve of either storage: sloppy = 2 takes the 16-bit one where
-// the option is set and the context is one rank without ghost zones.  Both add what they ran to c->slp_last.
+// the option is set, on one rank and on t-sharded slabs alike.  Both add what they ran to c->slp_last.
 int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                       int *iters, double *r2_over_b2, int *nupdates);
 // the fp32 finish of a 16-bit solve whose stall guard tripped (single and batched): A e = r to r2stop / *r2t with solve_xx_sloppy_dev,

@@ -194,17 +194,18 @@ int solve_xx_continue_dev(qexhip_ctx *c, DevField &x, double r2req, int maxits, 
 // 137.9 vs 130.9 us per iteration for every 1st / 4th iteration, 222 vs 224 iterations.
 // Sharded: the state every rank just read back decides whether its host posts another chunk, so the ranks must hold the same bits
 // (slp_update: the reductions are rank-global, and so are the flags computed from them).  Checked here, with host operands, before
-// any rank acts on its copy: {r2t, -r2t, key, -key} max-reduced, max and min must coincide.
-static int slp_agree(qexhip_ctx *c, const SlpScal &h) {
+// any rank acts on its copy: {r2t, -r2t, key, -key} max-reduced, max and min must coincide.  stalled: the 16-bit solve's stall flag, which
+// decides on every rank whether the fp32 finish -- more collectives -- is entered.
+static int slp_agree(qexhip_ctx *c, const SlpScal &h, int stalled = 0) {
   if (c->nranks < 2 || !comm_ready(c)) return 0;
   CHK(peer_check(c));
-  const double key = ((double)h.k * 2.0 + h.done) * 65536.0 + (h.nupd & 0xffff);      // (exact in a double)
+  const double key = (((double)h.k * 2.0 + h.done) * 2.0 + (stalled != 0)) * 65536.0 + (h.nupd & 0xffff);      // (exact in a double)
   double v[4] = {h.r2t, -h.r2t, key, -key};
   CHK(comm_allreduce_max(c, v, 4));
   const bool both_nan = std::isnan(v[0]) && std::isnan(v[1]);
   if ((!both_nan && v[0] != -v[1]) || v[2] != -v[3]) {
-    qexhip_set_error("sharded sloppy solve: the ranks disagree on the true residual (%.17g .. %.17g) or on iterations / updates / stop "
-                     "(key %g .. %g)", -v[1], v[0], -v[3], v[2]);
+    qexhip_set_error("sharded sloppy solve: the ranks disagree on the true residual (%.17g .. %.17g) or on iterations / updates / stop / "
+                     "stall (key %g .. %g)", -v[1], v[0], -v[3], v[2]);
     return QEXHIP_ERR_COMM;
   }
   return 0;
@@ -268,11 +269,13 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
 // light mass cond(A) 2^-15 reaches 1 and the 16-bit recursion can stop improving the true residual; when opt_half_stall reliable
 // updates in a row have not lowered it (0: at the first update) the device ends the 16-bit iteration and the solve finishes in
 // fp32 -- A e = r with solve_xx_sloppy_dev to r2req |b|^2 / |r|^2, x += e, and the true residual recomputed once.  iters and
-// nupdates are the sums.  One rank without ghost zones (solve_xx_sloppy_any sends everything else to the fp32 solve).
+// nupdates are the sums.  Sharded: slph_iterate's reductions are rank-global and the stall guard decides from the rank-global true
+// residual, so every rank takes the same updates, the same stop and the same stall; the state read back at the end of a chunk, stall
+// flag included, is checked with slp_agree before any rank acts on it, and the decision to enter half_finish_f32 (itself sharded
+// through solve_xx_sloppy_dev) is taken from that agreed state alone: all ranks enter it or none does.
 int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                       int *iters, double *r2_over_b2, int *nupdates) {
   const int par = par_even ? 0 : 1;
-  if (c->nranks > 1 || c->g.halo) { qexhip_set_error("16-bit sloppy solve: one rank without ghost zones only"); return -1; }
   const double m2 = mass * mass;
   if (m2 == 0.0) { qexhip_set_error("sloppy solve: mass 0 unsupported (op_xx's <p,Ap> needs 4 m^2 > 0)"); return -1; }
   DevField *r, *Ax;
@@ -287,11 +290,20 @@ int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, doub
   CHK(blas_copy(c, *r, b, par));
   HIPCHK(hipMemsetAsync(xs->par(par), 0, xs->half * sizeof(float2), c->stream));
   CHK(slp_init(c, s, r2req, maxits));
-  CHK(slph_begin(c, s));
+  CHK(slph_begin(c, s));                         // (sharded: collective where the 16-bit links are rebuilt)
   SlpScal h;
-  HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  memcpy(&h, c->pinned, sizeof(SlpScal));
+  int stalled = 0;
+  int *const pstall = (int *)((char *)c->pinned + 256);     // (behind the SlpScal)
+  static_assert(sizeof(SlpScal) <= 256, "pinned scratch layout");
+  auto read_state = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
+    CHK(slph_stalled_async(c, pstall));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(&h, c->pinned, sizeof(SlpScal));
+    stalled = *pstall;
+    return 0;
+  };
+  CHK(read_state());
   const int every = std::max(1, c->opt_sloppy_check);
   const int chunk = 32;
   int k = 0;
@@ -306,13 +318,11 @@ int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, doub
         CHK(slph_stall(c, s, c->opt_half_stall));
       }
     }
-    HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(&h, c->pinned, sizeof(SlpScal));
+    CHK(read_state());
+    CHK(slp_agree(c, h, stalled));
   }
-  int its = h.k, nupd = h.nupd, stalled = 0, its32 = 0;
+  int its = h.k, nupd = h.nupd, its32 = 0;
   double r2t = h.r2t;
-  CHK(slph_stalled(c, &stalled));
   if (stalled && r2t > h.r2stop && its < maxits) {
     // (x holds every increment: the update that tripped the guard flushed x_s; r is its true residual)
     int nu32 = 0;
@@ -348,7 +358,7 @@ int half_finish_f32(qexhip_ctx *c, DevField &x, DevField &b, const DevField &r, 
 
 int solve_xx_sloppy_any(qexhip_ctx *c, int sloppy, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                         int *iters, double *r2_over_b2, int *nupdates) {
-  if (sloppy == 2 && c->opt_half && c->nranks == 1 && !c->g.halo)
+  if (sloppy == 2 && c->opt_half)
     return solve_xx_half_dev(c, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
   int its = 0;
   CHK(solve_xx_sloppy_dev(c, x, b, mass, r2req, maxits, par_even, &its, r2_over_b2, nupdates));

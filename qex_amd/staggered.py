@@ -23,7 +23,9 @@ from ._lib import check, lib
 
 EVEN, ODD, ALL = 0, 1, 2
 # SolverParams.sloppySolve (solverBase.nim:8-15): SloppyHalf runs single precision unless the context's option "half" is 1, which
-# gives the single-system solves of a one-rank context 16-bit storage (Context.set_option("half", 1); half_pack_host is the format)
+# gives the single-system solves 16-bit storage, on one rank and on t-sharded lattices alike (Context.set_option("half", 1);
+# half_pack_host is the format; sharded, the faces travel at 16 B per site).  Lock-step batches and multi-shift solves of a sharded
+# context stay as they were: refused, and single precision
 SloppyNone, SloppySingle, SloppyHalf = 0, 1, 2
 _SUBSET = {"even": EVEN, "odd": ODD, "all": ALL}
 
@@ -299,12 +301,14 @@ class Context:
 
     def dev_op_xx_half(self, r_id, x_id, m2, par_even=True):
         """r[par] = 4 m2 x - (2D)(2D) x with the 16-bit links, vectors and sweep of SloppyHalf under option "half" = 1 (x rounded to
-        the 16-bit format, the intermediate and the result stored in it, the result back to fp64)"""
+        the 16-bit format, the intermediate and the result stored in it, the result back to fp64).  On a t-sharded context: collective
+        (the faces are exchanged in the 16-bit format), and the slab of the one-rank operator's result, bit for bit"""
         check(lib().qexhip_dev_op_xx_half(self._h, int(r_id), int(x_id), float(m2), 1 if par_even else 0))
 
     def links_info_half(self):
         """(format, s_fat, s_long, max deviation) of the 16-bit link copy: format 0 = 18 reals scaled by the largest |entry| of the
-        link kind (s_fat, s_long), 1 = rows 0,1 + the fp32 copy's sign masks (scale 1)"""
+        link kind (s_fat, s_long), 1 = rows 0,1 + the fp32 copy's sign masks (scale 1).  On a t-sharded context every rank gets the
+        values of the whole lattice, and the call is collective where the copy has to be rebuilt"""
         f, sf, sl, dev = C.c_int(0), C.c_double(0), C.c_double(0), C.c_double(0)
         check(lib().qexhip_stag_links_info_half(self._h, C.byref(f), C.byref(sf), C.byref(sl), C.byref(dev)))
         return f.value, sf.value, sl.value, dev.value
