@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The numbers of DESIGN.md section 4 "16-bit batches" (sloppy = 2 on the batched entries with option "half_batch" = 1), measured in one
 session on one MI355X at 32^4 (unless -lat L L L L is given), next to that session's copy bandwidth and the two yardsticks whose code is
-older than the 16-bit batch: the fp32 batch (k_dslash_mrhs_f32) and the single-system 16-bit solve (k_dslash_half):
+older than the 16-bit batch: the fp32 batch (k_dslash_mrhs_lowp<StoreF32, ..>) and the single-system 16-bit solve (k_dslash_lowp<StoreHalf, ..>):
 
   wall     the box's copy bandwidth (k_copy16 of libqexhip_tune, 1 GiB); then, on g.random (8 links, format 1) and on HISQ fat + Naik
            links (16 links, format 0): the meson workload's four systems (point source at (0,0,0,2), colour 0, and its three
@@ -49,12 +49,12 @@ def stats(path, copy_gbs, vh):
     for r in csv.DictReader(open(path)):
         name = r["Name"]
         us = float(r["AverageNs"]) / 1e3
-        m = re.match(r".*k_dslash_mrhs_(half|f32)<(\d+), (\d), (true|false)>", name)
+        m = re.match(r".*k_dslash_mrhs_lowp<Store(Half|F32), (\d+), (\d), (true|false)>", name)
         if m:
-            kind, ndir, recon, n = m.group(1), int(m.group(2)), int(m.group(3)), 4
+            kind, ndir, recon, n = m.group(1).lower(), int(m.group(2)), int(m.group(3)), 4
             sweep = "second" if m.group(4) == "true" else "first"
         else:
-            m = re.match(r".*k_dslash_half<(\d+), (true|false), (true|false), (\d)>", name)
+            m = re.match(r".*k_dslash_lowp<StoreHalf, (\d+), (?:true|false), (true|false), (true|false), (\d)>", name)
             if not m:
                 if re.search(r"k_slphb_|k_slpb_|k_slph_|k_slph_stall", name):
                     rows.append(dict(kernel=name[:60], calls=int(r["Calls"]), us=round(us, 2)))

@@ -5,9 +5,8 @@
 //
 // The rule is batch.hip's: every system keeps its own state (SlpScal: sigma, alpha, beta, max|r_s|^2, upd / noupd / done, k, nupd) and
 // its arithmetic is, operation for operation, that of the single-system solve_xx_sloppy_dev (solver.cpp) -- the sweep is
-// k_dslash_f32<NDIR, false, INIT, DOT, RECON> per system (same hop order, same (sgn*cb)*xs start, same final *= sgn, same fma nesting
-// in the dot, same workgroup partition, same fixed-order final sums), the BLAS kernels are k_slp_* with the system in blockIdx.y and
-// the single-system grid per system, and the reliable update runs the fp64 op_xx per system behind that system's `noupd` word.  A
+// k_dslash_mrhs_lowp<StoreF32, ..> (dslash_lowp.h: the single-system body per system), the BLAS kernels are k_slp_* with the system
+// in blockIdx.y and the single-system grid per system, and the reliable update runs the fp64 op_xx per system behind that system's `noupd` word.  A
 // system solved in a batch returns the bits -- solution, iterations, true residual, updates -- it returns alone.
 //
 // One rank, no ghost zones: t-sharded contexts are refused (the fp32 faces of all systems in one exchange are not built).
@@ -15,100 +14,9 @@
 #include "site_index.h"
 #include "reduce.h"
 #include "cg_device.h"
-#include "dslash_f32_core.h"
+#include "dslash_lowp.h"
 #include <algorithm>
 #include <cstring>
-
-#define QX_MAXRHS 4
-
-struct MrhsF32Args {
-  Geom g;
-  const f4v *W;                    // fp32 links of the output parity: [tile][pair][NL][64] float4
-  const unsigned long long *S;     // RECON: sign masks [tile][dir]
-  const float2 *in[QX_MAXRHS];
-  float2 *out[QX_MAXRHS];
-  const float2 *xs[QX_MAXRHS];
-  float cb[QX_MAXRHS];
-  double *partials[QX_MAXRHS];
-  const SlpScal *st;               // st[j].done switches system j off
-  int parity, nrhs;
-};
-
-// SECOND = false: out_j = +sum_mu (U in_j(+mu) - U^+ in_j(-mu))              (k_dslash_f32<.., INIT = false, DOT = false, ..>, sgn = +1)
-// SECOND = true : out_j = cb_j xs_j - sum_mu (...), partial <xs_j, out_j>   (k_dslash_f32<.., INIT = true,  DOT = true,  ..>, sgn = -1)
-// one lane per site; each pair of links is loaded once and applied to every live system
-template <int NDIR, int RECON, bool SECOND>
-__global__ void __launch_bounds__(256) k_dslash_mrhs_f32(MrhsF32Args A) {
-  bool act[QX_MAXRHS];
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
-  if (!any) return;
-  const Geom &g = A.g;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  double dotv[QX_MAXRHS] = {0, 0, 0, 0};
-  if (c < g.Vh) {
-    const SiteXYZT s = site_coord(g, c, A.parity);
-    const LinkCursorF<NDIR, RECON> L(A.W, A.S, c);
-    const float sgn = SECOND ? -1.f : 1.f;
-    float2 acc[QX_MAXRHS][3], xsv[QX_MAXRHS][3];
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;
-      if (SECOND) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) xsv[j][k] = A.xs[j][vec_off(c, k)];
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-        acc[j][k] = SECOND ? make_float2((sgn * A.cb[j]) * xsv[j][k].x, (sgn * A.cb[j]) * xsv[j][k].y) : make_float2(0.f, 0.f);
-    }
-#pragma unroll 1
-    for (int pr = 0; pr < NDIR / 2; pr++) {
-      const int mu = pr & 3;
-      const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<false>(g, c, s, mu, hop);
-      const int pb = nbr_pos<false>(g, c, s, mu, -hop);
-      float2 U[9], W[9];
-      L.fetch(pr, U, W);
-#pragma unroll
-      for (int j = 0; j < QX_MAXRHS; j++) {
-        if (!act[j]) continue;
-        float2 vf[3], vb[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { vf[k] = A.in[j][vec_off(pf, k)]; vb[k] = A.in[j][vec_off(pb, k)]; }
-        mv3f<false>(acc[j], U, vf);
-        mv3f<true>(acc[j], W, vb);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        acc[j][k].x *= sgn; acc[j][k].y *= sgn;
-        A.out[j][vec_off(c, k)] = acc[j][k];
-      }
-      if (SECOND) {
-        // xs_j is read AGAIN here rather than kept: 4 x 3 float2 held across the hop loop put the kernel at 178-184 VGPRs (2 waves/SIMD);
-        // read twice it is at 130-136 (3 waves/SIMD), still without scratch.  The same values, so the same dot.
-#pragma unroll
-        for (int k = 0; k < 3; k++) xsv[j][k] = A.xs[j][vec_off(c, k)];
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-          dotv[j] = fma((double)xsv[j][k].x, (double)acc[j][k].x, fma((double)xsv[j][k].y, (double)acc[j][k].y, dotv[j]));
-      }
-    }
-  }
-  if (SECOND) {
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;             // uniform over the grid
-      const double r = block_sum_256(dotv[j]);
-      if (threadIdx.x == 0) A.partials[j][blockIdx.x] = r;
-    }
-  }
-}
 
 // ---- the reliable-update CG's BLAS and bookkeeping kernels (dslash_f32.hip: k_slp_*) for n systems: system = blockIdx.y, each with
 // the single-system kernel's grid in x, so the workgroup partials group as they do there ----
@@ -283,20 +191,6 @@ int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass) {
   return 0;
 }
 
-template <int NDIR, int RECON>
-static void launch_mrhs_f32(const MrhsF32Args &A, bool second, int nb, hipStream_t st) {
-  if (second) hipLaunchKernelGGL((k_dslash_mrhs_f32<NDIR, RECON, true>), dim3(nb), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL((k_dslash_mrhs_f32<NDIR, RECON, false>), dim3(nb), dim3(256), 0, st, A);
-}
-static int sweep_mrhs_f32(qexhip_ctx *c, const MrhsF32Args &A, int fmt, bool second) {
-  const int nb = (c->g.Vh + 255) / 256;
-  ScopedTimer tm(c, "dslash_batch_f32", c->stream);
-  if (c->ndir == 8) { if (fmt == 1) launch_mrhs_f32<8, 1>(A, second, nb, c->stream); else launch_mrhs_f32<8, 0>(A, second, nb, c->stream); }
-  else { if (fmt == 1) launch_mrhs_f32<16, 1>(A, second, nb, c->stream); else launch_mrhs_f32<16, 0>(A, second, nb, c->stream); }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // n (1..4) mixed-precision solveXX's in lock-step: solve_xx_batch_dev's semantics (own mass, r2req, iteration count; shared maxits),
 // solve_xx_sloppy_dev's iteration per system.  iters: fp32 iterations; r2_over_b2: the TRUE residual; nupdates: reliable updates.
 int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
@@ -321,7 +215,7 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
   DevField *w64[2 * QX_MAXRHS];
   CHK(batch_work_fields(c, 2 * QX_MAXRHS, w64));                             // r, A x per system
   const int par = par_even ? 0 : 1;
-  MrhsF32Args A1, A2;
+  MrhsArgs<StoreF32> A1, A2;
   SlpBatch L;
   memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2); memset(&L, 0, sizeof L);
   double m2[QX_MAXRHS];
@@ -347,13 +241,7 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
     L.dotp[j] = S->partials + per * j; L.r2p[j] = S->partials + per * j + nbd;
   }
   L.s = S->s;
-  for (MrhsF32Args *A : {&A1, &A2}) {
-    const int parity = (A == &A1) ? 1 - par : par;
-    A->g = g; A->st = S->s; A->nrhs = n; A->parity = parity;
-    const void *Wv = nullptr;
-    CHK(f32_links_dev(c, parity, &Wv, &A->S, &fmt));
-    A->W = (const f4v *)Wv;
-  }
+  CHK(mrhs_links(c, n, par, S->s, A1, A2, &fmt));
   SlpScal h[QX_MAXRHS];
   auto read_states = [&]() -> int {
     HIPCHK(hipMemcpyAsync(c->pinned, S->s, sizeof(SlpScal) * n, hipMemcpyDeviceToHost, c->stream));
@@ -372,8 +260,8 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
         ScopedTimer tm(c, "blas", c->stream);
         k_slpb_xpay<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
       }
-      CHK(sweep_mrhs_f32(c, A1, fmt, false));
-      CHK(sweep_mrhs_f32(c, A2, fmt, true));
+      CHK(sweep_mrhs(c, A1, fmt, false));
+      CHK(sweep_mrhs(c, A2, fmt, true));
       {
         ScopedTimer tm(c, "blas", c->stream);
         k_slpb_update<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec, nbd);

@@ -4,11 +4,9 @@
 // conn4d.nim:52) and its GPU backend makes that 16-bit storage (qudaWrapperImpl.nim:197).
 //
 // The rule is batch_f32.hip's: every system keeps its own state (SlpScal, HalfStall) and its arithmetic is, operation for operation,
-// that of the single-system solve_xx_half_dev -- the sweep is k_dslash_half<NDIR, INIT, DOT, RECON> per system (same hop order, one
-// scale s norm_nbr / 32767^2 per hop on the unpacked neighbour, mv3f<false> then mv3f<true>, *= sgn, pack_site, the dot from the
-// unrounded acc against the unpacked xs, same fma nesting, same 256-lane workgroup partition, same fixed-order final sums), the BLAS
-// kernels are k_slph_* with the system in blockIdx.y on the single-system grid, the bookkeeping and the reliable update are the fp32
-// batch's (k_slpb_*, the gated fp64 op_xx per system), and the stall guard runs per system.  A system solved here returns the bits --
+// that of the single-system solve_xx_half_dev -- the sweep is k_dslash_mrhs_lowp<StoreHalf, ..> (dslash_lowp.h: the single-system
+// body per system), the BLAS kernels are k_slph_* with the system in blockIdx.y on the single-system grid, the bookkeeping and the
+// reliable update are the fp32 batch's (k_slpb_*, the gated fp64 op_xx per system), and the stall guard runs per system.  A system solved here returns the bits --
 // solution, iterations, true residual, updates, fall-back -- it returns from solve_xx_half_dev alone.
 //
 // One rank, no ghost zones.
@@ -16,107 +14,9 @@
 #include "site_index.h"
 #include "reduce.h"
 #include "cg_device.h"
-#include "dslash_half_core.h"
+#include "dslash_lowp.h"
 #include <algorithm>
 #include <cstring>
-
-struct MrhsHalfArgs {
-  Geom g;
-  const void *W;                   // int16 links of the output parity
-  const unsigned long long *S;     // RECON: the fp32 copy's sign masks [tile][dir]
-  const u4v *in[QX_MAXRHS];
-  u4v *out[QX_MAXRHS];
-  const u4v *xs[QX_MAXRHS];
-  float cb[QX_MAXRHS];
-  double *partials[QX_MAXRHS];
-  const SlpScal *st;               // st[j].done switches system j off
-  float s_fat, s_long;
-  int parity, nrhs;
-};
-
-// SECOND = false: out_j = +sum_mu (U in_j(+mu) - U^+ in_j(-mu))              (k_dslash_half<.., INIT = false, DOT = false, ..>, sgn = +1)
-// SECOND = true : out_j = cb_j xs_j - sum_mu (...), partial <xs_j, out_j>   (k_dslash_half<.., INIT = true,  DOT = true,  ..>, sgn = -1)
-// one lane per site; each pair of links is fetched once and applied to every live system.  The eight 16-byte neighbour loads of a hop
-// pair are issued ahead of the link fetch.
-template <int NDIR, int RECON, bool SECOND>
-__global__ void __launch_bounds__(256) k_dslash_mrhs_half(MrhsHalfArgs A) {
-  bool act[QX_MAXRHS];
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
-  if (!any) return;
-  const Geom &g = A.g;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  double dotv[QX_MAXRHS] = {0, 0, 0, 0};
-  if (c < g.Vh) {
-    const SiteXYZT s = site_coord(g, c, A.parity);
-    const LinkCursorH<NDIR, RECON> L(A.W, A.S, c);
-    const float sgn = SECOND ? -1.f : 1.f;
-    float2 acc[QX_MAXRHS][3];
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;
-      if (SECOND) {
-        float2 xsv[3];
-        unpack_site(A.xs[j][c], xsv, HQ_INV);
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[j][k] = make_float2((sgn * A.cb[j]) * xsv[k].x, (sgn * A.cb[j]) * xsv[k].y);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[j][k] = make_float2(0.f, 0.f);
-      }
-    }
-    const float qf = (RECON == 1 ? 1.f : A.s_fat) * (HQ_INV * HQ_INV), ql = (RECON == 1 ? 1.f : A.s_long) * (HQ_INV * HQ_INV);
-#pragma unroll 1
-    for (int pr = 0; pr < NDIR / 2; pr++) {
-      const int mu = pr & 3;
-      const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<false>(g, c, s, mu, hop);
-      const int pb = nbr_pos<false>(g, c, s, mu, -hop);
-      u4v hf[QX_MAXRHS], hb[QX_MAXRHS];
-#pragma unroll
-      for (int j = 0; j < QX_MAXRHS; j++) {
-        if (!act[j]) continue;
-        hf[j] = A.in[j][pf]; hb[j] = A.in[j][pb];
-      }
-      float2 U[9], W[9];
-      L.fetch(pr, U, W);
-      const float sc = pr >= 4 ? ql : qf;
-#pragma unroll
-      for (int j = 0; j < QX_MAXRHS; j++) {
-        if (!act[j]) continue;
-        float2 vf[3], vb[3];
-        unpack_site(hf[j], vf, sc);
-        unpack_site(hb[j], vb, sc);
-        mv3f<false>(acc[j], U, vf);
-        mv3f<true>(acc[j], W, vb);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;
-#pragma unroll
-      for (int k = 0; k < 3; k++) { acc[j][k].x *= sgn; acc[j][k].y *= sgn; }
-      A.out[j][c] = pack_site(acc[j]);
-      if (SECOND) {
-        // xs_j is read AGAIN here rather than kept across the hop loop (k_dslash_mrhs_f32 does the same): the same values, so the same dot
-        float2 xsv[3];
-        unpack_site(A.xs[j][c], xsv, HQ_INV);
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-          dotv[j] = fma((double)xsv[k].x, (double)acc[j][k].x, fma((double)xsv[k].y, (double)acc[j][k].y, dotv[j]));
-      }
-    }
-  }
-  if (SECOND) {
-#pragma unroll
-    for (int j = 0; j < QX_MAXRHS; j++) {
-      if (!act[j]) continue;             // uniform over the grid
-      const double r = block_sum_256(dotv[j]);
-      if (threadIdx.x == 0) A.partials[j][blockIdx.x] = r;
-    }
-  }
-}
 
 // ---- k_slph_xpay / k_slph_update (dslash_half.hip) for n systems: system = blockIdx.y, each with the single-system grid (grid_sites)
 // in x, so the |r_s|^2 partials group as they do alone ----
@@ -259,44 +159,6 @@ static int bh_state(qexhip_ctx *c, int n, size_t per, BatchHalfState **out) {
   return 0;
 }
 
-// the link bases, masks and scales of both sweeps of op_xx on parity px (A1: the other parity's links, A2: px's)
-static int mrhs_half_args(qexhip_ctx *c, int n, int px, SlpScal *st, MrhsHalfArgs &A1, MrhsHalfArgs &A2) {
-  const Geom &g = c->g;
-  HalfState *H = half_state(c);
-  if (H->fmt < 0 || g.halo) { qexhip_set_error("internal: 16-bit batch without its links, or on a lattice with ghost zones"); return -3; }
-  for (MrhsHalfArgs *A : {&A1, &A2}) {
-    const int parity = (A == &A1) ? 1 - px : px;
-    A->g = g; A->st = st; A->nrhs = n; A->parity = parity;
-    const size_t rows = (size_t)parity * g.ntile * (c->ndir / 2);          // pair rows before this parity
-    A->W = (const char *)H->W + rows * (H->fmt == 1 ? 3 * 64 * 16 : HALF_ROW0);
-    A->S = nullptr;
-    if (H->fmt == 1) {
-      const void *Wf = nullptr;
-      int f32fmt = 0;
-      CHK(f32_links_dev(c, parity, &Wf, &A->S, &f32fmt));
-      if (f32fmt != 1 || !A->S) { qexhip_set_error("internal: the 16-bit links' sign masks are gone"); return -3; }
-    }
-    A->s_fat = (float)H->s_fat; A->s_long = (float)H->s_long;
-  }
-  return 0;
-}
-
-template <int NDIR, int RECON>
-static void launch_mrhs_half(const MrhsHalfArgs &A, bool second, int nb, hipStream_t st) {
-  if (second) hipLaunchKernelGGL((k_dslash_mrhs_half<NDIR, RECON, true>), dim3(nb), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL((k_dslash_mrhs_half<NDIR, RECON, false>), dim3(nb), dim3(256), 0, st, A);
-}
-static int sweep_mrhs_half(qexhip_ctx *c, const MrhsHalfArgs &A, bool second) {
-  const int nb = (c->g.Vh + 255) / 256;
-  const int fmt = half_state(c)->fmt;
-  c->bnd_out_on_cstream = nullptr;
-  ScopedTimer tm(c, "dslash_batch_half", c->stream);
-  if (c->ndir == 8) { if (fmt == 1) launch_mrhs_half<8, 1>(A, second, nb, c->stream); else launch_mrhs_half<8, 0>(A, second, nb, c->stream); }
-  else { if (fmt == 1) launch_mrhs_half<16, 1>(A, second, nb, c->stream); else launch_mrhs_half<16, 0>(A, second, nb, c->stream); }
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // n (1..4) 16-bit solveXX's in lock-step: solve_xx_batch_sloppy_dev's loop (chunks of 32, one read of the n states per chunk, updates
 // posted every opt_sloppy_check-th iteration and at maxits; shared maxits), solve_xx_half_dev's start, iteration, stall guard and fp32
 // finish per system.  iters: 16-bit + fp32 iterations; r2_over_b2: the TRUE residual; nupdates: reliable updates.
@@ -315,7 +177,7 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
   DevField *w64[2 * QX_MAXRHS];
   CHK(batch_work_fields(c, 2 * QX_MAXRHS, w64));                             // r, A x per system
   const int par = par_even ? 0 : 1;
-  MrhsHalfArgs A1, A2;
+  MrhsArgs<StoreHalf> A1, A2;
   SlphBatch H;
   SlpBatch L;
   memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2); memset(&H, 0, sizeof H); memset(&L, 0, sizeof L);
@@ -346,7 +208,8 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
   H.s = S->s; L.s = S->s;
   k_slphb_stall_init<<<1, 64, 0, c->stream>>>(S->stall, S->s, n);
   HIPCHK(hipGetLastError());
-  CHK(mrhs_half_args(c, n, par, S->s, A1, A2));
+  int fmt = 0;
+  CHK(mrhs_links(c, n, par, S->s, A1, A2, &fmt));
   SlpScal h[QX_MAXRHS];
   auto read_states = [&]() -> int {
     HIPCHK(hipMemcpyAsync(c->pinned, S->s, sizeof(SlpScal) * n, hipMemcpyDeviceToHost, c->stream));
@@ -365,8 +228,8 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
         ScopedTimer tm(c, "blas", c->stream);
         k_slphb_xpay<<<dim3(nbh, n), 256, 0, c->stream>>>(H, nsites);
       }
-      CHK(sweep_mrhs_half(c, A1, false));
-      CHK(sweep_mrhs_half(c, A2, true));
+      CHK(sweep_mrhs(c, A1, fmt, false));
+      CHK(sweep_mrhs(c, A2, fmt, true));
       {
         ScopedTimer tm(c, "blas", c->stream);
         k_slphb_update<<<dim3(nbh, n), 256, 0, c->stream>>>(H, nsites, nbd);
@@ -443,7 +306,7 @@ int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, c
   CHK(bh_state(c, n, per, &S));
   HIPCHK(hipMemsetAsync(S->s, 0, sizeof(SlpScal) * QX_MAXRHS, c->stream));       // every system live
   const int px = par_even ? 0 : 1;
-  MrhsHalfArgs A1, A2;
+  MrhsArgs<StoreHalf> A1, A2;
   memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2);
   for (int j = 0; j < n; j++) {
     DevFieldH *const fj = &S->f[BH_N * j];
@@ -453,9 +316,10 @@ int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, c
     A2.cb[j] = (float)(4.0 * m2[j]);
     A2.partials[j] = S->partials + per * j;
   }
-  CHK(mrhs_half_args(c, n, px, S->s, A1, A2));
-  CHK(sweep_mrhs_half(c, A1, false));
-  CHK(sweep_mrhs_half(c, A2, true));
+  int fmt = 0;
+  CHK(mrhs_links(c, n, px, S->s, A1, A2, &fmt));
+  CHK(sweep_mrhs(c, A1, fmt, false));
+  CHK(sweep_mrhs(c, A2, fmt, true));
   for (int j = 0; j < n; j++) CHK(half_to_f64(c, fr[j]->par(px), S->f[BH_N * j + BH_AP].par(px)));
   return 0;
 }

@@ -291,14 +291,11 @@ static int halo_exchange(qexhip_ctx *c, char *base, size_t site_bytes, size_t gh
 int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready) {
   return halo_exchange(c, (char *)f.par(parity), 3 * sizeof(double2), (size_t)c->g.ntile * 192 * sizeof(double2), overlap, wait_ready);
 }
-// the fp32 fields of the mixed-precision CG (dslash_f32.hip): the same messages in the same order, half the bytes
-int comm_halo_exchange_f32(qexhip_ctx *c, DevFieldF &f, int parity, int overlap) {
-  return halo_exchange(c, (char *)f.par(parity), 3 * sizeof(float2), (size_t)c->g.ntile * 192 * sizeof(float2), overlap, true);
-}
-// the 16-bit fields of the SloppyHalf CG (dslash_half.hip): a site is one 16-byte element at its position, so the faces are the ranges
-// [0, depth F) and [Vh - depth F, Vh) of the parity half and the ghost zones follow the body (Vh = ntile * 64 on a halo context)
-int comm_halo_exchange_half(qexhip_ctx *c, DevFieldH &f, int parity, int overlap) {
-  return halo_exchange(c, (char *)f.par(parity), 16, (size_t)c->g.ntile * 64 * 16, overlap, true);
+// the reduced-precision fields of the mixed-precision CGs (dslash_lowp.h), one parity half at `half`: the same messages in the same order
+// at site_bytes = 24 (DevFieldF) or 16 (DevFieldH: a site is one 16-byte element at its position, so the faces are the ranges
+// [0, depth F) and [Vh - depth F, Vh) of the half); in both the ghost zones follow the body's ntile * 64 sites
+int comm_halo_exchange_sites(qexhip_ctx *c, void *half, size_t site_bytes, int overlap) {
+  return halo_exchange(c, (char *)half, site_bytes, (size_t)c->g.ntile * 64 * site_bytes, overlap, true);
 }
 
 // Peer transport, the fused sweeps: the faces of one parity half of n fields (fused_sweep_setup: n = 1 for dslash_sweep, up to 4 for the lock-step batch) will be

@@ -1,7 +1,7 @@
 // dslash_f32.hip -- the single-precision side of the mixed-precision CG (SolverParams.sloppySolve, solverBase.nim:8-15):
 // an fp32 copy of the operator's links, the fp32 Dslash sweep, and the fp32 BLAS / bookkeeping kernels of the reliable-update
 // CG whose host control is solve_xx_sloppy_dev (solver.cpp).  Whole lattice on one GPU, or a t-sharded slab with ghost zones (the
-// fp64 DevField's layout) filled by the fp32 face exchange (comm_halo_exchange_f32); no fused (self-pushing) form.
+// fp64 DevField's layout) filled by the fp32 face exchange; the sweep itself is dslash_lowp.h's, in fp32 storage.
 //
 // Links: built on the device from the resident fp64 links (c->W: BCs, staggered phases and Naik links already applied), lazily,
 // whenever c->links_gen has moved since the last build (every writer of W ends in links_compress, which bumps it).  Per parity
@@ -18,7 +18,7 @@
 #include "site_index.h"
 #include "reduce.h"
 #include "cg_device.h"
-#include "dslash_f32_core.h"
+#include "dslash_lowp.h"
 #include <cstring>
 #include <cmath>
 
@@ -198,184 +198,13 @@ int f32_field(qexhip_ctx *c, int slot, DevFieldF **f) {
 }
 
 // ---- fp32 Dslash sweep --------------------------------------------------------------------------------------------
-// out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)])  (k_dslash's arithmetic with ca = 0, post = 1): one lane per site, 64-site
-// tiles, links streamed non-temporally with 16-byte loads, fp32 FMAs, <xs,out> partials in double.
-//   HALO = false  the whole lattice on one GPU (t-hops wrap)
-//   HALO = true   a t-sharded slab (or a one-rank context with a halo): t-hops that leave the slab read the ghost zones (nbr_pos<true>),
-//                 over the site range [c0,c1) plus [d0,d1) for workgroups >= nb1 (both faces in one launch), as k_dslash<.., HALO, ..>.
-//                 Every site runs the operations of the HALO = false kernel in the same order -- only the positions its t-hops read
-//                 differ --, so a sharded fp32 operator gives the one-rank operator's bits site for site.
-struct DslashF32Args {
-  Geom g;
-  const f4v *W;                    // links of the output parity
-  const unsigned long long *S;     // RECON: sign masks [tile][dir]
-  const float2 *in;
-  float2 *out;
-  const float2 *xs;
-  float cb, sgn;
-  int parity;
-  double *partials;
-  const int *done;
-};
-struct DslashF32HaloArgs {         // (a type of its own: the HALO = false kernels keep their kernel arguments and code)
-  DslashF32Args a;
-  SweepRanges r;
-};
-template <bool HALO> struct F32SweepArgs { using T = DslashF32Args; };
-template <> struct F32SweepArgs<true> { using T = DslashF32HaloArgs; };
-__device__ __forceinline__ const DslashF32Args &f32_args(const DslashF32Args &P) { return P; }
-__device__ __forceinline__ const DslashF32Args &f32_args(const DslashF32HaloArgs &P) { return P.a; }
-
-template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON>
-__global__ void __launch_bounds__(256) k_dslash_f32(typename F32SweepArgs<HALO>::T P) {
-  const DslashF32Args &A = f32_args(P);
-  if (A.done && *A.done) return;
-  const Geom &g = A.g;
-  int c = blockIdx.x * 256 + threadIdx.x, clim = g.Vh;
-  if constexpr (HALO) sweep_site(P.r, blockIdx.x, c, clim);
-  const bool active = c < clim;
-  double dotv = 0;
-  if (active) {
-    const SiteXYZT s = site_coord(g, c, A.parity);
-    const LinkCursorF<NDIR, RECON> L(A.W, A.S, c);
-    float2 acc[3], xsv[3];
-    if (INIT || DOT) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) xsv[k] = A.xs[vec_off(c, k)];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) acc[k] = INIT ? make_float2((A.sgn * A.cb) * xsv[k].x, (A.sgn * A.cb) * xsv[k].y) : make_float2(0.f, 0.f);
-    constexpr int UNR = NDIR == 8 ? 4 : 2;
-#pragma unroll UNR
-    for (int pr = 0; pr < NDIR / 2; pr++) {
-      const int mu = pr & 3;
-      const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
-      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
-      float2 U[9], W[9], vf[3], vb[3];
-      L.fetch(pr, U, W);
-#pragma unroll
-      for (int k = 0; k < 3; k++) { vf[k] = A.in[vec_off(pf, k)]; vb[k] = A.in[vec_off(pb, k)]; }
-      mv3f<false>(acc, U, vf);
-      mv3f<true>(acc, W, vb);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      acc[k].x *= A.sgn; acc[k].y *= A.sgn;
-      A.out[vec_off(c, k)] = acc[k];
-    }
-    if (DOT) {
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-        dotv = fma((double)xsv[k].x, (double)acc[k].x, fma((double)xsv[k].y, (double)acc[k].y, dotv));
-    }
-  }
-  if (DOT) {
-    const double r = block_sum_256(dotv);
-    if (threadIdx.x == 0) A.partials[blockIdx.x] = r;
-  }
-}
-
-// one launch of the halo kernel over [c0,c1) (+ [d0,d1) behind it) on stream st, dot partials from A.partials + part_off
-static int launch_f32_halo(qexhip_ctx *c, int fmt, const DslashF32Args &A, int c0, int c1, int d0, int d1, bool init, bool dot,
-                           int part_off, const char *tname, hipStream_t st) {
-  DslashF32HaloArgs P;
-  memset(&P, 0, sizeof P);
-  const int nb = sweep_ranges(P.r, c0, c1, d0, d1);
-  if (!nb) return 0;
-  P.a = A;
-  P.a.partials = A.partials + part_off;
-  const dim3 grid(nb), block(256);
-  ScopedTimer tm(c, tname, st);
-#define QX_F32H(ND, R)                                                                                       \
-  do {                                                                                                       \
-    if (init && dot) hipLaunchKernelGGL((k_dslash_f32<ND, true, true, true, R>), grid, block, 0, st, P);    \
-    else if (init) hipLaunchKernelGGL((k_dslash_f32<ND, true, true, false, R>), grid, block, 0, st, P);     \
-    else if (dot) hipLaunchKernelGGL((k_dslash_f32<ND, true, false, true, R>), grid, block, 0, st, P);      \
-    else hipLaunchKernelGGL((k_dslash_f32<ND, true, false, false, R>), grid, block, 0, st, P);              \
-  } while (0)
-  if (c->ndir == 8) { if (fmt == 1) QX_F32H(8, 1); else QX_F32H(8, 0); }
-  else { if (fmt == 1) QX_F32H(16, 1); else QX_F32H(16, 0); }
-#undef QX_F32H
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// One fp32 sweep; *nparts <- how many <xs,out> partials it left in c->partials.  With g.halo, in the forms the fp64 sweep chooses
-// between (sweep_plan / sweep_form): exchange-first (the fp32 faces on the compute stream, one launch over all sites) or split by
-// sites (exchange + both faces' launch on the comm stream, interior launch on the compute stream, device-side join).  The fused form
-// has no fp32 kernel: where sweep_form picks it, the fp32 sweep is split by sites.  dot: the caller's next operation on the compute
-// stream is comm_allreduce_parts (slp_update), which takes the join of a split sweep with it where the mailboxes carry the sum.
-static int sweep_f32(qexhip_ctx *c, DevFieldF &out, DevFieldF &in, int parity, const DevFieldF *xs, double cb, bool neg,
-                     bool dot, const int *done, int *nparts) {
-  const Geom &g = c->g;
-  DslashF32Args A;
-  memset(&A, 0, sizeof A);
-  A.g = g;
-  int fmt = 0;
-  const void *Wv = nullptr;
-  CHK(f32_links_dev(c, parity, &Wv, &A.S, &fmt));
-  A.W = (const f4v *)Wv;
-  A.in = in.par(1 - parity);
-  A.out = out.par(parity);
-  A.xs = xs ? xs->par(parity) : nullptr;
-  A.cb = (float)cb;
-  A.sgn = neg ? -1.f : 1.f;
-  A.parity = parity;
-  A.partials = c->partials;
-  A.done = done;
-  const bool init = cb != 0.0;
-  c->bnd_out_on_cstream = nullptr;        // (the fp64 sweep's early-exchange shortcut is for a pair of fp64 sweeps only)
-  if (g.halo) {
-    int lo_end, hi_beg, overlap;
-    sweep_plan(c, &lo_end, &hi_beg, &overlap);
-    CHK(devjoin_flush(c));
-    if (!overlap) {
-      CHK(comm_halo_exchange_f32(c, in, 1 - parity, 0));
-      CHK(launch_f32_halo(c, fmt, A, 0, g.Vh, 0, 0, init, dot, 0, "dslash_f32", c->stream));
-      *nparts = (g.Vh + 255) / 256;
-    } else {
-      // split by sites (also where sweep_form(c, overlap) == 2: no fused fp32 sweep yet)
-      const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
-      HIPCHK(hipEventRecord(c->ev_ready, c->stream));
-      CHK(comm_halo_exchange_f32(c, in, 1 - parity, 1));
-      CHK(launch_f32_halo(c, fmt, A, lo_end, hi_beg, 0, 0, init, dot, 0, "dslash_f32", c->stream));
-      CHK(launch_f32_halo(c, fmt, A, 0, lo_end, hi_beg, g.Vh, init, dot, nb_int, "dslash_f32_bnd", c->cstream));
-      CHK(devjoin_signal(c, c->cstream));
-      if (dot && c->peer) CHK(devjoin_defer(c));
-      else CHK(devjoin_wait(c, c->stream, c->cstream));
-      *nparts = nb_int + nb_lo + nb_hi;
-    }
-    return 0;
-  }
-  const dim3 grid((g.Vh + 255) / 256), block(256);
-  ScopedTimer tm(c, "dslash_f32", c->stream);
-#define QX_F32(ND, R)                                                                                  \
-  do {                                                                                                 \
-    if (init && dot) hipLaunchKernelGGL((k_dslash_f32<ND, false, true, true, R>), grid, block, 0, c->stream, A);   \
-    else if (init) hipLaunchKernelGGL((k_dslash_f32<ND, false, true, false, R>), grid, block, 0, c->stream, A);    \
-    else if (dot) hipLaunchKernelGGL((k_dslash_f32<ND, false, false, true, R>), grid, block, 0, c->stream, A);     \
-    else hipLaunchKernelGGL((k_dslash_f32<ND, false, false, false, R>), grid, block, 0, c->stream, A);             \
-  } while (0)
-  if (c->ndir == 8) { if (fmt == 1) QX_F32(8, 1); else QX_F32(8, 0); }
-  else { if (fmt == 1) QX_F32(16, 1); else QX_F32(16, 0); }
-#undef QX_F32
-  HIPCHK(hipGetLastError());
-  *nparts = (g.Vh + 255) / 256;
-  return 0;
-}
-
+// k_dslash_lowp<StoreF32, ..> behind sweep_lowp<StoreF32> (dslash_lowp.h: the operator, its forms on a slab, the host sweep)
 // r[px] = 4 m2 x - (2D)(2D) x in fp32 (op_xx's two sweeps); dot: <x,r> partials in c->partials[0..*nparts)
 int f32_op_xx(qexhip_ctx *c, DevFieldF &r, DevFieldF &x, double m2, int par_even, int dot, const int *done, int *nparts) {
   CHK(f32_links(c, nullptr, nullptr));
   DevFieldF *t;
   CHK(f32_field(c, F32_T, &t));
-  const int px = par_even ? 0 : 1, py = 1 - px;
-  int np = 0;
-  CHK(sweep_f32(c, *t, x, py, nullptr, 0.0, false, false, done, &np));
-  CHK(sweep_f32(c, r, *t, px, &x, 4.0 * m2, true, dot != 0, done, &np));
-  if (nparts) *nparts = np;
-  return 0;
+  return op_xx_lowp<StoreF32>(c, r, x, *t, m2, par_even, dot, done, nparts);
 }
 
 // ---- precision conversions ----------------------------------------------------------------------------------------

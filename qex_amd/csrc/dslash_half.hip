@@ -1,8 +1,8 @@
 // dslash_half.hip -- 16-bit storage for the mixed-precision CG (SolverParams.sloppySolve = SloppyHalf with option "half" = 1;
 // QUDA's half precision behind qudaWrapperImpl.nim:197): a 16-bit copy of the operator's links, the Dslash sweep on 16-bit
 // vectors, and the BLAS kernels of the reliable-update CG whose host control is solve_xx_half_dev (solver.cpp).  Whole lattice on
-// one GPU, or a t-sharded slab with ghost zones filled by the 16-bit face exchange (comm_halo_exchange_half); one system; no fused
-// (self-pushing) form.  Arithmetic is fp32 (dslash_f32_core.h); only what lies in HBM between kernels is 16-bit.
+// one GPU, or a t-sharded slab with ghost zones filled by the 16-bit face exchange; one system.  The sweep itself is dslash_lowp.h's,
+// in 16-bit storage.  Arithmetic is fp32 (dslash_f32_core.h); only what lies in HBM between kernels is 16-bit.
 //
 // Vectors: fixed point, not IEEE half.  One site is 16 bytes, six int16 (re, im of the three colours) and one fp32 norm = the
 // largest |component| of the site: q = rint(v 32767 / norm), v ~ q norm / 32767; a zero site (norm below FLT_MIN) is all zeros.
@@ -25,7 +25,7 @@
 #include "site_index.h"
 #include "reduce.h"
 #include "cg_device.h"
-#include "dslash_half_core.h"
+#include "dslash_lowp.h"
 #include <cstring>
 #include <cmath>
 #include <cfloat>
@@ -217,192 +217,12 @@ static int half_field(qexhip_ctx *c, int slot, DevFieldH **f) {
 }
 
 // ---- 16-bit Dslash sweep ------------------------------------------------------------------------------------------------
-// out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)]) as k_dslash_f32: one lane per site, links streamed
-// non-temporally, fp32 FMAs on the integer link entries with one scale s norm_nbr / 32767^2 per hop on the neighbour's 3-vector,
-// the site normed, rounded and written with one 16-byte store; <xs,out> partials in double from the stored values.
-//   HALO = false  the whole lattice on one GPU (t-hops wrap)
-//   HALO = true   a t-sharded slab (or a one-rank context with a halo): t-hops that leave the slab read the ghost zones (nbr_pos<true>),
-//                 over the site range [c0,c1) plus [d0,d1) for workgroups >= nb1 (both faces in one launch), as k_dslash_f32<.., HALO, ..>.
-//                 Every site runs the operations of the HALO = false kernel in the same order -- the same hop order, one scale per hop on
-//                 the unpacked neighbour, pack_site on the result, the dot from the values as stored; only the positions its t-hops
-//                 read differ --, so a slab's output is the one-rank operator's bits site for site.
-struct DslashHalfArgs {
-  Geom g;
-  const void *W;                   // links of the output parity
-  const unsigned long long *S;     // RECON: the fp32 copy's sign masks [tile][dir]
-  const u4v *in;
-  u4v *out;
-  const u4v *xs;
-  float cb, sgn, s_fat, s_long;
-  int parity;
-  double *partials;
-  const int *done;
-};
-struct DslashHalfHaloArgs {        // (a type of its own: the HALO = false kernels keep their kernel arguments and code)
-  DslashHalfArgs a;
-  SweepRanges r;
-};
-template <bool HALO> struct HalfSweepArgs { using T = DslashHalfArgs; };
-template <> struct HalfSweepArgs<true> { using T = DslashHalfHaloArgs; };
-__device__ __forceinline__ const DslashHalfArgs &half_args(const DslashHalfArgs &P) { return P; }
-__device__ __forceinline__ const DslashHalfArgs &half_args(const DslashHalfHaloArgs &P) { return P.a; }
-
-template <int NDIR, bool HALO, bool INIT, bool DOT, int RECON>
-__global__ void __launch_bounds__(256) k_dslash_half(typename HalfSweepArgs<HALO>::T P) {
-  const DslashHalfArgs &A = half_args(P);
-  if (A.done && *A.done) return;
-  const Geom &g = A.g;
-  int c = blockIdx.x * 256 + threadIdx.x, clim = g.Vh;
-  if constexpr (HALO) sweep_site(P.r, blockIdx.x, c, clim);
-  const bool active = c < clim;
-  double dotv = 0;
-  if (active) {
-    const SiteXYZT s = site_coord(g, c, A.parity);
-    const LinkCursorH<NDIR, RECON> L(A.W, A.S, c);
-    float2 acc[3], xsv[3];
-    if (INIT || DOT) unpack_site(A.xs[c], xsv, HQ_INV);
-#pragma unroll
-    for (int k = 0; k < 3; k++) acc[k] = INIT ? make_float2((A.sgn * A.cb) * xsv[k].x, (A.sgn * A.cb) * xsv[k].y) : make_float2(0.f, 0.f);
-    const float qf = (RECON == 1 ? 1.f : A.s_fat) * (HQ_INV * HQ_INV), ql = (RECON == 1 ? 1.f : A.s_long) * (HQ_INV * HQ_INV);
-    constexpr int UNR = NDIR == 8 ? 4 : 2;
-#pragma unroll UNR
-    for (int pr = 0; pr < NDIR / 2; pr++) {
-      const int mu = pr & 3;
-      const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
-      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
-      const u4v hf = A.in[pf], hb = A.in[pb];
-      float2 U[9], W[9], vf[3], vb[3];
-      L.fetch(pr, U, W);
-      const float sc = pr >= 4 ? ql : qf;
-      unpack_site(hf, vf, sc);
-      unpack_site(hb, vb, sc);
-      mv3f<false>(acc, U, vf);
-      mv3f<true>(acc, W, vb);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { acc[k].x *= A.sgn; acc[k].y *= A.sgn; }
-    A.out[c] = pack_site(acc);
-    if (DOT) {
-#pragma unroll
-      for (int k = 0; k < 3; k++)
-        dotv = fma((double)xsv[k].x, (double)acc[k].x, fma((double)xsv[k].y, (double)acc[k].y, dotv));
-    }
-  }
-  if (DOT) {
-    const double r = block_sum_256(dotv);
-    if (threadIdx.x == 0) A.partials[blockIdx.x] = r;
-  }
-}
-
-// one launch of the halo kernel over [c0,c1) (+ [d0,d1) behind it) on stream st, dot partials from A.partials + part_off
-static int launch_half_halo(qexhip_ctx *c, int fmt, const DslashHalfArgs &A, int c0, int c1, int d0, int d1, bool init, bool dot,
-                            int part_off, const char *tname, hipStream_t st) {
-  DslashHalfHaloArgs P;
-  memset(&P, 0, sizeof P);
-  const int nb = sweep_ranges(P.r, c0, c1, d0, d1);
-  if (!nb) return 0;
-  P.a = A;
-  P.a.partials = A.partials + part_off;
-  const dim3 grid(nb), block(256);
-  ScopedTimer tm(c, tname, st);
-#define QX_HH(ND, R)                                                                                      \
-  do {                                                                                                    \
-    if (init && dot) hipLaunchKernelGGL((k_dslash_half<ND, true, true, true, R>), grid, block, 0, st, P);    \
-    else if (init) hipLaunchKernelGGL((k_dslash_half<ND, true, true, false, R>), grid, block, 0, st, P);     \
-    else if (dot) hipLaunchKernelGGL((k_dslash_half<ND, true, false, true, R>), grid, block, 0, st, P);      \
-    else hipLaunchKernelGGL((k_dslash_half<ND, true, false, false, R>), grid, block, 0, st, P);              \
-  } while (0)
-  if (c->ndir == 8) { if (fmt == 1) QX_HH(8, 1); else QX_HH(8, 0); }
-  else { if (fmt == 1) QX_HH(16, 1); else QX_HH(16, 0); }
-#undef QX_HH
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// One 16-bit sweep; *nparts <- how many <xs,out> partials it left in c->partials.  With g.halo in sweep_f32's two forms, chosen by the
-// same sweep_plan: exchange-first (the 16-byte-per-site faces on the compute stream, one launch over all sites with the one-rank
-// workgroup partition) or split by sites (interior launch on the compute stream; exchange and both faces' launch on the comm stream;
-// device-side join).  There is no fused 16-bit kernel: where sweep_form picks the fused form, the 16-bit sweep is split by sites.
-// dot: the caller's next operation on the compute stream is comm_allreduce_parts (slph_iterate), which takes the join of a split sweep
-// with it where the mailboxes carry the sum.
-static int sweep_half(qexhip_ctx *c, DevFieldH &out, DevFieldH &in, int parity, const DevFieldH *xs, double cb, bool neg, bool dot,
-                      const int *done, int *nparts) {
-  const Geom &g = c->g;
-  HalfState *S = hs_of(c);
-  if (S->fmt < 0) { qexhip_set_error("internal: 16-bit sweep without its links"); return -3; }
-  DslashHalfArgs A;
-  memset(&A, 0, sizeof A);
-  A.g = g;
-  const int fmt = S->fmt;
-  const size_t rows = (size_t)parity * g.ntile * (c->ndir / 2);          // pair rows before this parity
-  A.W = (const char *)S->W + rows * (fmt == 1 ? 3 * 64 * 16 : HALF_ROW0);
-  if (fmt == 1) {
-    const void *Wf = nullptr;
-    int f32fmt = 0;
-    CHK(f32_links_dev(c, parity, &Wf, &A.S, &f32fmt));
-    if (f32fmt != 1 || !A.S) { qexhip_set_error("internal: the 16-bit links' sign masks are gone"); return -3; }
-  }
-  A.in = in.par(1 - parity);
-  A.out = out.par(parity);
-  A.xs = xs ? xs->par(parity) : nullptr;
-  A.cb = (float)cb;
-  A.sgn = neg ? -1.f : 1.f;
-  A.s_fat = (float)S->s_fat; A.s_long = (float)S->s_long;
-  A.parity = parity;
-  A.partials = c->partials;
-  A.done = done;
-  const bool init = cb != 0.0;
-  c->bnd_out_on_cstream = nullptr;
-  if (g.halo) {
-    int lo_end, hi_beg, overlap;
-    sweep_plan(c, &lo_end, &hi_beg, &overlap);
-    CHK(devjoin_flush(c));
-    if (!overlap) {
-      CHK(comm_halo_exchange_half(c, in, 1 - parity, 0));
-      CHK(launch_half_halo(c, fmt, A, 0, g.Vh, 0, 0, init, dot, 0, "dslash_half", c->stream));
-      *nparts = (g.Vh + 255) / 256;
-    } else {
-      // split by sites (also where sweep_form(c, overlap) == 2: there is no fused 16-bit sweep)
-      const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
-      HIPCHK(hipEventRecord(c->ev_ready, c->stream));
-      CHK(comm_halo_exchange_half(c, in, 1 - parity, 1));
-      CHK(launch_half_halo(c, fmt, A, lo_end, hi_beg, 0, 0, init, dot, 0, "dslash_half", c->stream));
-      CHK(launch_half_halo(c, fmt, A, 0, lo_end, hi_beg, g.Vh, init, dot, nb_int, "dslash_half_bnd", c->cstream));
-      CHK(devjoin_signal(c, c->cstream));
-      if (dot && c->peer) CHK(devjoin_defer(c));
-      else CHK(devjoin_wait(c, c->stream, c->cstream));
-      *nparts = nb_int + nb_lo + nb_hi;
-    }
-    return 0;
-  }
-  const dim3 grid((g.Vh + 255) / 256), block(256);
-  ScopedTimer tm(c, "dslash_half", c->stream);
-#define QX_H(ND, R)                                                                                      \
-  do {                                                                                                   \
-    if (init && dot) hipLaunchKernelGGL((k_dslash_half<ND, false, true, true, R>), grid, block, 0, c->stream, A);   \
-    else if (init) hipLaunchKernelGGL((k_dslash_half<ND, false, true, false, R>), grid, block, 0, c->stream, A);    \
-    else if (dot) hipLaunchKernelGGL((k_dslash_half<ND, false, false, true, R>), grid, block, 0, c->stream, A);     \
-    else hipLaunchKernelGGL((k_dslash_half<ND, false, false, false, R>), grid, block, 0, c->stream, A);             \
-  } while (0)
-  if (c->ndir == 8) { if (fmt == 1) QX_H(8, 1); else QX_H(8, 0); }
-  else { if (fmt == 1) QX_H(16, 1); else QX_H(16, 0); }
-#undef QX_H
-  HIPCHK(hipGetLastError());
-  *nparts = (g.Vh + 255) / 256;
-  return 0;
-}
-
+// k_dslash_lowp<StoreHalf, ..> behind sweep_lowp<StoreHalf> (dslash_lowp.h: the operator, its one scale per hop, its forms on a slab)
 // r[px] = 4 m2 x - (2D)(2D) x on 16-bit fields (slots of HalfState); dot: <x,r> partials in c->partials[0..*nparts)
 static int half_op_xx(qexhip_ctx *c, DevFieldH &r, DevFieldH &x, double m2, int par_even, int dot, const int *done, int *nparts) {
   DevFieldH *t;
   CHK(half_field(c, HALF_T, &t));
-  const int px = par_even ? 0 : 1, py = 1 - px;
-  int np = 0;
-  CHK(sweep_half(c, *t, x, py, nullptr, 0.0, false, false, done, &np));
-  CHK(sweep_half(c, r, *t, px, &x, 4.0 * m2, true, dot != 0, done, &np));
-  if (nparts) *nparts = np;
-  return 0;
+  return op_xx_lowp<StoreHalf>(c, r, x, *t, m2, par_even, dot, done, nparts);
 }
 
 // ---- conversions (the operator probe) ---------------------------------------------------------------------------------

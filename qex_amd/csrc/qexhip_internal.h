@@ -360,8 +360,7 @@ int comm_halo_push_only_multi(qexhip_ctx *c, int n, DevField *const *f, int pari
                                                                               // and reads what arrives in the receive arena
 int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool wait_ready = true);  // overlap: on cstream after ev_ready (wait_ready);
                                                                               // the caller joins behind what it posts next
-int comm_halo_exchange_f32(qexhip_ctx *c, DevFieldF &f, int parity, int overlap);  // the same for an fp32 field (half the bytes)
-int comm_halo_exchange_half(qexhip_ctx *c, DevFieldH &f, int parity, int overlap); // and for a 16-bit field (16 B per site, a third of fp64's)
+int comm_halo_exchange_sites(qexhip_ctx *c, void *half, size_t site_bytes, int overlap);  // the same for one parity half of an fp32 (24 B per site) or 16-bit (16 B) field
 int comm_halo_exchange_multi(qexhip_ctx *c, int n, DevField *const *f, int parity, int overlap);   // n fields, one RCCL group
 int comm_allreduce(qexhip_ctx *c, double *dptr, int n);          // on stream
 int comm_allreduce_parts(qexhip_ctx *c, double *parts, int n, int *n_out);   // workgroup partials -> *n_out values whose sum is the rank-global dot product
