@@ -451,6 +451,25 @@ int qexhip_dev_trace_accum(qexhip_handle h, int cfield, int n, const int *a_ids,
  * bit-identical run to run and for any number of ranks. */
 int qexhip_dev_cfield_slices(qexhip_handle h, int cfield, double *out);
 
+/* ---------------- connected scalar correlator from point sources on resident fields ----------------
+ * The pieces of src/observables/conn4d.nim (the connected part of the flavour-singlet scalar) around the batched solves
+ * (qexhip_dev_solve_batch*); `locmes` is a cfield of the section above, est[t] the Re column of qexhip_dev_cfield_slices.
+ * Coordinates are GLOBAL (x, y, z, t), pts[4*k + mu]; a coordinate outside the global lattice, a colour outside 0..2, n outside
+ * 1..4 or an unknown id is QEXHIP_ERR_ARG before anything is written.
+ *
+ * pointSource (conn4d.nim:173-182) for n <= 4 distinct colour vectors in one launch: field ids[k] := 0 on every site, then 1 + 0i
+ * in colour ic[k] at pts[k].  On a t-sharded context only the rank that owns pts[k][3] stores the one. */
+int qexhip_dev_point_source(qexhip_handle h, int n, const int *ids, const int *pts /* n x 4, global */, const int *ic);
+/* Re cfield(x) += scal * |phi_k(x (+) pts_k)|^2 for k = 0..n-1 (n <= 4), (+) the coordinate-wise sum wrapped over the global
+ * extents: conn4d.nim:223-229, whose `translate` (:184-195) shifts forward pts[mu] times, so the source point lands on the origin.
+ * |phi|^2 is the fma chain of qexhip_dev_trace_accum with a == b, then w = scal * n2, then acc += w, the n terms one at a time in
+ * ascending k: the result is bit for bit that of n calls with one system each.  The imaginary part is not touched.  Odd
+ * coordinates are allowed.  On a t-sharded context w (8 B per site) travels through one all-gather and every rank's slab equals
+ * the one-rank result bit for bit. */
+int qexhip_dev_conn_accum(qexhip_handle h, int cfield, int n, const int *phi_ids, const int *pts /* n x 4, global */, double scal);
+/* cfield(x) *= (-1)^(x0+x1+x2), both components, in place (conn4d.nim:238-245) */
+int qexhip_cfield_stag_sign(qexhip_handle h, int cfield);
+
 /* ---------------- low modes of the even/odd operator and deflated solves ----------------
  * src/eigens/hisqev.nim: the lowest singular pairs (sv_i, v_i) of D_oe on the even sites (`hisqev` with EigOpts, hisqev.nim:380-560,
  * block Lanczos of src/eigens/svdLanczos.nim + Rayleigh-Ritz passes), and the deflated solveEE of its main program (:653-705).

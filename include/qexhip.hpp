@@ -462,7 +462,18 @@ class TraceField {
     out.resize((size_t)c_.lo.nSites * 2);
     check(qexhip_cfield_download(c_.h, id, out.data()));
   }
+  // conn4d.nim:223-229: Re trce(x) += scal |phi_k(x (+) pts[k])|^2, k ascending (at most four propagators a call; global points)
+  void connAccum(const std::vector<int> &phi, const std::vector<std::array<int, 4>> &pts, double scal) {
+    if (phi.size() != pts.size()) throw Error("TraceField::connAccum: phi and pts differ in length");
+    check(qexhip_dev_conn_accum(c_.h, id, (int)phi.size(), phi.data(), pts.empty() ? nullptr : pts[0].data(), scal));
+  }
+  void stagSign() { check(qexhip_cfield_stag_sign(c_.h, id)); }     // trce(x) *= (-1)^(x0+x1+x2)  (conn4d.nim:238-245)
 };
+// pointSource (conn4d.nim:173-182): field ids[k] := 0, then 1 in colour ic[k] at the global point pts[k] (at most four a call)
+inline void pointSource(Context &c, const std::vector<int> &ids, const std::vector<std::array<int, 4>> &pts, const std::vector<int> &ic) {
+  if (ids.size() != pts.size() || ids.size() != ic.size()) throw Error("pointSource: ids, pts and ic differ in length");
+  check(qexhip_dev_point_source(c.h, (int)ids.size(), ids.data(), pts.empty() ? nullptr : pts[0].data(), ic.data()));
+}
 enum DilutionKind { dkEvenOdd = 0, dkCorners3D = 1 };     // src/algorithms/dilution.nim
 // dst_k = scale * src on the sites of global time t[k] in pattern idx[k], zero elsewhere (at most four destinations a call)
 inline void dilute(Context &c, const std::vector<int> &dst, int src, DilutionKind kind, const std::vector<int> &idx, const std::vector<int> &t,

@@ -14,6 +14,7 @@ from .staggered import (  # noqa: F401
 )
 from .stout import StoutSmear, newStoutSmear, stoutSmear, stoutSmearGetForce  # noqa: F401
 from .io import loadGauge, loadGaugeSlab, saveGauge, getFileLattice, gaugeFileInfo, writeField, readField, fileMetadata  # noqa: F401
-from .rng import RngField, RngMilc6, MRG32k3a  # noqa: F401
+from .rng import GlobalRng, RngField, RngMilc6, MRG32k3a  # noqa: F401
 from .mesons import stagLocalMesons, stagMesons, norm2slice, sft, printLocalMesons, pointSource, wallSource, localMesonTables  # noqa: F401
 from .scalar_trace import DilutionKind, Dilution, dilution, parseDilution, scalarTrace  # noqa: F401
+from .conn4d import connMeson, defaultSqMinDistance, randomPoint  # noqa: F401

@@ -186,6 +186,9 @@ SYMBOLS = [
     ("qexhip_dev_dilute", _ci, [_vp, _ci, _pi, _ci, _ci, _pi, _pi, _cd]),
     ("qexhip_dev_trace_accum", _ci, [_vp, _ci, _ci, _pi, _pi, _cd]),
     ("qexhip_dev_cfield_slices", _ci, [_vp, _ci, _vp]),
+    ("qexhip_dev_point_source", _ci, [_vp, _ci, _pi, _pi, _pi]),
+    ("qexhip_dev_conn_accum", _ci, [_vp, _ci, _ci, _pi, _pi, _cd]),
+    ("qexhip_cfield_stag_sign", _ci, [_vp, _ci]),
     ("qexhip_nhyp_fforce_dev", _ci, [_vp, _vp, _ci, _pi, _pd, _pd, _pd, _ci, _pi, _pi, _pi]),
     ("qexhip_rng_state_words", _ci, [_vp]),
     ("qexhip_rng_get_state", _ci, [_vp, _vp]),

@@ -1186,6 +1186,53 @@ extern "C" int qexhip_dev_cfield_slices(qexhip_handle c, int cfield, double *out
   return cfield_slices(c, *tr, out);
 }
 
+// ---- connected scalar correlator from point sources (conn4d.nim): point sources, translated |phi|^2 accumulation, staggered sign ----
+static int check_points(qexhip_ctx *c, const char *who, int n, const int *pts) {
+  for (int k = 0; k < n; k++)
+    for (int mu = 0; mu < 4; mu++) {
+      const int L = c->g.X[mu] * c->rankGeom[mu];
+      if (pts[4 * k + mu] < 0 || pts[4 * k + mu] >= L) {
+        qexhip_set_error("%s: pts[%d][%d] = %d outside [0, %d)", who, k, mu, pts[4 * k + mu], L);
+        return QEXHIP_ERR_ARG;
+      }
+    }
+  return 0;
+}
+extern "C" int qexhip_dev_point_source(qexhip_handle c, int n, const int *ids, const int *pts, const int *ic) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!ids || !pts || !ic) { qexhip_set_error("dev_point_source: null argument"); return QEXHIP_ERR_ARG; }
+  if (n < 1 || n > 4) { qexhip_set_error("dev_point_source: n = %d, must be 1..4", n); return QEXHIP_ERR_ARG; }
+  DevField *dst[4];
+  for (int k = 0; k < n; k++) {
+    for (int j = 0; j < k; j++)
+      if (ids[j] == ids[k]) { qexhip_set_error("dev_point_source: destinations %d and %d are the same field %d", j, k, ids[k]); return QEXHIP_ERR_ARG; }
+    CHK(find_field(c, ids[k], &dst[k]));
+    if (ic[k] < 0 || ic[k] > 2) { qexhip_set_error("dev_point_source: ic[%d] = %d, must be 0..2", k, ic[k]); return QEXHIP_ERR_ARG; }
+  }
+  CHK(check_points(c, "dev_point_source", n, pts));
+  HIPCHK(hipSetDevice(c->device));
+  return conn_point_source(c, n, dst, pts, ic);
+}
+extern "C" int qexhip_dev_conn_accum(qexhip_handle c, int cfield, int n, const int *phi_ids, const int *pts, double scal) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!phi_ids || !pts) { qexhip_set_error("dev_conn_accum: null argument"); return QEXHIP_ERR_ARG; }
+  if (n < 1 || n > 4) { qexhip_set_error("dev_conn_accum: n = %d, must be 1..4", n); return QEXHIP_ERR_ARG; }
+  DevCField *tr;
+  CHK(find_cfield(c, cfield, &tr));
+  DevField *phi[4];
+  for (int k = 0; k < n; k++) CHK(find_field(c, phi_ids[k], &phi[k]));
+  CHK(check_points(c, "dev_conn_accum", n, pts));
+  HIPCHK(hipSetDevice(c->device));
+  return conn_accum(c, *tr, n, phi, pts, scal);
+}
+extern "C" int qexhip_cfield_stag_sign(qexhip_handle c, int cfield) {
+  if (!c) return QEXHIP_ERR_ARG;
+  DevCField *tr;
+  CHK(find_cfield(c, cfield, &tr));
+  HIPCHK(hipSetDevice(c->device));
+  return cfield_stag_sign(c, *tr);
+}
+
 // ---- link smearing ----
 extern "C" int qexhip_fat7(qexhip_handle c, const double *g, const double coef[5], double *fl, double *ll, double naik) {
   if (!c || !g || !coef || !fl) return QEXHIP_ERR_ARG;

@@ -595,6 +595,11 @@ int trace_dilute(qexhip_ctx *c, int n, DevField *const *dst, const DevField &src
 int trace_accum(qexhip_ctx *c, DevCField &tr, int n, DevField *const *a, DevField *const *b, double coef);
 int cfield_slices(qexhip_ctx *c, const DevCField &tr, double *host_out);              // [nt_global][2], rank-global
 
+// ---- conn.hip: point sources, translated |phi|^2 accumulation and staggered sign of the connected scalar correlator ----
+int conn_point_source(qexhip_ctx *c, int n, DevField *const *dst, const int *pts, const int *ic);            // pts: [n][4], global
+int conn_accum(qexhip_ctx *c, DevCField &tr, int n, DevField *const *phi, const int *pts, double scal);
+int cfield_stag_sign(qexhip_ctx *c, DevCField &f);
+
 // ---- smear.hip ----
 int smear_fat7_host(qexhip_ctx *c, const double *g_host, const double coef[5], double *fl_host, double *ll_host, double naik);
 int smear_hisq_host(qexhip_ctx *c, const double *g_host, double *fl_host, double *ll_host);

@@ -87,6 +87,10 @@ proc qexhip_cfield_download(h: QexhipHandle; id: cint; host: ptr cdouble): cint 
 proc qexhip_dev_dilute(h: QexhipHandle; n: cint; dstIds: ptr cint; srcId, kind: cint; idx, t: ptr cint; scale: cdouble): cint {.qh.}
 proc qexhip_dev_trace_accum(h: QexhipHandle; cfield, n: cint; aIds, bIds: ptr cint; coef: cdouble): cint {.qh.}
 proc qexhip_dev_cfield_slices(h: QexhipHandle; cfield: cint; o: ptr cdouble): cint {.qh.}
+# connected scalar correlator from point sources (conn4d.nim): point sources, translated |phi|^2 accumulation, staggered sign
+proc qexhip_dev_point_source(h: QexhipHandle; n: cint; ids, pts, ic: ptr cint): cint {.qh.}
+proc qexhip_dev_conn_accum(h: QexhipHandle; cfield, n: cint; phiIds, pts: ptr cint; scal: cdouble): cint {.qh.}
+proc qexhip_cfield_stag_sign(h: QexhipHandle; cfield: cint): cint {.qh.}
 proc qexhip_rng_z4_vector(r: pointer; v: ptr cdouble): cint {.qh.}
 proc qexhip_rng_z2_vector(r: pointer; v: ptr cdouble): cint {.qh.}
 proc qexhip_rng_dev_z4_vector(h: QexhipHandle; r: pointer; fieldId: cint): cint {.qh.}

@@ -10,6 +10,28 @@ from ._lib import check, lib
 RngMilc6, MRG32k3a = 0, 1
 
 
+class GlobalRng:
+    """`var R: RngMilc6; R.seed(seed, 987654321)` (src/observables/conn4d.nim:63-65, staghmc_sh.nim:178-179): ONE RngMilc6 stream,
+    not a field of them -- the global generator every rank advances alike.  Host only."""
+
+    def __init__(self, seed, index=987654321):
+        m = 0xFFFFFFFF
+        s, self.r = int(seed) & m, []
+        for _ in range(7):
+            s = ((69607 + 8 * index) * s + 12345) & m
+            self.r.append((s >> 8) & 0xFFFFFF)
+        self.ic = ((69607 + 8 * index) * s + 12345) & m
+        self.mult = (100005 + 8 * index) & m
+
+    def uniform(self):
+        """the next draw in [0, 1): a multiple of 2^-24, as the reference's float32 product gives it"""
+        r = self.r
+        t = (((r[5] >> 7) | (r[6] << 17)) ^ ((r[4] >> 1) | (r[5] << 23))) & 0xFFFFFF
+        self.r = [t] + r[:6]
+        self.ic = (self.ic * self.mult + 12345) & 0xFFFFFFFF
+        return float(np.float32(t ^ ((self.ic >> 8) & 0xFFFFFF)) * np.float32(1.0 / 16777216.0))
+
+
 class RngField:
     """lo.newRNGField(RngMilc6 | MRG32k3a, seed); for a t-sharded rank pass the global lattice and t_offset."""
 

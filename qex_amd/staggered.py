@@ -466,6 +466,29 @@ class Context:
         check(lib().qexhip_dev_cfield_slices(self._h, int(cid), _p(out)))
         return out
 
+    # connected scalar correlator (conn4d.nim; csrc/conn.hip): point sources, translated |phi|^2 accumulation, staggered sign
+    def dev_point_source(self, ids, pts, ic):
+        """field ids[k] := 0, then 1 + 0i in colour ic[k] at the GLOBAL coordinate pts[k] = (x, y, z, t); up to four in one launch"""
+        n = len(ids)
+        if n != len(pts) or n != len(ic) or any(len(p) != 4 for p in pts):
+            raise ValueError("ids, pts (four coordinates each) and ic differ in length")
+        i = C.c_int * max(n, 1)
+        check(lib().qexhip_dev_point_source(self._h, n, i(*[int(v) for v in ids]), (C.c_int * max(4 * n, 1))(*[int(v) for p in pts for v in p]),
+                                            i(*[int(v) for v in ic])))
+
+    def dev_conn_accum(self, cid, phis, pts, scal):
+        """Re cfield(x) += scal * |phi_k(x (+) pts[k])|^2 for up to four propagators, one after the other in ascending k; (+) wraps
+        over the GLOBAL extents, so the source point pts[k] lands on the origin"""
+        n = len(phis)
+        if n != len(pts) or any(len(p) != 4 for p in pts):
+            raise ValueError("phis and pts (four coordinates each) differ in length")
+        check(lib().qexhip_dev_conn_accum(self._h, int(cid), n, (C.c_int * max(n, 1))(*[int(v) for v in phis]),
+                                          (C.c_int * max(4 * n, 1))(*[int(v) for p in pts for v in p]), float(scal)))
+
+    def cfield_stag_sign(self, cid):
+        """cfield(x) *= (-1)^(x0+x1+x2), in place"""
+        check(lib().qexhip_cfield_stag_sign(self._h, int(cid)))
+
     # field algebra hooks (fieldET.nim:605-625,704-724)
     def norm2(self, x, subset="all"):
         out = C.c_double(0)
