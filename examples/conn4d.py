@@ -12,7 +12,7 @@ unit gauge.  The links are re-unitarised, nHYP(0.4, 0.5, 0.5) smeared and given 
 phases on the device; the points come from -sources or from randomPoint on the global RngMilc6 stream of the seed (every rank draws
 the same points); the 3 * num_source point sources are built, solved in lock-step batches of -batch systems and contracted on the
 device (qex_amd.connMeson).  locmes is written as one SciDAC record of 8-byte sites.  -sloppy 1 or 2 solves in mixed precision: one
-rank only; -half 1 lets -sloppy 2 iterate on 16-bit storage (the context options "half" and "half_batch"; default 0: it runs
+rank only unless -batch_ranks 1 is given (the context option "batch_ranks" on every rank: the batches run t-sharded); -half 1 lets -sloppy 2 iterate on 16-bit storage (the context options "half" and "half_batch"; default 0: it runs
 single).  -nev N computes the N lowest eigenpairs of the even/odd operator once and deflates every batch with them."""
 import argparse
 import os
@@ -37,12 +37,14 @@ ap.add_argument("-sq_min_distance", type=int, default=None)
 ap.add_argument("-seed", type=int, default=int(1000 * time.time()))
 ap.add_argument("-sloppy", type=int, default=2, choices=[0, 1, 2])
 ap.add_argument("-half", type=int, default=0, choices=[0, 1], help="1: -sloppy 2 iterates on 16-bit storage (options half, half_batch)")
+ap.add_argument("-batch_ranks", type=int, default=0, choices=[0, 1],
+                help="1: on more than one rank, -sloppy 1 / 2 runs the mixed-precision lock-step batches t-sharded (option batch_ranks)")
 ap.add_argument("-batch", type=int, default=4, choices=[1, 2, 3, 4])
 ap.add_argument("-nev", type=int, default=0, help="deflate every batch with this many low modes (0: no eigensolve)")
 a = ap.parse_args()
 if len(a.sources) % 4 != 0:
     sys.exit("sources should be an integer array with its length divisable by 4\n  received: %s" % (a.sources,))
-if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.batch_ranks:
     sys.exit("conn4d.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
              "lattices (run with -sloppy 0, or on one rank)" % a.sloppy)
 
@@ -69,6 +71,11 @@ if world > 1:
     uid = [q.Context.unique_id() if rank == 0 else None]
     dist.broadcast_object_list(uid, src=0)
     ctx.comm_init(uid[0], world, rank)
+    if a.batch_ranks:                             # (the same options on every rank)
+        ctx.set_option("batch_ranks", 1)
+        if a.half:
+            ctx.set_option("half", 1)
+            ctx.set_option("half_batch", 1)
 else:
     ctx = q.Context(lat)
     if a.half:

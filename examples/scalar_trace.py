@@ -11,7 +11,8 @@ The parameters are the reference program's.  Without -inlat the configuration is
 streams then go on into the noise, as there; -smear 1 builds the operator on nHYP(0.4, 0.5, 0.5) links (the reference always
 smears).  The noise is drawn, diluted, solved in lock-step batches of -batch patterns and contracted on the device
 (qex_amd.scalarTrace); each trace is written as one SciDAC record of 16-byte sites, read back, and its per-timeslice sums are
-printed once more, as `loadsrc` lines.  -sloppy 1 or 2 solves in mixed precision: one rank only; -half 1 lets -sloppy 2 iterate on
+printed once more, as `loadsrc` lines.  -sloppy 1 or 2 solves in mixed precision: one rank only unless -batch_ranks 1 is
+given (the context option "batch_ranks" on every rank: the batches run t-sharded); -half 1 lets -sloppy 2 iterate on
 16-bit storage (the context options "half" and "half_batch"; default 0: it runs single).  -nev N computes the N lowest
 eigenpairs of the even/odd operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every
 batch with them, the odd-parity patterns included; the first source is then also solved without deflation and the eigensolve
@@ -37,6 +38,8 @@ ap.add_argument("-outfn", default="output")
 ap.add_argument("-mass", type=float, default=0.1)
 ap.add_argument("-sloppy", type=int, default=0, choices=[0, 1, 2])
 ap.add_argument("-half", type=int, default=0, choices=[0, 1], help="1: -sloppy 2 iterates on 16-bit storage (options half, half_batch)")
+ap.add_argument("-batch_ranks", type=int, default=0, choices=[0, 1],
+                help="1: on more than one rank, -sloppy 1 / 2 runs the mixed-precision lock-step batches t-sharded (option batch_ranks)")
 ap.add_argument("-cg_prec", type=float, default=1e-9)
 ap.add_argument("-cg_max", type=int, default=100000)
 ap.add_argument("-num_stoch", type=int, default=1)
@@ -51,7 +54,7 @@ ap.add_argument("-nvecs", type=int, default=0, help="size of the Lanczos basis (
 ap.add_argument("-cheb", type=int, default=12, help="Chebyshev degree (0: plain Lanczos)")
 ap.add_argument("-cheb_lo", type=float, default=0.3)
 a = ap.parse_args()
-if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.batch_ranks:
     sys.exit("scalar_trace.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
              "lattices (run without -sloppy, or on one rank)" % a.sloppy)
 
@@ -76,6 +79,11 @@ if world > 1:
     uid = [q.Context.unique_id() if rank == 0 else None]
     dist.broadcast_object_list(uid, src=0)
     ctx.comm_init(uid[0], world, rank)
+    if a.batch_ranks:                             # (the same options on every rank)
+        ctx.set_option("batch_ranks", 1)
+        if a.half:
+            ctx.set_option("half", 1)
+            ctx.set_option("half_batch", 1)
     rng = q.RngField(lat, q.RngMilc6, a.seed, glat=glat, t_offset=rank * lt)
 else:
     ctx = q.Context(lat)

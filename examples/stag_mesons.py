@@ -2,7 +2,7 @@
 """src/observables/fpvaMeas.nim through libqexhip: local and one-link (symmetric spatial shift) staggered meson correlators
 from point-source propagators.
 
-    python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5] [-sloppy 0] [-half 0]
+    python examples/stag_mesons.py [-lat 8 8 8 8] [-mass 0.1] [-t0 2] [-seed 987654321] [-warm 0.5] [-sloppy 0] [-half 0] [-batch_ranks 0]
                                    [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3]
     python -m torch.distributed.run --nproc-per-node N examples/stag_mesons.py ...     # t-sharded over N ranks
 
@@ -11,7 +11,8 @@ For each colour the point source at (0,0,0,t0) and its three symmetric one-link 
 no propagator leaves the GPU.  The tables are printed as printLocalMesons prints them: Walsh-Hadamard transform over the corner
 bits, normalisation nt / physVol.  The configuration is the library's RngMilc6 warm start (as examples/stag_prop.py), seeded by
 global site, so every partition sees the same gauge field.  -sloppy 1 runs the batches in mixed precision (fp32 iterations with
-fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only; -half 1 lets
+fp64 reliable updates, qexhip_dev_solve_batch_sloppy): one rank only unless -batch_ranks 1 is given (every rank then sets the
+context option "batch_ranks" and the batches run t-sharded); -half 1 lets
 -sloppy 2 iterate on 16-bit storage (the context options "half" and "half_batch"; default 0: it runs single).  -nev N computes the N lowest eigenpairs of the even/odd
 operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every batch with them; the
 measurement is then also run without deflation and the eigensolve time and the iterations with / without are printed."""
@@ -34,12 +35,14 @@ ap.add_argument("-warm", type=float, default=0.5)
 ap.add_argument("-r2req", type=float, default=1e-16)
 ap.add_argument("-sloppy", type=int, default=0, choices=[0, 1, 2])
 ap.add_argument("-half", type=int, default=0, choices=[0, 1], help="1: -sloppy 2 iterates on 16-bit storage (options half, half_batch)")
+ap.add_argument("-batch_ranks", type=int, default=0, choices=[0, 1],
+                help="1: on more than one rank, -sloppy 1 / 2 runs the mixed-precision lock-step batches t-sharded (option batch_ranks)")
 ap.add_argument("-nev", type=int, default=0, help="deflate every batch with this many low modes (0: no eigensolve)")
 ap.add_argument("-nvecs", type=int, default=0, help="size of the Lanczos basis (default max(2 nev, nev + 8))")
 ap.add_argument("-cheb", type=int, default=12, help="Chebyshev degree (0: plain Lanczos)")
 ap.add_argument("-cheb_lo", type=float, default=0.3)
 a = ap.parse_args()
-if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.batch_ranks:
     sys.exit("stag_mesons.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
              "lattices (run without -sloppy, or on one rank)" % a.sloppy)
 
@@ -60,6 +63,11 @@ if world > 1:
     uid = [q.Context.unique_id() if rank == 0 else None]
     dist.broadcast_object_list(uid, src=0)
     ctx.comm_init(uid[0], world, rank)
+    if a.batch_ranks:                             # (the same options on every rank)
+        ctx.set_option("batch_ranks", 1)
+        if a.half:
+            ctx.set_option("half", 1)
+            ctx.set_option("half_batch", 1)
     rng = q.RngField(lat, q.RngMilc6, a.seed, glat=glat, t_offset=rank * lt)
 else:
     ctx = q.Context(lat)

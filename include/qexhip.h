@@ -237,7 +237,8 @@ int qexhip_stag_solve_prev(qexhip_handle h, double *x, const double *b, double m
  *                             ghost zones forced on one rank): the single-system 16-bit solve runs there as on one rank -- the
  *                             faces travel in the 16-bit format, 16 B per site; the int16 links are scaled by the largest
  *                             |entry| of the whole lattice; every rank takes the same updates, the same stall decision and the
- *                             same fp32 finish --, the sloppy batches stay refused
+ *                             same fp32 finish --; the sloppy batches are refused there unless option "batch_ranks" is 1
+ *                             (qexhip_stag_solve_xx_batch_sloppy below)
  * The solve stops on the TRUE (fp64) residual: r2_over_b2 is |b - A x|^2/|b|^2 of the returned x (solveXX); iters counts fp32
  * iterations; nupdates (may be NULL) receives the number of reliable updates, the last one that confirmed convergence included
  * (0 for sloppy = 0).  iters == maxits is not an error.  QEXHIP_ERR_ARG for sloppy outside 0..2.
@@ -346,6 +347,11 @@ int qexhip_dev_op_xx_half(qexhip_handle h, int r_id, int x_id, double m2, int pa
 /* the batched form: n <= 4 fields x_ids[j][par] rounded to the format, ONE batched operator (two multi-right-hand-side 16-bit sweeps that
  * stream the links once for all systems) at m2[j], the results back in fp64 in r_ids[j][par]; per system the bits of qexhip_dev_op_xx_half */
 int qexhip_dev_op_xx_half_batch(qexhip_handle h, int n, const int *r_ids, const int *x_ids, const double *m2, int par_even);
+/* the fp32 twin: n <= 4 fields rounded to fp32, ONE batched fp32 operator (two multi-right-hand-side fp32 sweeps) at m2[j], the
+ * results back in fp64; per system the bits of qexhip_dev_op_xx_sloppy.  Both batched probes run on one rank without ghost zones,
+ * and refuse t-sharded contexts (QEXHIP_ERR_ARG) unless option "batch_ranks" is 1: then they are collective, all systems' faces
+ * travel in one exchange per sweep, and every system's slab is the slab of the one-rank single-system result, bit for bit */
+int qexhip_dev_op_xx_sloppy_batch(qexhip_handle h, int n, const int *r_ids, const int *x_ids, const double *m2, int par_even);
 /* the 16-bit link copy (building it if stale, behind the fp32 copy whose format decision it shares): format 1 = rows 0,1 as int16
  * of u 32767 (clamped) + the fp32 copy's sign masks, 48 B per forward/backward pair; format 0 = 18 reals as int16 of u 32767 / s,
  * 72 B per pair, s = *s_fat for the one-hop links and *s_long for the Naik links: the largest |entry| of each kind (reported in
@@ -402,7 +408,8 @@ int qexhip_dev_zero(qexhip_handle h, int id, int parity);
  * operator's current links: faction / pbp of the HMC drivers without moving a vector (staghmc_sh.nim:260-272,339-364) */
 int qexhip_dev_solve_batch(qexhip_handle h, int n, const int *x_ids, const int *b_ids, const double *mass,
                            const double *r2req, int maxits, int *iters, double *r2);
-/* qexhip_stag_solve_batch_sloppy (below) on resident fields: ONE lock-step batch, n in 1..4 */
+/* qexhip_stag_solve_batch_sloppy (below) on resident fields: ONE lock-step batch, n in 1..4 (t-sharded with sloppy > 0: option
+ * "batch_ranks", as there) */
 int qexhip_dev_solve_batch_sloppy(qexhip_handle h, int n, const int *x_ids, const int *b_ids, const double *mass,
                                   const double *r2req, int maxits, int sloppy, int *iters, double *r2_final, int *nupdates);
 
@@ -550,7 +557,8 @@ int qexhip_stag_solve_deflated(qexhip_handle h, int basis, int nev, double *x, c
  * (a mode with lambda_i <= 0 gets coefficient 0): two single-parity sweeps per system, no second basis.  The projections of all
  * systems are ONE block_dot_multi and ONE block_axpy_multi, so a system's starting guess is bit for bit the single deflated solve's;
  * a system with |b_k - A x0_k|^2 <= r2req_k |b_k|^2 is finished with 0 iterations, the others run as ONE lock-step batch CG (sloppy = 0:
- * the fp64 batch; > 0: the mixed-precision one, refused with QEXHIP_ERR_ARG on t-sharded contexts before anything is launched) on
+ * the fp64 batch; > 0: the mixed-precision one, refused with QEXHIP_ERR_ARG on t-sharded contexts before anything is launched unless
+ * option "batch_ranks" is 1, with which it runs there as qexhip_stag_solve_xx_batch_sloppy describes) on
  * A d_k = r0_k, then x_k = x0_k + d_k.  iters, r2_over_b2 (the TRUE residuals) and nupdates (may be NULL) are arrays of n; maxits is
  * shared.  nev = 0 is the undeflated batch entry itself: same bits, same iteration counts.  solve_batch_deflated: n x Staggered.solve
  * (qexhip_stag_solve_batch semantics: same ReconR / ReconL decisions, outer loop and maxits sharing) whose inner solveXX groups of BOTH
@@ -695,8 +703,16 @@ int qexhip_stag_solve_batch(qexhip_handle h, int n, double *const *x, const doub
  * system, so x, iters (fp32 iterations), the residual and nupdates are bit for bit what qexhip_stag_solve_xx_sloppy /
  * qexhip_stag_solve_sloppy return for it alone; maxits is shared, as in the fp64 batch.  iters, r2_* and nupdates (may be NULL) are
  * arrays of n.  sloppy = 0 is qexhip_stag_solve_xx_batch / qexhip_stag_solve_batch itself (nupdates 0).
- * QEXHIP_ERR_ARG for sloppy outside 0..2, n outside 1..4, mass 0 (with sloppy > 0), and -- with sloppy > 0 -- for t-sharded
- * contexts (more than one rank, or qexhip_comm_force_halo): the batched fp32 face exchange is not built; nothing is launched. */
+ * QEXHIP_ERR_ARG for sloppy outside 0..2, n outside 1..4, mass 0 (with sloppy > 0), and -- with sloppy > 0 and option "batch_ranks"
+ * = 0, the default -- for t-sharded contexts (more than one rank, or qexhip_comm_force_halo); nothing is launched.
+ * With option "batch_ranks" = 1 (set on every rank) the batches run t-sharded, collectively: each rank passes its slabs; the
+ * reduced-precision faces of ALL n systems travel in one exchange per sweep (fp32: 24 B per site, 16-bit with "half_batch" = 1: 16 B),
+ * whether or not a system has finished; every system's <p,Ap>, |r_s|^2 and |b - A x|^2 are rank-global, summed for all systems in
+ * one collective per reduction point exactly as the single-system sharded solve sums them; the reliable updates run the sharded fp64
+ * operator per system.  Every system returns the bits of its single-system sloppy solve on the SAME sharded context (same sweep
+ * form -- option "overlap" --, same transport), every rank returns the same iters, residuals, nupdates and
+ * qexhip_stag_sloppy_last_batch, and the n states are checked for agreement across the ranks every 32 iterations (QEXHIP_ERR_COMM).
+ * The refinement phase of the sharded mixed-precision multi-shift solve stays one shift at a time. */
 int qexhip_stag_solve_xx_batch_sloppy(qexhip_handle h, int n, double *const *x, const double *const *b, const double *mass,
                                       const double *r2req, int maxits, int par_even, int sloppy, int *iters, double *r2_over_b2,
                                       int *nupdates);
@@ -747,8 +763,11 @@ int qexhip_link_ortho_host(const double *links, int n, unsigned char *escaped, d
  *   "half"         1: sloppy = 2 (SloppyHalf) iterates on 16-bit storage in the single-system solves, on one rank and on t-sharded
  *                  contexts (set it on every rank); 0 (default): it runs single.  Other values are refused
  *   "half_batch"   1: sloppy = 2 on the lock-step batched entries (the deflated batches included) iterates on 16-bit storage, up to
- *                  four systems per stream of the int16 links, on a one-rank context without ghost zones; 0 (default): those
+ *                  four systems per stream of the int16 links (t-sharded contexts: with "batch_ranks" = 1); 0 (default): those
  *                  batches run single.  Independent of "half".  Other values are refused
+ *   "batch_ranks"  1: the mixed-precision lock-step batched entries (sloppy > 0; the deflated batches and both batched operator probes
+ *                  included) run on t-sharded contexts -- more than one rank, or qexhip_comm_force_halo; set it on every rank; 0
+ *                  (default): they refuse there, as before the option existed.  Precision follows "half_batch".  Other values are refused
  *   "half_stall"   successive reliable updates of a 16-bit solve that may fail to lower the true residual before the solve
  *                  finishes in fp32 (default 2; 0: hand over at the first update, a test hook)
  *   "stout_check"  inverse iterations of qexhip_stout_inverse posted between two read-backs of its device-side loop state

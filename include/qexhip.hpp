@@ -138,6 +138,11 @@ class Context {
     if (rIds.size() != xIds.size() || rIds.size() != m2.size()) throw std::invalid_argument("devOpXXHalfBatch: sizes differ");
     check(qexhip_dev_op_xx_half_batch(h, (int)rIds.size(), rIds.data(), xIds.data(), m2.data(), parEven ? 1 : 0));
   }
+  // its fp32 twin (qexhip_dev_op_xx_sloppy_batch); both run t-sharded with setOption("batch_ranks", 1) on every rank
+  void devOpXXSloppyBatch(const std::vector<int> &rIds, const std::vector<int> &xIds, const std::vector<double> &m2, bool parEven = true) {
+    if (rIds.size() != xIds.size() || rIds.size() != m2.size()) throw std::invalid_argument("devOpXXSloppyBatch: sizes differ");
+    check(qexhip_dev_op_xx_sloppy_batch(h, (int)rIds.size(), rIds.data(), xIds.data(), m2.data(), parEven ? 1 : 0));
+  }
   // out[par] = r(M^+M) b[par] on resident fields, r(x) = f0 + sum_k alpha_k / (x + beta_k): one accumulating multi-shift solve
   // (qexhip_dev_rational_xx); returns the iterations of the base system
   int devRationalXX(int outId, int bId, double mass, double f0, const std::vector<double> &alpha, const std::vector<double> &beta,
@@ -283,7 +288,7 @@ class Staggered {
   }
   // n <= 4 independent solves on these links in lock-step (one stream of the links per sweep for all of them);
   // per system the result of solve(x[j], b[j], m[j], sps[j]).  sloppy = -1: fp64, and a sloppy SolverParams is refused (as before);
-  // 0, 1, 2: the precision of the batch, chosen explicitly (qexhip_stag_solve_batch_sloppy; one rank only when > 0), overriding
+  // 0, 1, 2: the precision of the batch, chosen explicitly (qexhip_stag_solve_batch_sloppy; when > 0: one rank, or t-sharded with option "batch_ranks" = 1), overriding
   // sps[j].sloppySolve; sps[j].reliableUpdates gets system j's updates
   void solveBatch(std::vector<Field> &xs, const std::vector<Field> &bs, const std::vector<double> &ms, std::vector<SolverParams> &sps,
                   int sloppy = -1) {

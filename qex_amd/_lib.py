@@ -57,6 +57,7 @@ SYMBOLS = [
     ("qexhip_stag_links_info_half", _ci, [_vp, _pi, _pd, _pd, _pd]),
     ("qexhip_stag_sloppy_last", _ci, [_vp, _pi, _pi, _pi, _pi]),
     ("qexhip_dev_op_xx_half_batch", _ci, [_vp, _ci, _pi, _pi, _pd, _ci]),
+    ("qexhip_dev_op_xx_sloppy_batch", _ci, [_vp, _ci, _pi, _pi, _pd, _ci]),
     ("qexhip_stag_sloppy_last_batch", _ci, [_vp, _ci, _pi, _pi, _pi, _pi, _pi]),
     ("qexhip_half_pack_host", _ci, [_pd, C.c_size_t, C.POINTER(C.c_int16), C.POINTER(C.c_float)]),
     ("qexhip_half_unpack_host", _ci, [C.POINTER(C.c_int16), C.POINTER(C.c_float), C.c_size_t, _pd]),

@@ -60,7 +60,8 @@ def connMeson(stag, lo, pts, mass, r2req, maxits=100000, t_offset=0, sloppy=0, b
     then locmes(x) *= (-1)^(x0+x1+x2).  Returns (locmes, est, stats): locmes the (vol,) field of the local lattice in host site
     order, est[t] = sum_{x in slice t} locmes over the GLOBAL t, stats = {"solve_s", "contract_s", "iterations", "updates"}
     (seconds in the batched solves; in sources, accumulation, sign and slice sums; iterations and reliable updates per system in
-    (point, colour) order).  sloppy = 1 (or 2) solves in mixed precision (one rank only).  deflate = an EigBasis of the operator's
+    (point, colour) order).  sloppy = 1 (or 2) solves in mixed precision (one rank; t-sharded with the context option
+    "batch_ranks" = 1 on every rank).  deflate = an EigBasis of the operator's
     even sites, used with its leading nev vectors (None: deflate.nconv).  out receives the reference's log lines (None: none, and
     the norms they print are not computed)."""
     ctx = stag.ctx

@@ -734,6 +734,19 @@ extern "C" int qexhip_dev_op_xx_half_batch(qexhip_handle c, int n, const int *r_
   }
   return half_op_xx_batch_probe(c, n, fr, fx, m2, par_even);
 }
+// the fp32 twin of qexhip_dev_op_xx_half_batch: n <= 4 fields rounded to fp32, ONE batched op_xx (two multi-RHS fp32 sweeps), back in fp64
+extern "C" int qexhip_dev_op_xx_sloppy_batch(qexhip_handle c, int n, const int *r_ids, const int *x_ids, const double *m2, int par_even) {
+  if (!c || !r_ids || !x_ids || !m2) return QEXHIP_ERR_ARG;
+  if (n < 1 || n > 4) { qexhip_set_error("dev_op_xx_sloppy_batch: 1 <= n <= 4"); return QEXHIP_ERR_ARG; }
+  CHK(sloppy_check(c, 1));
+  HIPCHK(hipSetDevice(c->device));
+  DevField *fr[4], *fx[4];
+  for (int j = 0; j < n; j++) {
+    CHK(find_field(c, r_ids[j], &fr[j]));
+    CHK(find_field(c, x_ids[j], &fx[j]));
+  }
+  return f32_op_xx_batch_probe(c, n, fr, fx, m2, par_even);
+}
 // what the last batched sloppy call ran per system: n <- its systems; arrays of n_max entries, the first min(n, n_max) filled
 extern "C" int qexhip_stag_sloppy_last_batch(qexhip_handle c, int n_max, int *n, int *precision, int *half_iters, int *f32_iters,
                                              int *fell_back) {
@@ -1292,6 +1305,10 @@ extern "C" int qexhip_set_option(qexhip_handle c, const char *name, int value) {
     if (value != 0 && value != 1) { qexhip_set_error("option half_batch: 0 (SloppyHalf batches run single) or 1 (16-bit batches)"); return QEXHIP_ERR_ARG; }
     c->opt_half_batch = value;
   }
+  else if (n == "batch_ranks") {
+    if (value != 0 && value != 1) { qexhip_set_error("option batch_ranks: 0 (batched sloppy solves refuse t-sharded contexts) or 1 (they run there)"); return QEXHIP_ERR_ARG; }
+    c->opt_batch_ranks = value;
+  }
   else if (n == "half_stall") {
     if (value < 0) { qexhip_set_error("option half_stall: >= 0 failed reliable updates"); return QEXHIP_ERR_ARG; }
     c->opt_half_stall = value;
@@ -1336,7 +1353,8 @@ extern "C" int qexhip_stag_solve_batch(qexhip_handle c, int n, double *const *x,
   if (!c || !x || !b || !mass || !r2req) return QEXHIP_ERR_ARG;
   return solve_batch_host(c, n, x, b, mass, r2req, maxits, -1, 0, nullptr, 0, iters, r2_over_b2, nullptr);
 }
-// Mixed-precision lock-step batches.  sloppy = 0 IS the fp64 entry; the batched fp32 form is one-rank only (batch_sloppy_check).
+// Mixed-precision lock-step batches.  sloppy = 0 IS the fp64 entry; the batched mixed-precision forms run on one rank, and on t-sharded
+// contexts with option "batch_ranks" (batch_sloppy_check).
 extern "C" int qexhip_stag_solve_xx_batch_sloppy(qexhip_handle c, int n, double *const *x, const double *const *b, const double *mass,
                                                  const double *r2req, int maxits, int par_even, int sloppy, int *iters,
                                                  double *r2_over_b2, int *nupdates) {

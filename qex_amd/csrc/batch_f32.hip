@@ -9,7 +9,13 @@
 // in blockIdx.y and the single-system grid per system, and the reliable update runs the fp64 op_xx per system behind that system's `noupd` word.  A
 // system solved in a batch returns the bits -- solution, iterations, true residual, updates -- it returns alone.
 //
-// One rank, no ghost zones: t-sharded contexts are refused (the fp32 faces of all systems in one exchange are not built).
+// One rank without ghost zones by default: t-sharded contexts are refused unless option "batch_ranks" is 1.  With it the sweep takes its
+// HALO form (dslash_lowp.h: sweep_mrhs, all systems' faces in one exchange), every set of partials is summed over the ranks for all
+// systems in ONE collective per reduction point (comm_allreduce_parts_multi: each system's sum formed as comm_allreduce_parts forms it
+// alone) and the n states read back at the end of a chunk are checked for agreement per system (slp_agree) before any rank acts on
+// them.  "Alone" is then the single-system solve_xx_sloppy_dev on the same sharded context, sweep form and transport.  The INVARIANT
+// above slp_update holds per system: rank-global sums, hence the same flags on every rank; the host posts the same exchanges and
+// collectives on every rank whatever the flags say.
 #include "qexhip_internal.h"
 #include "site_index.h"
 #include "reduce.h"
@@ -140,9 +146,12 @@ __global__ void __launch_bounds__(256) k_slpb_rclose(SlpBatch B, int nparts) {
   }
 }
 
-// the bookkeeping launches for another file's iteration kernels (batch_half.hip): one rank
-int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts) {
-  k_slpb_close<<<n, 256, 0, c->stream>>>(L, nparts, SLP_DELTA * SLP_DELTA);
+// the bookkeeping launches, shared with another file's iteration kernels (batch_half.hip).  nparts |r_s|^2 partials per system in
+// L.r2p[j] = L.r2p[0] + j r2stride: summed over the ranks first (one collective for all systems; one rank: nothing)
+int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts, size_t r2stride) {
+  int nr2 = nparts;
+  CHK(comm_allreduce_parts_multi(c, n, L.r2p[0], r2stride, nparts, L.s, 1, &nr2));
+  k_slpb_close<<<n, 256, 0, c->stream>>>(L, nr2, SLP_DELTA * SLP_DELTA);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -151,9 +160,12 @@ int slpb_flush(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb) {
   HIPCHK(hipGetLastError());
   return 0;
 }
-int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb) {
+int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb, size_t r2stride) {
   k_slpb_resid<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
-  k_slpb_rclose<<<n, 256, 0, c->stream>>>(L, nbb);
+  HIPCHK(hipGetLastError());
+  int nr2 = nbb;
+  CHK(comm_allreduce_parts_multi(c, n, L.r2p[0], r2stride, nbb, L.s, 2, &nr2));     // (posted whether or not an update is due, as slp_resid's)
+  k_slpb_rclose<<<n, 256, 0, c->stream>>>(L, nr2);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -178,10 +190,22 @@ void batch_f32_state_free(qexhip_ctx *c) {
   c->batch_f32 = nullptr;
 }
 
+// all systems' <p,Ap> partials, nbd apart, then all systems' |r_s|^2 / |b - A x|^2 partials, nbb apart: one contiguous range per reduction point
+static int bf_partials(BatchF32State *S, int nbd, int nbb) {
+  const size_t need = ((size_t)nbd + nbb) * QX_MAXRHS;
+  if (S->npart < need) {
+    if (S->partials) HIPCHK(hipFree(S->partials));
+    S->partials = nullptr; S->npart = 0;
+    HIPCHK(hipMalloc((void **)&S->partials, need * sizeof(double)));
+    S->npart = need;
+  }
+  return 0;
+}
+
 // what every batched sloppy entry checks before anything is launched
 int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
-  if (c->nranks > 1 || c->g.halo) {
+  if ((c->nranks > 1 || c->g.halo) && !c->opt_batch_ranks) {
     qexhip_set_error("batched sloppy solve: t-sharded contexts (more than one rank, or ghost zones in t) are not supported -- the "
                      "sharded form is not built; use the fp64 batch or single-system sloppy solves there");
     return -1;
@@ -203,15 +227,9 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
   if (!S) { S = new BatchF32State(); c->batch_f32 = S; }
   if (!S->s) HIPCHK(hipMalloc((void **)&S->s, sizeof(SlpScal) * QX_MAXRHS));
   const size_t nvec = (size_t)g.ntile * 192;
-  const int nbd = (g.Vh + 255) / 256;                                          // <p,Ap> partials of a sweep (f32_op_xx's count)
+  const int nbd = (g.Vh + 255) / 256 + 4;                                      // room for a sweep's <p,Ap> partials (a split sweep rounds up per range)
   const int nbb = (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048));   // the k_slp_* grid (grid_for)
-  const size_t per = (size_t)nbd + nbb;
-  if (S->npart < per * QX_MAXRHS) {
-    if (S->partials) HIPCHK(hipFree(S->partials));
-    S->partials = nullptr; S->npart = 0;
-    HIPCHK(hipMalloc((void **)&S->partials, per * QX_MAXRHS * sizeof(double)));
-    S->npart = per * QX_MAXRHS;
-  }
+  CHK(bf_partials(S, nbd, nbb));
   DevField *w64[2 * QX_MAXRHS];
   CHK(batch_work_fields(c, 2 * QX_MAXRHS, w64));                             // r, A x per system
   const int par = par_even ? 0 : 1;
@@ -235,10 +253,10 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
     A1.in[j] = ps->par(par); A1.out[j] = t->par(1 - par);
     A2.in[j] = t->par(1 - par); A2.out[j] = aps->par(par); A2.xs[j] = ps->par(par);
     A2.cb[j] = (float)(4.0 * m2[j]);
-    A2.partials[j] = S->partials + per * j;
+    A2.partials[j] = S->partials + (size_t)nbd * j;
     L.x[j] = x[j]->par(par); L.r[j] = rj[j]->par(par); L.b[j] = b[j]->par(par); L.Ax[j] = axj[j]->par(par);
     L.rs[j] = rs->par(par); L.ps[j] = ps->par(par); L.xs[j] = xs->par(par); L.aps[j] = aps->par(par);
-    L.dotp[j] = S->partials + per * j; L.r2p[j] = S->partials + per * j + nbd;
+    L.dotp[j] = S->partials + (size_t)nbd * j; L.r2p[j] = S->partials + (size_t)nbd * QX_MAXRHS + (size_t)nbb * j;
   }
   L.s = S->s;
   CHK(mrhs_links(c, n, par, S->s, A1, A2, &fmt));
@@ -249,6 +267,8 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
     memcpy(h, c->pinned, sizeof(SlpScal) * n);
     return 0;
   };
+  // sharded: every rank holds the same n states before any of them acts on its copy (comm_allreduce_max takes four values: one call per system)
+  auto agree = [&]() -> int { for (int j = 0; j < n; j++) CHK(slp_agree(c, h[j])); return 0; };
   auto all_done = [&]() { for (int j = 0; j < n; j++) if (!h[j].done) return false; return true; };
   CHK(read_states());
   const int every = std::max(1, c->opt_sloppy_check);
@@ -260,31 +280,70 @@ int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, 
         ScopedTimer tm(c, "blas", c->stream);
         k_slpb_xpay<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
       }
+      int ndot = 0;
       CHK(sweep_mrhs(c, A1, fmt, false));
-      CHK(sweep_mrhs(c, A2, fmt, true));
+      CHK(sweep_mrhs(c, A2, fmt, true, &ndot));
+      CHK(comm_allreduce_parts_multi(c, n, L.dotp[0], nbd, ndot, L.s, 1, &ndot));
+      CHK(devjoin_flush(c));            // (no-op when the all-reduce has taken the second sweep's join with it)
       {
         ScopedTimer tm(c, "blas", c->stream);
-        k_slpb_update<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec, nbd);
+        k_slpb_update<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec, ndot);
       }
-      k_slpb_close<<<n, 256, 0, c->stream>>>(L, nbb, SLP_DELTA * SLP_DELTA);
       HIPCHK(hipGetLastError());
+      CHK(slpb_close(c, L, n, nbb, nbb));
       // the (device-gated) reliable update of every system whose `upd` is up, posted as solve_xx_sloppy_dev posts its own; a system
       // that is done counts no further, so the host's k is each live system's own k
       if ((k + 1) % every == 0 || k + 1 >= maxits) {
         k_slpb_flush<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
         HIPCHK(hipGetLastError());
         for (int j = 0; j < n; j++) CHK(op_xx(c, *axj[j], *x[j], m2[j], par_even, 0, &S->s[j].noupd));
-        k_slpb_resid<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
-        k_slpb_rclose<<<n, 256, 0, c->stream>>>(L, nbb);
-        HIPCHK(hipGetLastError());
+        CHK(slpb_resid(c, L, n, nvec, nbb, nbb));
       }
     }
     CHK(read_states());
+    CHK(agree());
   }
   for (int j = 0; j < n; j++) {
     if (iters) iters[j] = h[j].k;
     if (r2_over_b2) r2_over_b2[j] = (h[j].b2 != 0.0) ? h[j].r2t / h[j].b2 : 0.0;
     if (nupdates) nupdates[j] = h[j].nupd;
   }
+  return 0;
+}
+
+// fr_j[px] = the batched fp32 operator at m2_j on fx_j[px] rounded to fp32, back in fp64 (qexhip_dev_op_xx_sloppy_batch): the fp32 twin of
+// half_op_xx_batch_probe, on one rank and -- with option "batch_ranks" -- on t-sharded contexts
+int f32_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even) {
+  if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("dev_op_xx_sloppy_batch: 1 <= n <= %d", QX_MAXRHS); return -1; }
+  if ((c->nranks > 1 || c->g.halo) && !c->opt_batch_ranks) {
+    qexhip_set_error("the batched fp32 operator runs on one rank without ghost zones (t-sharded: option batch_ranks)");
+    return -1;
+  }
+  int fmt = 0;
+  CHK(f32_links(c, &fmt, nullptr));
+  BatchF32State *S = (BatchF32State *)c->batch_f32;
+  if (!S) { S = new BatchF32State(); c->batch_f32 = S; }
+  if (!S->s) HIPCHK(hipMalloc((void **)&S->s, sizeof(SlpScal) * QX_MAXRHS));
+  const int nbd = (c->g.Vh + 255) / 256 + 4;
+  const size_t nvec = (size_t)c->g.ntile * 192;
+  CHK(bf_partials(S, nbd, (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048))));
+  HIPCHK(hipMemsetAsync(S->s, 0, sizeof(SlpScal) * QX_MAXRHS, c->stream));       // every system live
+  const int px = par_even ? 0 : 1;
+  MrhsArgs<StoreF32> A1, A2;
+  memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2);
+  for (int j = 0; j < n; j++) {
+    DevFieldF *const fj = &S->f[BF_N * j];
+    for (int k = 0; k < BF_N; k++) CHK(f32_field_ensure(c, fj[k]));
+    CHK(f32_from_f64(c, fj[BF_P], *fx[j], px, 1.0));
+    A1.in[j] = fj[BF_P].par(px); A1.out[j] = fj[BF_T].par(1 - px);
+    A2.in[j] = fj[BF_T].par(1 - px); A2.out[j] = fj[BF_AP].par(px); A2.xs[j] = fj[BF_P].par(px);
+    A2.cb[j] = (float)(4.0 * m2[j]);
+    A2.partials[j] = S->partials + (size_t)nbd * j;
+  }
+  CHK(mrhs_links(c, n, px, S->s, A1, A2, &fmt));
+  CHK(sweep_mrhs(c, A1, fmt, false));
+  CHK(sweep_mrhs(c, A2, fmt, true));
+  CHK(devjoin_flush(c));
+  for (int j = 0; j < n; j++) CHK(f32_to_f64(c, *fr[j], S->f[BF_N * j + BF_AP], px, 1.0, 0));
   return 0;
 }

@@ -9,7 +9,10 @@
 // reliable update are the fp32 batch's (k_slpb_*, the gated fp64 op_xx per system), and the stall guard runs per system.  A system solved here returns the bits --
 // solution, iterations, true residual, updates, fall-back -- it returns from solve_xx_half_dev alone.
 //
-// One rank, no ghost zones.
+// One rank without ghost zones by default; with option "batch_ranks" on t-sharded contexts too, as batch_f32.hip describes: the HALO
+// sweep with all systems' 16-bit faces in one exchange, one collective per reduction point for all systems, and the n states with each
+// system's stall flag checked for agreement (slp_agree) at the end of every chunk.  The decision to enter half_finish_f32 -- itself
+// sharded, it posts collectives -- is taken for every system from that agreed state alone, on all ranks or on none.
 #include "qexhip_internal.h"
 #include "site_index.h"
 #include "reduce.h"
@@ -168,10 +171,11 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
   CHK(batch_sloppy_check(c, n, mass));
   CHK(half_links(c, nullptr, nullptr, nullptr, nullptr));
   const size_t nvec = (size_t)g.ntile * 192, nsites = nsite_h(c);
-  const int nbd = (g.Vh + 255) / 256;                                          // <p,Ap> partials of a sweep (sweep_half's count)
+  const int nbd = (g.Vh + 255) / 256 + 4;                                      // room for a sweep's <p,Ap> partials (a split sweep rounds up per range)
   const int nbh = grid_sites(nsites);                                          // the k_slph_* grid
   const int nbb = (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048));   // the fp64 k_slp_* grid (grid_for)
-  const size_t per = (size_t)nbd + std::max(nbh, nbb);
+  const size_t nbr = (size_t)std::max(nbh, nbb);                               // doubles between two systems' r2p
+  const size_t per = (size_t)nbd + nbr;                                        // (layout: all dotp, nbd apart, then all r2p, nbr apart)
   BatchHalfState *S;
   CHK(bh_state(c, n, per, &S));
   DevField *w64[2 * QX_MAXRHS];
@@ -198,12 +202,12 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
     A1.in[j] = ps->par(par); A1.out[j] = t->par(1 - par);
     A2.in[j] = t->par(1 - par); A2.out[j] = aps->par(par); A2.xs[j] = ps->par(par);
     A2.cb[j] = (float)(4.0 * m2[j]);
-    A2.partials[j] = S->partials + per * j;
+    A2.partials[j] = S->partials + (size_t)nbd * j;
     H.r[j] = rj[j]->par(par); H.rs[j] = rs->par(par); H.ps[j] = ps->par(par); H.aps[j] = aps->par(par); H.xs[j] = xs->par(par);
-    H.dotp[j] = S->partials + per * j; H.r2p[j] = S->partials + per * j + nbd;
+    H.dotp[j] = S->partials + (size_t)nbd * j; H.r2p[j] = S->partials + (size_t)nbd * QX_MAXRHS + nbr * j;
     L.x[j] = x[j]->par(par); L.r[j] = rj[j]->par(par); L.b[j] = b[j]->par(par); L.Ax[j] = axj[j]->par(par);
     L.xs[j] = xs->par(par);
-    L.dotp[j] = S->partials + per * j; L.r2p[j] = S->partials + per * j + nbd;
+    L.dotp[j] = S->partials + (size_t)nbd * j; L.r2p[j] = H.r2p[j];
   }
   H.s = S->s; L.s = S->s;
   k_slphb_stall_init<<<1, 64, 0, c->stream>>>(S->stall, S->s, n);
@@ -211,12 +215,19 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
   int fmt = 0;
   CHK(mrhs_links(c, n, par, S->s, A1, A2, &fmt));
   SlpScal h[QX_MAXRHS];
+  HalfStall hs[QX_MAXRHS];
+  static_assert(sizeof(SlpScal) * QX_MAXRHS <= 2048 && sizeof(HalfStall) * QX_MAXRHS <= 2048, "pinned scratch layout");
+  HalfStall *const pstall = (HalfStall *)((char *)c->pinned + 2048);     // (behind the SlpScal's)
   auto read_states = [&]() -> int {
     HIPCHK(hipMemcpyAsync(c->pinned, S->s, sizeof(SlpScal) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pstall, S->stall, sizeof(HalfStall) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(h, c->pinned, sizeof(SlpScal) * n);
+    memcpy(hs, pstall, sizeof(HalfStall) * n);
     return 0;
   };
+  // sharded: every rank holds the same n states and stall flags before any of them acts on its copy (one call per system)
+  auto agree = [&]() -> int { for (int j = 0; j < n; j++) CHK(slp_agree(c, h[j], hs[j].stalled)); return 0; };
   auto all_done = [&]() { for (int j = 0; j < n; j++) if (!h[j].done) return false; return true; };
   CHK(read_states());
   const int every = std::max(1, c->opt_sloppy_check);
@@ -228,28 +239,30 @@ int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, co
         ScopedTimer tm(c, "blas", c->stream);
         k_slphb_xpay<<<dim3(nbh, n), 256, 0, c->stream>>>(H, nsites);
       }
+      int ndot = 0;
       CHK(sweep_mrhs(c, A1, fmt, false));
-      CHK(sweep_mrhs(c, A2, fmt, true));
+      CHK(sweep_mrhs(c, A2, fmt, true, &ndot));
+      CHK(comm_allreduce_parts_multi(c, n, L.dotp[0], nbd, ndot, L.s, 1, &ndot));
+      CHK(devjoin_flush(c));            // (no-op when the all-reduce has taken the second sweep's join with it)
       {
         ScopedTimer tm(c, "blas", c->stream);
-        k_slphb_update<<<dim3(nbh, n), 256, 0, c->stream>>>(H, nsites, nbd);
+        k_slphb_update<<<dim3(nbh, n), 256, 0, c->stream>>>(H, nsites, ndot);
       }
       HIPCHK(hipGetLastError());
-      CHK(slpb_close(c, L, n, nbh));
+      CHK(slpb_close(c, L, n, nbh, nbr));
       // the (device-gated) reliable update of every system whose `upd` is up, and each system's stall guard behind it; a system that is
       // done counts no further, so the host's k is each live system's own k
       if ((k + 1) % every == 0 || k + 1 >= maxits) {
         CHK(slpb_flush(c, L, n, nvec, nbb));
         for (int j = 0; j < n; j++) CHK(op_xx(c, *axj[j], *x[j], m2[j], par_even, 0, &S->s[j].noupd));
-        CHK(slpb_resid(c, L, n, nvec, nbb));
+        CHK(slpb_resid(c, L, n, nvec, nbb, nbr));
         k_slphb_stall<<<1, 64, 0, c->stream>>>(S->stall, S->s, n, c->opt_half_stall);
         HIPCHK(hipGetLastError());
       }
     }
     CHK(read_states());
+    CHK(agree());
   }
-  HalfStall hs[QX_MAXRHS];
-  HIPCHK(hipMemcpy(hs, S->stall, sizeof(HalfStall) * n, hipMemcpyDeviceToHost));
   for (int j = 0; j < n; j++) {
     int its = h[j].k, nupd = h[j].nupd, its32 = 0, fell = 0;
     double r2t = h[j].r2t;
@@ -280,7 +293,7 @@ void slpb_last_reset(qexhip_ctx *c, int n) {
 
 int solve_xx_batch_sloppy_any(qexhip_ctx *c, int sloppy, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                               int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates) {
-  if (sloppy == 2 && c->opt_half_batch && c->nranks == 1 && !c->g.halo)
+  if (sloppy == 2 && c->opt_half_batch && ((c->nranks == 1 && !c->g.halo) || c->opt_batch_ranks))
     return solve_xx_batch_half_dev(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
   int its[QX_MAXRHS] = {0, 0, 0, 0};
   CHK(solve_xx_batch_sloppy_dev(c, n, x, b, mass, r2req, maxits, par_even, its, r2_over_b2, nupdates));
@@ -296,9 +309,9 @@ int solve_xx_batch_sloppy_any(qexhip_ctx *c, int sloppy, int n, DevField **x, De
 // fr_j[px] = the batched 16-bit operator at m2_j on fx_j[px] rounded to 16 bits, back in fp64 (qexhip_dev_op_xx_half_batch)
 int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("dev_op_xx_half_batch: 1 <= n <= %d", QX_MAXRHS); return -1; }
-  if (c->nranks > 1 || c->g.halo) { qexhip_set_error("the 16-bit operator runs on one rank without ghost zones"); return -1; }
+  if ((c->nranks > 1 || c->g.halo) && !c->opt_batch_ranks) { qexhip_set_error("the 16-bit operator runs on one rank without ghost zones"); return -1; }
   CHK(half_links(c, nullptr, nullptr, nullptr, nullptr));
-  const int nbd = (c->g.Vh + 255) / 256;
+  const int nbd = (c->g.Vh + 255) / 256 + 4;
   const size_t nvec = (size_t)c->g.ntile * 192;
   const int nbb = (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048));
   const size_t per = (size_t)nbd + std::max(grid_sites(nsite_h(c)), nbb);
@@ -314,12 +327,13 @@ int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, c
     A1.in[j] = fj[BH_P].par(px); A1.out[j] = fj[BH_T].par(1 - px);
     A2.in[j] = fj[BH_T].par(1 - px); A2.out[j] = fj[BH_AP].par(px); A2.xs[j] = fj[BH_P].par(px);
     A2.cb[j] = (float)(4.0 * m2[j]);
-    A2.partials[j] = S->partials + per * j;
+    A2.partials[j] = S->partials + (size_t)nbd * j;
   }
   int fmt = 0;
   CHK(mrhs_links(c, n, px, S->s, A1, A2, &fmt));
   CHK(sweep_mrhs(c, A1, fmt, false));
   CHK(sweep_mrhs(c, A2, fmt, true));
+  CHK(devjoin_flush(c));
   for (int j = 0; j < n; j++) CHK(half_to_f64(c, fr[j]->par(px), S->f[BH_N * j + BH_AP].par(px)));
   return 0;
 }

@@ -370,6 +370,55 @@ int comm_halo_exchange_multi(qexhip_ctx *c, int n, DevField *const *f, int parit
   return 0;
 }
 
+// The reduced-precision parity halves of the n systems of a mixed-precision lock-step batch (dslash_lowp.h: sweep_mrhs) in ONE RCCL group
+// or ONE peer exchange with n buffers per direction (no communicator: n pairs of wrap copies): per half the messages of
+// comm_halo_exchange_sites, halves in ascending order on every rank -- the message order of comm_halo_exchange_multi.  The emulated
+// transport delay sees the true byte count n depth F site_bytes.  n is the batch's nrhs on every rank, whatever its systems' `done` words say.
+int comm_halo_exchange_sites_multi(qexhip_ctx *c, int n, void *const *halves, size_t site_bytes, int overlap) {
+  CHK(need_comm(c));
+  if (n < 1 || n > 4) { qexhip_set_error("internal: face exchange of %d reduced-precision halves", n); return QEXHIP_ERR_ARG; }
+  hipStream_t cs = overlap ? c->cstream : c->stream;
+  const Geom &g = c->g;
+  const size_t bytes = (size_t)g.depth * g.F * site_bytes;       // per face
+  const size_t ghost_off = (size_t)g.ntile * 64 * site_bytes;
+  const ncclDataType_t type = site_bytes == 24 ? ncclFloat : ncclUint32;
+  const size_t nd = bytes / 4;
+  if (overlap) HIPCHK(hipStreamWaitEvent(c->cstream, c->ev_ready, 0));
+  ScopedTimer tm(c, "exchange", cs);
+  CHK(emu_exchange(c, cs, (size_t)n * bytes));
+  if (peer_faces(c)) {
+    const void *dn[4], *up[4];
+    void *from_up[4], *from_dn[4];
+    for (int j = 0; j < n; j++) {
+      char *base = (char *)halves[j];
+      dn[j] = base; up[j] = base + ghost_off - bytes;
+      from_up[j] = base + ghost_off; from_dn[j] = base + ghost_off + bytes;
+    }
+    CHK(peer_exchange(c, cs, n, dn, n, up, from_up, from_dn, bytes, emu_exchange_time(c, (size_t)n * bytes)));
+  } else if (c->comm) {
+    ncclComm_t comm = (ncclComm_t)((overlap && c->comm2) ? c->comm2 : c->comm);
+    NCCLCHK(ncclGroupStart());
+    for (int j = 0; j < n; j++) {
+      char *base = (char *)halves[j];
+      NCCLCHK(ncclSend(base, nd, type, lower(c), comm, cs));
+      NCCLCHK(ncclSend(base + ghost_off - bytes, nd, type, upper(c), comm, cs));
+    }
+    for (int j = 0; j < n; j++) {
+      char *ghost_hi = (char *)halves[j] + ghost_off;
+      NCCLCHK(ncclRecv(ghost_hi, nd, type, upper(c), comm, cs));
+      NCCLCHK(ncclRecv(ghost_hi + bytes, nd, type, lower(c), comm, cs));
+    }
+    NCCLCHK(ncclGroupEnd());
+  } else {
+    for (int j = 0; j < n; j++) {
+      char *base = (char *)halves[j], *ghost_hi = base + ghost_off;
+      HIPCHK(hipMemcpyAsync(ghost_hi, base, bytes, hipMemcpyDeviceToDevice, cs));
+      HIPCHK(hipMemcpyAsync(ghost_hi + bytes, base + ghost_off - bytes, bytes, hipMemcpyDeviceToDevice, cs));
+    }
+  }
+  return 0;
+}
+
 // send `bytes` to the upper neighbour, receive the same amount from the lower one (stream-ordered)
 int comm_exchange_raw(qexhip_ctx *c, const void *send_up, void *recv_from_down, size_t bytes, hipStream_t st) {
   CHK(need_comm(c));
@@ -459,6 +508,27 @@ int comm_allreduce_parts(qexhip_ctx *c, double *parts, int n, int *n_out) {
   ScopedTimer tm(c, "allreduce", c->stream);
   *n_out = 1;
   return peer_allreduce_parts(c, parts, n);
+}
+
+// comm_allreduce_parts for the m systems of a lock-step batch in ONE collective: system j's partials are parts[j][0..n), and the ranges
+// lie `stride` doubles apart (parts[j] = parts[0] + j stride).  Every system's sum is formed exactly as comm_allreduce_parts forms it for
+// that system alone, so the consumer sees the bits of the single-system solve:
+//   RCCL  the partial vectors are all-reduced elementwise in place, one all-reduce over [parts[0], parts[m-1] + n), *n_out = n
+//   peer  one single-workgroup launch sums every system's vector in cg_sum_parts order to one operand, the m operands cross the mailboxes
+//         in one set of tagged words and the rank-ordered totals land in parts[j][0], *n_out = 1; the deferred join of a split sweep
+//         rides in its prologue
+// gate (peer): 1 leaves out the systems that are done, 2 those without a pending reliable update (what their consumers skip) -- a system's
+// stale partials never enter a sum.  RCCL reduces stale ranges in place with the rest; they grow by the factor nranks per collective and
+// NOTHING reads them: every consumer (k_slpb_update, k_slpb_close, k_slpb_rclose and their 16-bit forms) tests the same flags first, and
+// a live system's producer rewrites its whole range ahead of the collective.  Posted whatever the flags say: same collectives on every rank.
+int comm_allreduce_parts_multi(qexhip_ctx *c, int m, double *parts0, size_t stride, int n, const SlpScal *st, int gate, int *n_out) {
+  *n_out = n;
+  CHK(need_comm(c));
+  if (!multi_rank(c) || !comm_ready(c) || n <= 0) return devjoin_flush(c);
+  if (!c->peer) { CHK(devjoin_flush(c)); return comm_allreduce(c, parts0, (int)(stride * (size_t)(m - 1)) + n); }
+  ScopedTimer tm(c, "allreduce", c->stream);
+  *n_out = 1;
+  return peer_allreduce_parts_multi(c, m, parts0, stride, n, st, gate);
 }
 
 int comm_allreduce_max(qexhip_ctx *c, double *host, int n) {

@@ -14,6 +14,8 @@
 //   HALO = false  the whole lattice on one GPU (t-hops wrap)
 //   HALO = true   a t-sharded slab (or a one-rank context with a halo): t-hops that leave the slab read the ghost zones (nbr_pos<true>),
 //                 over the site range [c0,c1) plus [d0,d1) for workgroups >= nb1 (both faces in one launch), as k_dslash<.., HALO, ..>.
+//                 Both kernels have it; the lock-step one writes each system's partials from a per-launch offset, and its host sweep
+//                 (sweep_mrhs) runs on such a context under option "batch_ranks" only.
 // Every site runs the same operations in the same order whatever HALO is and whether it is alone or one of a batch -- only the positions
 // its t-hops read differ --, because there is one body: a slab's output is the one-rank operator's bits site for site, and a system
 // solved in a batch returns the bits it returns alone.
@@ -47,7 +49,8 @@ struct StoreF32 {
   using LinkBase = f4v;
   template <int NDIR, int RECON> using Cursor = LinkCursorF<NDIR, RECON>;
   static constexpr size_t WIRE = 3 * sizeof(float2);     // bytes per site in a face exchange
-  static constexpr const char *T_SWEEP = "dslash_f32", *T_BND = "dslash_f32_bnd", *T_BATCH = "dslash_batch_f32";
+  static constexpr const char *T_SWEEP = "dslash_f32", *T_BND = "dslash_f32_bnd", *T_BATCH = "dslash_batch_f32",
+                              *T_BATCH_BND = "dslash_batch_f32_bnd";
   static constexpr int NK = 3;                           // an access (read, take) is one colour
   struct Scales {};                                      // no hop scales: nothing in the kernel arguments, nothing in the code
   struct Nbr {};                                         // nothing is in flight across the link fetch
@@ -80,7 +83,8 @@ struct StoreHalf {
   using LinkBase = void;
   template <int NDIR, int RECON> using Cursor = LinkCursorH<NDIR, RECON>;
   static constexpr size_t WIRE = sizeof(u4v);
-  static constexpr const char *T_SWEEP = "dslash_half", *T_BND = "dslash_half_bnd", *T_BATCH = "dslash_batch_half";
+  static constexpr const char *T_SWEEP = "dslash_half", *T_BND = "dslash_half_bnd", *T_BATCH = "dslash_batch_half",
+                              *T_BATCH_BND = "dslash_batch_half_bnd";
   static constexpr int NK = 1;                           // an access is the whole site
   struct Scales { float s_fat, s_long; };                // format 0: the largest |entry| of the fat / long links
   using Nbr = u4v;                                       // a neighbour's element, loaded ahead of the link fetch
@@ -307,21 +311,35 @@ struct MrhsArgs {
   int parity, nrhs;
 };
 
+template <class St>
+struct MrhsHaloArgs {              // (a type of its own, as SweepHaloArgs: the HALO = false kernels keep their kernel arguments and code)
+  MrhsArgs<St> a;
+  SweepRanges r;
+  int part_off;                    // this launch's first <xs,out> partial of every system
+};
+template <class St, bool HALO> using MrhsKernelArgs = std::conditional_t<HALO, MrhsHaloArgs<St>, MrhsArgs<St>>;
+template <class St> __device__ __forceinline__ const MrhsArgs<St> &mrhs_args(const MrhsArgs<St> &P) { return P; }
+template <class St> __device__ __forceinline__ const MrhsArgs<St> &mrhs_args(const MrhsHaloArgs<St> &P) { return P.a; }
+
 // k_dslash_lowp's body per system, the links of a hop pair fetched once and applied to every live system:
 // SECOND = false: out_j = +sum_mu (U in_j(+mu) - U^+ in_j(-mu))              (INIT = false, DOT = false, sgn = +1)
 // SECOND = true : out_j = cb_j xs_j - sum_mu (...), partial <xs_j, out_j>   (INIT = true,  DOT = true,  sgn = -1)
 // with the single-system workgroup partition and the same fixed-order sums.  All systems' neighbours are issued ahead of the link fetch.
-template <class St, int NDIR, int RECON, bool SECOND>
-__global__ void __launch_bounds__(256) k_dslash_mrhs_lowp(MrhsArgs<St> A) {
+// HALO: k_dslash_lowp's -- the site ranges of sweep_site, t-hops through nbr_pos<true>, every system's partials from part_off on, so that
+// a split sweep lays them out per system as sweep_lowp does for one: interior, low face, high face.
+template <class St, int NDIR, int RECON, bool SECOND, bool HALO>
+__global__ void __launch_bounds__(256) k_dslash_mrhs_lowp(MrhsKernelArgs<St, HALO> P) {
+  const MrhsArgs<St> &A = mrhs_args(P);
   bool act[QX_MAXRHS];
   bool any = false;
 #pragma unroll
   for (int j = 0; j < QX_MAXRHS; j++) { act[j] = j < A.nrhs && !A.st[j].done; any = any || act[j]; }
   if (!any) return;
   const Geom &g = A.g;
-  const int c = blockIdx.x * 256 + threadIdx.x;
+  int c = blockIdx.x * 256 + threadIdx.x, clim = g.Vh;
+  if constexpr (HALO) sweep_site(P.r, blockIdx.x, c, clim);
   double dotv[QX_MAXRHS] = {0, 0, 0, 0};
-  if (c < g.Vh) {
+  if (c < clim) {
     const SiteXYZT s = site_coord(g, c, A.parity);
     const typename St::template Cursor<NDIR, RECON> L(A.W, A.S, c);
     const float sgn = SECOND ? -1.f : 1.f;
@@ -342,8 +360,8 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_lowp(MrhsArgs<St> A) {
     for (int pr = 0; pr < NDIR / 2; pr++) {
       const int mu = pr & 3;
       const int hop = pr >= 4 ? 3 : 1;
-      const int pf = nbr_pos<false>(g, c, s, mu, hop);
-      const int pb = nbr_pos<false>(g, c, s, mu, -hop);
+      const int pf = nbr_pos<HALO>(g, c, s, mu, hop);
+      const int pb = nbr_pos<HALO>(g, c, s, mu, -hop);
       typename St::Nbr hf[QX_MAXRHS], hb[QX_MAXRHS];
 #pragma unroll
       for (int j = 0; j < QX_MAXRHS; j++) {
@@ -382,7 +400,8 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_lowp(MrhsArgs<St> A) {
     for (int j = 0; j < QX_MAXRHS; j++) {
       if (!act[j]) continue;             // uniform over the grid
       const double r = block_sum_256(dotv[j]);
-      if (threadIdx.x == 0) A.partials[j][blockIdx.x] = r;
+      if constexpr (HALO) { if (threadIdx.x == 0) A.partials[j][P.part_off + blockIdx.x] = r; }
+      else { if (threadIdx.x == 0) A.partials[j][blockIdx.x] = r; }
     }
   }
 }
@@ -390,7 +409,7 @@ __global__ void __launch_bounds__(256) k_dslash_mrhs_lowp(MrhsArgs<St> A) {
 // the links of both sweeps of op_xx on parity px for n systems with states st (A1: the other parity's links, A2: px's); *fmt <- their format
 template <class St>
 static int mrhs_links(qexhip_ctx *c, int n, int px, const SlpScal *st, MrhsArgs<St> &A1, MrhsArgs<St> &A2, int *fmt) {
-  if (c->g.halo) { qexhip_set_error("internal: lock-step sweep on a lattice with ghost zones"); return -3; }
+  if (c->g.halo && !c->opt_batch_ranks) { qexhip_set_error("internal: lock-step sweep on a lattice with ghost zones"); return -3; }
   for (MrhsArgs<St> *A : {&A1, &A2}) {
     A->g = c->g; A->st = st; A->nrhs = n; A->parity = (A == &A1) ? 1 - px : px;
     CHK(St::links(c, A->parity, &A->W, &A->S, &A->q, fmt));
@@ -398,16 +417,63 @@ static int mrhs_links(qexhip_ctx *c, int n, int px, const SlpScal *st, MrhsArgs<
   return 0;
 }
 
-template <class St>
-static int sweep_mrhs(qexhip_ctx *c, const MrhsArgs<St> &A, int fmt, bool second) {
-  const dim3 grid((c->g.Vh + 255) / 256), block(256);
-  c->bnd_out_on_cstream = nullptr;
-  ScopedTimer tm(c, St::T_BATCH, c->stream);
+// One launch on stream st, every system's dot partials from A.partials[j] + part_off.  HALO: over [c0,c1) (+ [d0,d1) behind it), nothing
+// where both are empty; else over all sites.
+template <class St, bool HALO>
+static int launch_mrhs(qexhip_ctx *c, int fmt, const MrhsArgs<St> &A, bool second, int c0, int c1, int d0, int d1, int part_off,
+                       const char *tname, hipStream_t st) {
+  MrhsKernelArgs<St, HALO> P;
+  memset(&P, 0, sizeof P);
+  int nb = (c->g.Vh + 255) / 256;
+  if constexpr (HALO) {
+    nb = sweep_ranges(P.r, c0, c1, d0, d1);
+    if (!nb) return 0;
+    P.a = A;
+    P.part_off = part_off;
+  } else {
+    P = A;
+  }
+  const dim3 grid(nb), block(256);
+  ScopedTimer tm(c, tname, st);
   with_ndir_recon(c->ndir, fmt, [&](auto nd, auto rc) {
     constexpr int ND = decltype(nd)::value, R = decltype(rc)::value;
-    if (second) hipLaunchKernelGGL((k_dslash_mrhs_lowp<St, ND, R, true>), grid, block, 0, c->stream, A);
-    else hipLaunchKernelGGL((k_dslash_mrhs_lowp<St, ND, R, false>), grid, block, 0, c->stream, A);
+    if (second) hipLaunchKernelGGL((k_dslash_mrhs_lowp<St, ND, R, true, HALO>), grid, block, 0, st, P);
+    else hipLaunchKernelGGL((k_dslash_mrhs_lowp<St, ND, R, false, HALO>), grid, block, 0, st, P);
   });
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// One lock-step sweep; *nparts <- how many <xs,out> partials it left per system (second).  With g.halo (option "batch_ranks"), in the two
+// forms of sweep_lowp, chosen by the same sweep_plan: exchange-first (all systems' faces in ONE exchange on the compute stream, one
+// launch over the slab with the one-rank workgroup partition) or split by sites (the exchange and both faces' launch on the comm stream,
+// the interior launch on the compute stream, device-side join).  There is no fused form: where sweep_form picks it, the sweep is split by
+// sites.  The faces of ALL nrhs systems travel every sweep, done or not: `done` lives on the device and the number of messages a rank
+// posts must not depend on it.  second: the caller's next operation on the compute stream is comm_allreduce_parts_multi, which takes the
+// join of a split sweep with it where the mailboxes carry the sums.
+template <class St>
+static int sweep_mrhs(qexhip_ctx *c, const MrhsArgs<St> &A, int fmt, bool second, int *nparts = nullptr) {
+  const Geom &g = c->g;
+  c->bnd_out_on_cstream = nullptr;
+  if (nparts) *nparts = (g.Vh + 255) / 256;
+  if (!g.halo) return launch_mrhs<St, false>(c, fmt, A, second, 0, 0, 0, 0, 0, St::T_BATCH, c->stream);
+  void *halves[QX_MAXRHS];
+  for (int j = 0; j < A.nrhs; j++) halves[j] = const_cast<typename St::Elem *>(A.in[j]);
+  int lo_end, hi_beg, overlap;
+  sweep_plan(c, &lo_end, &hi_beg, &overlap);
+  CHK(devjoin_flush(c));
+  if (!overlap) {
+    CHK(comm_halo_exchange_sites_multi(c, A.nrhs, halves, St::WIRE, 0));
+    return launch_mrhs<St, true>(c, fmt, A, second, 0, g.Vh, 0, 0, 0, St::T_BATCH, c->stream);
+  }
+  const int nb_int = (hi_beg - lo_end + 255) / 256, nb_lo = (lo_end + 255) / 256, nb_hi = (g.Vh - hi_beg + 255) / 256;
+  HIPCHK(hipEventRecord(c->ev_ready, c->stream));
+  CHK(comm_halo_exchange_sites_multi(c, A.nrhs, halves, St::WIRE, 1));
+  CHK((launch_mrhs<St, true>(c, fmt, A, second, lo_end, hi_beg, 0, 0, 0, St::T_BATCH, c->stream)));
+  CHK((launch_mrhs<St, true>(c, fmt, A, second, 0, lo_end, hi_beg, g.Vh, nb_int, St::T_BATCH_BND, c->cstream)));
+  CHK(devjoin_signal(c, c->cstream));
+  if (second && c->peer) CHK(devjoin_defer(c));
+  else CHK(devjoin_wait(c, c->stream, c->cstream));
+  if (nparts) *nparts = nb_int + nb_lo + nb_hi;
   return 0;
 }

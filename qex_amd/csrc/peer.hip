@@ -267,6 +267,54 @@ __global__ void __launch_bounds__(256) k_peer_allreduce_small(double *x, int n, 
   }
 }
 
+// k_peer_allreduce_small<0, true> for the m <= 4 systems of a lock-step batch (comm_allreduce_parts_multi): system j's operand is the sum
+// of x[j stride + 0..nparts) in cg_sum_parts order, value j of the tagged words (they carry up to PEER_GRAN_N doubles); the rank-ordered
+// total goes to x[j stride].  A gated system (gate 1: done; gate 2: done or no update pending -- the test of its consumer) sends 0 and
+// keeps its words: the messages do not depend on the flags, the sums of the others are theirs alone.
+__global__ void __launch_bounds__(256) k_peer_allreduce_parts_multi(double *x, int m, size_t stride, int nparts, const SlpScal *st, int gate,
+                                                                    const PeerGran G, u64 seq, const u64 *join, u64 joinval) {
+  __shared__ double val[PEER_MAXR * PEER_GRAN_N];
+  __shared__ double local[4];
+  __shared__ int ok;
+  if (threadIdx.x == 0) ok = 1;
+  if (join) {
+    if (threadIdx.x == 0) {
+      if (!peer_poll_ge(join, joinval, G.err, G.ticks, 0x400)) ok = 0;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (!ok) return;
+  }
+  const long long t_start = G.emu_ticks > 0 ? wall_clock64() : 0;
+  auto live = [&](int j) { return !(st && gate && (st[j].done || (gate == 2 && !st[j].upd))); };
+  for (int j = 0; j < m; j++) {
+    const double v = live(j) ? cg_sum_parts(x + (size_t)j * stride, nparts) : 0.0;     // (the test is uniform over the workgroup)
+    if (threadIdx.x == 0) local[j] = v;
+  }
+  const int slot = (int)(seq & (PEER_NSLOT - 1));
+  const unsigned tag = (unsigned)seq;
+  __syncthreads();
+  const int r = threadIdx.x / PEER_GRAN_N, i = threadIdx.x % PEER_GRAN_N;
+  for (int rr = r; rr < G.nranks; rr += 256 / PEER_GRAN_N)
+    if (i < m) gran_send(G.gran[rr] + ((size_t)(slot * PEER_MAXR + G.me) * PEER_GRAN_N + i) * 2, local[i], tag);
+  if (G.emu_ticks > 0) while (wall_clock64() - t_start < G.emu_ticks) __builtin_amdgcn_s_sleep(2);
+  for (int rr = r; rr < G.nranks; rr += 256 / PEER_GRAN_N) {
+    if (i < m) {
+      double v = 0;
+      if (!gran_recv(G.gran[G.me] + ((size_t)(slot * PEER_MAXR + rr) * PEER_GRAN_N + i) * 2, tag, &v, G.err, G.ticks, 0x300 + rr)) ok = 0;
+      val[rr * PEER_GRAN_N + i] = v;
+    }
+  }
+  __syncthreads();
+  if (!ok) return;
+  if ((int)threadIdx.x < m && live((int)threadIdx.x)) {
+    double acc = val[threadIdx.x];
+    for (int q = 1; q < G.nranks; q++) acc += val[q * PEER_GRAN_N + threadIdx.x];
+    x[(size_t)threadIdx.x * stride] = acc;
+  }
+}
+
 // ---------------- host side ----------------
 static u64 *ctrl_word(char *ctrl, int w) { return (u64 *)ctrl + w; }
 
@@ -583,6 +631,21 @@ int peer_allreduce_parts(qexhip_ctx *c, double *parts, int n) {
   const u64 *join = c->dj.deferred ? c->dj.ready + 16 : nullptr;      // the deferred join from the comm stream rides in this kernel's prologue
   c->dj.deferred = 0;
   hipLaunchKernelGGL((k_peer_allreduce_small<0, true>), dim3(1), dim3(256), 0, c->stream, parts, 1, n, G, ++p->seq_red, join, c->dj.seq[1]);
+  p->allreduces++;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int peer_allreduce_parts_multi(qexhip_ctx *c, int m, double *parts0, size_t stride, int n, const SlpScal *st, int gate) {
+  PeerComm *p = c->peer;
+  CHK(peer_check_err(c));
+  if (m < 1 || m > 4) { qexhip_set_error("internal: partial sums of %d systems", m); return QEXHIP_ERR_ARG; }
+  PeerGran G;
+  fill_gran(p, G);
+  G.emu_ticks = (long long)(c->emu_allreduce_us * 1e-6 * (double)p->ticks / p->timeout_s);
+  const u64 *join = c->dj.deferred ? c->dj.ready + 16 : nullptr;      // the deferred join from the comm stream rides in this kernel's prologue
+  c->dj.deferred = 0;
+  hipLaunchKernelGGL(k_peer_allreduce_parts_multi, dim3(1), dim3(256), 0, c->stream, parts0, m, stride, n, st, gate, G, ++p->seq_red, join, c->dj.seq[1]);
   p->allreduces++;
   HIPCHK(hipGetLastError());
   return 0;

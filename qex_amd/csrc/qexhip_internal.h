@@ -267,6 +267,8 @@ struct qexhip_ctx {
   // the last batched sloppy call per system (qexhip_stag_sloppy_last_batch); map: system of the entry <- system of the inner batch
   struct { int n = 0, precision[4] = {0, 0, 0, 0}, half_iters[4] = {0, 0, 0, 0}, f32_iters[4] = {0, 0, 0, 0}, fell_back[4] = {0, 0, 0, 0},
            map[4] = {0, 1, 2, 3}; } slpb_last;
+  int opt_batch_ranks = 0;                           // option "batch_ranks": 1 = the batched sloppy entries run on t-sharded contexts (more than one rank, or
+                                                     // ghost zones in t); 0 = they refuse there.  Set on every rank
   int opt_sloppy_check = 4;                          // option "sloppy_check": the gated reliable-update launches are posted every this many fp32
                                                      // iterations (solver.cpp: solve_xx_sloppy_dev)
 };
@@ -319,7 +321,7 @@ int solve_xx_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const d
                        int maxits, int par_even, int *iters, double *r2_over_b2);      // n (1..4) solveXX's in lock-step, fp64
 // ---- batch_f32.hip: the mixed-precision lock-step batch (one rank, no ghost zones) ----
 void batch_f32_state_free(qexhip_ctx *c);
-int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass);     // n in 1..4, not t-sharded, no mass 0 -- before anything is launched
+int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass);     // n in 1..4, not t-sharded unless option batch_ranks, no mass 0 -- before anything is launched
 int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                               int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
 int solve_full_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
@@ -334,9 +336,9 @@ struct SlpBatch {
   SlpScal *s;
 };
 // k_slpb_close / k_slpb_flush / k_slpb_resid + k_slpb_rclose for n systems, for the 16-bit batch (nvec, nbb: the fp32 batch's BLAS size and grid)
-int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts);
+int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts, size_t r2stride);      // (r2stride: doubles between two systems' r2p)
 int slpb_flush(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb);
-int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb);
+int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb, size_t r2stride);
 
 // ---- batch_half.hip: the 16-bit lock-step batch (option "half_batch") ----
 void batch_half_state_free(qexhip_ctx *c);
@@ -348,6 +350,7 @@ int solve_xx_batch_sloppy_any(qexhip_ctx *c, int sloppy, int n, DevField **x, De
                               int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
 void slpb_last_reset(qexhip_ctx *c, int n);             // the batched entries start a new report
 int half_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even);
+int f32_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even);     // (batch_f32.hip)
 int nhyp_fforce(qexhip_ctx *c, double *f_host, int n, const double *const *phi, const double *mass, const double *scale,
                 const double *r2req, int maxits, int bcmask, const int ph[4], int *iters, DevField *const *phi_dev = nullptr);
 
@@ -362,8 +365,11 @@ int comm_halo_exchange(qexhip_ctx *c, DevField &f, int parity, int overlap, bool
                                                                               // the caller joins behind what it posts next
 int comm_halo_exchange_sites(qexhip_ctx *c, void *half, size_t site_bytes, int overlap);  // the same for one parity half of an fp32 (24 B per site) or 16-bit (16 B) field
 int comm_halo_exchange_multi(qexhip_ctx *c, int n, DevField *const *f, int parity, int overlap);   // n fields, one RCCL group
+int comm_halo_exchange_sites_multi(qexhip_ctx *c, int n, void *const *halves, size_t site_bytes, int overlap);   // n (<= 4) reduced-precision parity halves, one group
 int comm_allreduce(qexhip_ctx *c, double *dptr, int n);          // on stream
 int comm_allreduce_parts(qexhip_ctx *c, double *parts, int n, int *n_out);   // workgroup partials -> *n_out values whose sum is the rank-global dot product
+// the same for m (<= 4) systems' partials parts0 + j stride in ONE collective, each system summed as alone; gate: see comm.cpp
+int comm_allreduce_parts_multi(qexhip_ctx *c, int m, double *parts0, size_t stride, int n, const SlpScal *st, int gate, int *n_out);
 int comm_allreduce_max(qexhip_ctx *c, double *host, int n);      // host values -> max over the ranks, back on the host (n <= 4, synchronous)
 int comm_agree_post(qexhip_ctx *c);                               // max-reduce c->cg->agree over the ranks (on stream)
 int comm_agree_check(qexhip_ctx *c, const CgScal &host);          // after the state was read back: all ranks hold the same residual and count
@@ -393,6 +399,7 @@ int peer_exchange(qexhip_ctx *c, hipStream_t st, int ns_dn, const void *const *s
                   const void **zc_from_dn = nullptr, struct PeerPush *push_only = nullptr);   // push_only (+ zc_*): nothing is launched, the caller's kernel
                                                                                               // pushes and reads the arena (credits owed: peer_ghost_args)
 int peer_allreduce_parts(qexhip_ctx *c, double *parts, int n);       // parts[0] := sum over ranks of (sum of parts[0..n) in cg_sum_parts order)
+int peer_allreduce_parts_multi(qexhip_ctx *c, int m, double *parts0, size_t stride, int n, const SlpScal *st, int gate);   // per system j, into parts0[j stride]
 int peer_allreduce(qexhip_ctx *c, double *dptr, int n, int op);      // on the compute stream; op 0 sum, 1 max; rank order
 int peer_host_reduce(qexhip_ctx *c, double *host, int n, int op);    // host operands (op 0 max, 1 min, 2 sum), synchronous
 int peer_allgather(qexhip_ctx *c, const double *send, double *recv, size_t n);
@@ -506,6 +513,9 @@ int solve_full_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double 
                    int *iters, double *r2_final, int use_prev = 0, int sloppy = 0, int *nupdates = nullptr);
 int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
                         int *iters, double *r2_over_b2, int *nupdates);
+// sharded: the state every rank read back at the end of a chunk (and a 16-bit solve's stall flag) is the same on all ranks, checked
+// before any rank acts on it; one call per system for a batch
+int slp_agree(qexhip_ctx *c, const SlpScal &h, int stalled = 0);
 // the 16-bit solve (option "half"), and the single-system sloppy solve of either storage: sloppy = 2 takes the 16-bit one where
 // the option is set, on one rank and on t-sharded slabs alike.  Both add what they ran to c->slp_last.
 int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,

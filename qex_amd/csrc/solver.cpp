@@ -196,7 +196,7 @@ int solve_xx_continue_dev(qexhip_ctx *c, DevField &x, double r2req, int maxits, 
 // (slp_update: the reductions are rank-global, and so are the flags computed from them).  Checked here, with host operands, before
 // any rank acts on its copy: {r2t, -r2t, key, -key} max-reduced, max and min must coincide.  stalled: the 16-bit solve's stall flag, which
 // decides on every rank whether the fp32 finish -- more collectives -- is entered.
-static int slp_agree(qexhip_ctx *c, const SlpScal &h, int stalled = 0) {
+int slp_agree(qexhip_ctx *c, const SlpScal &h, int stalled) {
   if (c->nranks < 2 || !comm_ready(c)) return 0;
   CHK(peer_check(c));
   const double key = (((double)h.k * 2.0 + h.done) * 2.0 + (stalled != 0)) * 65536.0 + (h.nupd & 0xffff);      // (exact in a double)

@@ -123,7 +123,8 @@ def localMesonTables(stag, lo, mass, t0, r2req, maxits=100000, t_offset=0, slopp
         cs[mu] = stagLocalMesons(dest, symShift(solve(symShift(src, mu)), mu), t0)        mu = 0, 1, 2
     lo is the rank-local Layout, t_offset its first global t.  Returns (cl, [cx, cy, cz], stats) with the raw (nt, 8) tables
     (printLocalMesons transforms and scales them) and stats = {"solve_s", "contract_s", "iterations", "updates"}.
-    sloppy = 1 (or 2) runs the batches in mixed precision (Context.dev_solve_batch(..., sloppy=...): one rank only); "updates" then
+    sloppy = 1 (or 2) runs the batches in mixed precision (Context.dev_solve_batch(..., sloppy=...): one rank, or t-sharded with
+    the context option "batch_ranks" = 1 on every rank); "updates" then
     holds the reliable updates per colour and system, and zeros for the fp64 batch.  deflate = an EigBasis of the operator's even
     sites: every batch is deflated from it with its leading nev vectors (None: deflate.nconv)."""
     import time

@@ -61,7 +61,8 @@ def scalarTrace(stag, lo, rng, mass, r2req, maxits=100000, num_stoch=1, source_t
     site order and est[t] = Re sum_{x in slice t} trce / spatial volume over the GLOBAL t; stats = {"solve_s", "contract_s",
     "noise_s", "log_s", "iterations", "updates"} (seconds in the batched solves; in dilution, accumulation, scaling and slice sums;
     in the noise fill; in the norms of the log lines; iterations and reliable updates per pattern and source).
-    sloppy = 1 (or 2) solves in mixed precision (one rank only).  deflate = an EigBasis of the operator's even sites: every batch is
+    sloppy = 1 (or 2) solves in mixed precision (one rank; t-sharded with the context option "batch_ranks" = 1
+    on every rank).  deflate = an EigBasis of the operator's even sites: every batch is
     deflated from it with its leading nev vectors (None: deflate.nconv), the odd-parity patterns included.  out receives the reference's log lines (None: none, and the
     norms they print are not computed)."""
     ctx = stag.ctx

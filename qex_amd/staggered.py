@@ -24,8 +24,9 @@ from ._lib import check, lib
 EVEN, ODD, ALL = 0, 1, 2
 # SolverParams.sloppySolve (solverBase.nim:8-15): SloppyHalf runs single precision unless the context's option "half" is 1, which
 # gives the single-system solves 16-bit storage, on one rank and on t-sharded lattices alike (Context.set_option("half", 1);
-# half_pack_host is the format; sharded, the faces travel at 16 B per site).  Lock-step batches and multi-shift solves of a sharded
-# context stay as they were: refused, and single precision
+# half_pack_host is the format; sharded, the faces travel at 16 B per site).  Lock-step batches of a sharded context are refused
+# unless its option "batch_ranks" is 1 (then fp32, or 16-bit with "half_batch" = 1, as on one rank); its multi-shift solves refine
+# one shift at a time in single precision
 SloppyNone, SloppySingle, SloppyHalf = 0, 1, 2
 _SUBSET = {"even": EVEN, "odd": ODD, "all": ALL}
 
@@ -322,13 +323,23 @@ class Context:
 
     def dev_op_xx_half_batch(self, r_ids, x_ids, m2s, par_even=True):
         """the batched form of dev_op_xx_half (qexhip_dev_op_xx_half_batch): n <= 4 fields rounded to the 16-bit format, one batched
-        operator with its own m2 per system (the links streamed once for all of them), the results back in fp64"""
+        operator with its own m2 per system (the links streamed once for all of them), the results back in fp64.  One rank without
+        ghost zones; with set_option("batch_ranks", 1) on a t-sharded context too: collective (all systems' 16-bit faces in one
+        exchange per sweep), every system's slab of the one-rank single-system operator's result, bit for bit"""
+        self._op_xx_batch("qexhip_dev_op_xx_half_batch", r_ids, x_ids, m2s, par_even)
+
+    def dev_op_xx_sloppy_batch(self, r_ids, x_ids, m2s, par_even=True):
+        """the fp32 twin of dev_op_xx_half_batch (qexhip_dev_op_xx_sloppy_batch): n <= 4 fields rounded to fp32, one batched fp32
+        operator with its own m2 per system, the results back in fp64; t-sharded contexts with set_option("batch_ranks", 1)"""
+        self._op_xx_batch("qexhip_dev_op_xx_sloppy_batch", r_ids, x_ids, m2s, par_even)
+
+    def _op_xx_batch(self, entry, r_ids, x_ids, m2s, par_even):
         n = len(x_ids)
         if len(r_ids) != n or len(m2s) != n:
-            raise ValueError("dev_op_xx_half_batch: r_ids, x_ids and m2s differ in length")
-        check(lib().qexhip_dev_op_xx_half_batch(self._h, n, (C.c_int * max(n, 1))(*[int(v) for v in r_ids]),
-                                                (C.c_int * max(n, 1))(*[int(v) for v in x_ids]),
-                                                (C.c_double * max(n, 1))(*[float(v) for v in m2s]), 1 if par_even else 0))
+            raise ValueError("%s: r_ids, x_ids and m2s differ in length" % entry[len("qexhip_"):])
+        check(getattr(lib(), entry)(self._h, n, (C.c_int * max(n, 1))(*[int(v) for v in r_ids]),
+                                    (C.c_int * max(n, 1))(*[int(v) for v in x_ids]),
+                                    (C.c_double * max(n, 1))(*[float(v) for v in m2s]), 1 if par_even else 0))
 
     def sloppy_last_batch(self):
         """what the last batched sloppy call ran per system (qexhip_stag_sloppy_last_batch): a list of dicts as sloppy_last()'s"""
@@ -347,7 +358,8 @@ class Context:
     def dev_solve_batch(self, x_ids, b_ids, masses, r2req, maxits=1000000, sloppy=None, deflate=None, nev=None):
         """n x Staggered.solve on resident fields (lock-step batches of four); returns (iterations, r2) per system.
         sloppy = 0, 1 or 2 (SloppyNone / SloppySingle / SloppyHalf) chooses the precision of the batched CG explicitly
-        (qexhip_dev_solve_batch_sloppy; mixed precision on one rank only) and returns (iterations, r2, reliable updates).
+        (qexhip_dev_solve_batch_sloppy; mixed precision on one rank, and on t-sharded contexts with
+        set_option("batch_ranks", 1) on every rank) and returns (iterations, r2, reliable updates).
         deflate = an EigBasis: the inner solveEE / solveOO batches are deflated from it with its leading nev vectors (None:
         deflate.nconv; qexhip_dev_solve_batch_deflated); the return value is that of the same call without it."""
         n = len(x_ids)
@@ -884,7 +896,7 @@ class Staggered:
         all systems.  sps: one SolverParams (shared r2req / maxits) or one per system; each gets the
         statistics of its own system, exactly as n calls of solve would record them.
         sloppy: None = fp64, and a SolverParams that asks for a sloppy solve is refused; 0, 1 or 2 (SloppyNone / SloppySingle /
-        SloppyHalf) = the precision of the batched CG, chosen explicitly whatever sps say (mixed precision: one rank only; every
+        SloppyHalf) = the precision of the batched CG, chosen explicitly whatever sps say (mixed precision: one rank, or t-sharded with option "batch_ranks" = 1; every
         system comes out bit for bit as its own sloppy solve does; sp.reliableUpdates gets each system's updates).
         deflate = an EigBasis: the inner solveEE / solveOO batches are deflated from it (leading nev vectors; None: deflate.nconv)."""
         sl = [sps] * len(xs) if isinstance(sps, SolverParams) else list(sps)
