@@ -4,7 +4,7 @@ noise sources diluted in time and even/odd or the eight 3-d corners.
 
     python examples/scalar_trace.py [-inlat FILE | -lat 4 4 4 8] [-outfn output] [-mass 0.1] [-sloppy 0] [-half 0] [-cg_prec 1e-9]
                                     [-cg_max 100000] [-num_stoch 1] [-improved_trace 1] [-source_type Z4] [-dilute_type EO]
-                                    [-seed N] [-smear 0] [-batch 4] [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3]
+                                    [-seed N] [-smear 0] [-batch 4] [-nev 0] [-nvecs N] [-cheb 12] [-cheb_lo 0.3] [-lma 0]
     python -m torch.distributed.run --nproc-per-node N examples/scalar_trace.py ...     # t-sharded over N ranks
 
 The parameters are the reference program's.  Without -inlat the configuration is g.random of the seed's RngMilc6 field, whose
@@ -16,7 +16,9 @@ given (the context option "batch_ranks" on every rank: the batches run t-sharded
 16-bit storage (the context options "half" and "half_batch"; default 0: it runs single).  -nev N computes the N lowest
 eigenpairs of the even/odd operator once (Staggered.eigs; -nvecs, -cheb, -cheb_lo as in examples/stag_eigs.py) and deflates every
 batch with them, the odd-parity patterns included; the first source is then also solved without deflation and the eigensolve
-time and the iterations with / without deflation are printed."""
+time and the iterations with / without deflation are printed.  -lma 1 (needs -nev > 0; not in the reference) averages those modes
+exactly: their part L(x) of the trace is computed once without noise, every solution is projected off them before it is contracted,
+and the exact part is printed once as `lowsrc ... timeslice t pbp` lines."""
 import argparse
 import os
 import sys
@@ -53,7 +55,11 @@ ap.add_argument("-nev", type=int, default=0, help="deflate every batch with this
 ap.add_argument("-nvecs", type=int, default=0, help="size of the Lanczos basis (default max(2 nev, nev + 8))")
 ap.add_argument("-cheb", type=int, default=12, help="Chebyshev degree (0: plain Lanczos)")
 ap.add_argument("-cheb_lo", type=float, default=0.3)
+ap.add_argument("-lma", type=int, default=0, choices=[0, 1],
+                help="1: low-mode averaging with the -nev modes (needs -nev > 0): their part of the trace is summed exactly")
 a = ap.parse_args()
+if a.lma and a.nev <= 0:
+    sys.exit("scalar_trace.py: -lma 1 needs -nev > 0 (the low modes that are averaged exactly)")
 if a.sloppy and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.batch_ranks:
     sys.exit("scalar_trace.py: -sloppy %d needs a single rank: the mixed-precision lock-step batch is not built for t-sharded "
              "lattices (run without -sloppy, or on one rank)" % a.sloppy)
@@ -135,6 +141,8 @@ if a.nev > 0:
                               dilute_type=a.dilute_type, improved_trace=bool(a.improved_trace), t_offset=rank * lt, sloppy=a.sloppy,
                               batch=a.batch, out=None)
     rng.set_state(state)
+    if a.lma:
+        defl["lma"] = True
 t0 = time.perf_counter()
 traces, ests, st = q.scalarTrace(s, lo, rng, a.mass, a.cg_prec * a.cg_prec, maxits=a.cg_max, num_stoch=a.num_stoch,
                                  source_type=a.source_type, dilute_type=a.dilute_type, improved_trace=bool(a.improved_trace),
@@ -146,6 +154,10 @@ if a.nev > 0:
 print("solves: %.4f s, dilution + contraction + slice sums: %.6f s (%.3f %% of the measurement, %.4f s)" %
       (st["solve_s"], st["contract_s"], 100.0 * st["contract_s"] / total, total))
 print("iterations per pattern:", st["iterations"])
+if a.lma:
+    print("low-mode averaging: L(x) of %d modes in %.4f s, projections %.4f s" % (a.nev, st["lowmode_s"], st["project_s"]))
+    for t in range(nt):
+        print("lowsrc mom 0 0 0 timeslice %d pbp %r" % (t, float(st["low_est"][t])))
 
 spatv = glat[0] * glat[1] * glat[2]
 for i in range(a.num_stoch):

@@ -443,6 +443,8 @@ int qexhip_cfield_free(qexhip_handle h, int id);
 int qexhip_cfield_zero(qexhip_handle h, int id);
 int qexhip_cfield_scale(qexhip_handle h, int id, double s);
 int qexhip_cfield_download(qexhip_handle h, int id, double *host);
+/* dst += a * src on every site, both components (product and sum rounded as written); dst != src, a finite */
+int qexhip_cfield_axpy(qexhip_handle h, int dst, double a, int src);
 /* Time + pattern dilution (src/algorithms/dilution.nim, scalarTrace.nim:169-185) of src into n <= 4 colour vectors in one launch:
  *   dst_k(x) = scale * src(x)  where the GLOBAL time of x is t[k] and x belongs to pattern idx[k];  +0.0 elsewhere
  * kind 0 (EO):     idx in 0..1, the global parity (x0+x1+x2+t)&1
@@ -576,6 +578,31 @@ int qexhip_dev_solve_batch_deflated(qexhip_handle h, int basis, int nev, int n, 
 int qexhip_stag_solve_batch_deflated(qexhip_handle h, int basis, int nev, int n, double *const *x, const double *const *b,
                                      const double *mass, const double *r2req, int maxits, int sloppy, int *iters, double *r2_final,
                                      int *nupdates);
+/* LOW-MODE AVERAGING of the scalar trace (no counterpart in src/observables/scalarTrace.nim: an opt-in extension).  With the pairs
+ * (lambda_i, v_i) of a basis, i < nev, and w_i = D_oe v_i / sqrt(lambda_i) for lambda_i > 0, P is the orthogonal projector onto
+ * span{(v_i, 0), (0, w_i)}: P = V V^+ on the even sites, P phi_o = -D_oe V diag(1/lambda) V^+ D_eo phi_o on the odd sites (a mode with
+ * lambda_i <= 0 has no odd partner).  For exact pairs P commutes with D, and P (D+m)^-1 has the real site diagonal
+ *   L(x) = sum_i m/(m^2 + lambda_i) |v_i(x)|^2  (x even),   sum_i m/(m^2 + lambda_i) |(D_oe v_i)(x)|^2 / lambda_i  (x odd),
+ * |.|^2 summed over colour; sum_{x even} L = sum_{x odd} L = sum_i m/(m^2 + lambda_i).  With Q = 1 - P and phi_d = (D+m)^-1 eta_d,
+ *   L(x) + sum_d m |(Q phi_d)(x)|^2      and      L(x) + sum_d conj(eta_d(x)) (Q phi_d)(x)
+ * estimate m (M^+ M)^-1(x,x) with the low modes' part exact.  With eigenvectors of finite residual P is still an orthogonal projector
+ * but no longer commutes with D: the estimators then carry a bias of the order of the eigenvector residuals.  lambda_i are the basis's
+ * Rayleigh quotients (qexhip_eig_evals).
+ *   block_norm2_accum  (test hook) cfield.even(c).re += sum_{j<n} wgt[j] sum_col |v_{i0+j}(c,col)|^2 in one pass over the n vectors, the
+ *                cfield read and written once.  Vector after vector in ascending j: n2 by the fma chain of qexhip_dev_trace_accum with
+ *                a == b, then re += wgt[j] * n2 (product and sum rounded as written), so the even sites are BIT FOR BIT those of
+ *                get_vector(i0+j, f) + dev_trace_accum(cfield, f, f, wgt[j]) for j = 0..n-1.  Imaginary part and odd sites: untouched.
+ *   lowmode_diag cfield.re += L(x) on both parities for the leading nev vectors: the even sites are block_norm2_accum with
+ *                wgt_i = m/(m^2 + lambda_i); the odd sites take one D_oe sweep per vector with lambda_i > 0 and add
+ *                wgt_i/lambda_i |D_oe v_i|^2 in ascending i.  t-sharded: collective (the sweeps' halo).
+ *   project_out  phi_k <- (1 - P) phi_k in place on both parities for the n (1..4) distinct resident fields ids[k]: per parity ONE
+ *                block_dot_multi and ONE block_axpy_multi, on the odd sites between a D_eo and a D_oe sweep per system; each field's
+ *                result is bit for bit what it is alone.  t-sharded: collective.
+ * Refused before anything is launched: mass not finite or <= 0, nev outside 0..nvecs, n outside 1..4, repeated or unknown ids
+ * (QEXHIP_ERR_ARG); a basis of other links (QEXHIP_ERR_STATE).  nev = 0 changes nothing. */
+int qexhip_eig_block_norm2_accum(qexhip_handle h, int basis, int i0, int n, const double *wgt, int cfield);
+int qexhip_eig_lowmode_diag(qexhip_handle h, int basis, int nev, double mass, int cfield);
+int qexhip_eig_project_out(qexhip_handle h, int basis, int nev, int n, const int *ids);
 /* Dense real symmetric eigensolver on the host (cyclic Jacobi, no external library): what the eigensolver diagonalises at every
  * restart (the reference calls LAPACK there, src/eigens/lapack.nim).  a: n x n symmetric; w[n]: eigenvalues ascending; z (may be
  * NULL): n x n column-major, column i the unit eigenvector of w[i].  Needs no device. */

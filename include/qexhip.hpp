@@ -269,6 +269,13 @@ class Staggered {
     void blockAxpyMulti(int i0, int n, const double *coef, const std::vector<int> &yFields) {
       check(qexhip_eig_block_axpy_multi(c.h, id, i0, n, (int)yFields.size(), coef, yFields.data()));
     }
+    // low-mode averaging (cfield = TraceField::id): cfield.even.re += sum_j wgt[j] |v_{i0+j}|^2 (hook); cfield.re += L(x) of the leading
+    // nev modes at mass m; phi_k <- (1 - P) phi_k in place for at most four resident fields
+    void blockNorm2Accum(int i0, int n, const double *wgt, int cfield) const { check(qexhip_eig_block_norm2_accum(c.h, id, i0, n, wgt, cfield)); }
+    void lowmodeDiag(int nev, double m, int cfield) const { check(qexhip_eig_lowmode_diag(c.h, id, nev, m, cfield)); }
+    void projectOut(int nev, const std::vector<int> &fields) const {
+      check(qexhip_eig_project_out(c.h, id, nev, (int)fields.size(), fields.data()));
+    }
   };
   void eigs(EigBasis &B, const qexhip_eig_opts &o) {
     B.evals.assign(o.nev > 0 ? o.nev : 0, 0.0); B.resid = B.evals;
@@ -451,6 +458,7 @@ class TraceField {
   TraceField(const TraceField &) = delete;
   void zero() { check(qexhip_cfield_zero(c_.h, id)); }
   void scale(double s) { check(qexhip_cfield_scale(c_.h, id, s)); }
+  void axpy(double a, const TraceField &src) { check(qexhip_cfield_axpy(c_.h, id, a, src.id)); }     // this += a * src
   // trce += coef * a_k.dot b_k, k ascending (at most four pairs a call)
   void accum(const std::vector<int> &a, const std::vector<int> &b, double coef = 1.0) {
     if (a.size() != b.size()) throw Error("TraceField::accum: a and b differ in length");

@@ -184,6 +184,10 @@ SYMBOLS = [
     ("qexhip_cfield_zero", _ci, [_vp, _ci]),
     ("qexhip_cfield_scale", _ci, [_vp, _ci, _cd]),
     ("qexhip_cfield_download", _ci, [_vp, _ci, _vp]),
+    ("qexhip_cfield_axpy", _ci, [_vp, _ci, _cd, _ci]),
+    ("qexhip_eig_block_norm2_accum", _ci, [_vp, _ci, _ci, _ci, _vp, _ci]),
+    ("qexhip_eig_lowmode_diag", _ci, [_vp, _ci, _ci, _cd, _ci]),
+    ("qexhip_eig_project_out", _ci, [_vp, _ci, _ci, _ci, _pi]),
     ("qexhip_dev_dilute", _ci, [_vp, _ci, _pi, _ci, _ci, _pi, _pi, _cd]),
     ("qexhip_dev_trace_accum", _ci, [_vp, _ci, _ci, _pi, _pi, _cd]),
     ("qexhip_dev_cfield_slices", _ci, [_vp, _ci, _vp]),

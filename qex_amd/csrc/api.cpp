@@ -1148,6 +1148,16 @@ extern "C" int qexhip_cfield_scale(qexhip_handle c, int id, double s) {
   HIPCHK(hipSetDevice(c->device));
   return cfield_scale(c, *f, s);
 }
+extern "C" int qexhip_cfield_axpy(qexhip_handle c, int dst, double a, int src) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!std::isfinite(a)) { qexhip_set_error("cfield_axpy: a is not finite"); return QEXHIP_ERR_ARG; }
+  DevCField *fd, *fs;
+  CHK(find_cfield(c, dst, &fd));
+  CHK(find_cfield(c, src, &fs));
+  if (dst == src) { qexhip_set_error("cfield_axpy: dst and src are the same cfield %d", dst); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  return cfield_axpy(c, *fd, a, *fs);
+}
 extern "C" int qexhip_cfield_download(qexhip_handle c, int id, double *host) {
   if (!c) return QEXHIP_ERR_ARG;
   if (!host) { qexhip_set_error("cfield_download: null argument"); return QEXHIP_ERR_ARG; }
@@ -1197,6 +1207,56 @@ extern "C" int qexhip_dev_cfield_slices(qexhip_handle c, int cfield, double *out
   CHK(find_cfield(c, cfield, &tr));
   HIPCHK(hipSetDevice(c->device));
   return cfield_slices(c, *tr, out);
+}
+
+// ---- low-mode averaging of the scalar trace (eig.hip): the exact low-mode diagonal and phi <- (1 - P) phi ----
+extern "C" int qexhip_eig_block_norm2_accum(qexhip_handle c, int basis, int i0, int n, const double *wgt, int cfield) {
+  if (!c || !wgt) return QEXHIP_ERR_ARG;
+  EigBasis *B; DevCField *cf;
+  CHK(eig_basis_find(c, basis, &B));
+  CHK(find_cfield(c, cfield, &cf));
+  if (i0 < 0 || n < 1 || i0 > B->nvecs - n) { qexhip_set_error("eig_block_norm2_accum: vectors %d..%d of a basis of %d", i0, i0 + n - 1, B->nvecs); return QEXHIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(c->device));
+  double2 *buf;
+  CHK(eig_coef_buffers(c, nullptr, &buf));
+  HIPCHK(hipMemcpyAsync(buf, wgt, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  CHK(eig_block_norm2_accum(c, *B, i0, n, (const double *)buf, *cf));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// (nev and the basis's links are checked by eig_lowmode_diag / eig_project_out themselves, before they launch anything)
+static int lowmode_args(qexhip_ctx *c, int basis, const char *who, EigBasis **B) {
+  CHK(eig_basis_find(c, basis, B));
+  if (!c->W) { qexhip_set_error("%s: no links set", who); return QEXHIP_ERR_STATE; }
+  return 0;
+}
+extern "C" int qexhip_eig_lowmode_diag(qexhip_handle c, int basis, int nev, double mass, int cfield) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!std::isfinite(mass) || !(mass > 0)) { qexhip_set_error("eig_lowmode_diag: the mass must be finite and positive"); return QEXHIP_ERR_ARG; }
+  EigBasis *B; DevCField *cf;
+  CHK(find_cfield(c, cfield, &cf));
+  CHK(lowmode_args(c, basis, "eig_lowmode_diag", &B));
+  HIPCHK(hipSetDevice(c->device));
+  CHK(eig_lowmode_diag(c, *B, nev, mass, *cf));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return peer_check(c);
+}
+extern "C" int qexhip_eig_project_out(qexhip_handle c, int basis, int nev, int n, const int *ids) {
+  if (!c) return QEXHIP_ERR_ARG;
+  if (!ids) { qexhip_set_error("eig_project_out: null argument"); return QEXHIP_ERR_ARG; }
+  if (n < 1 || n > EIG_MAXRHS) { qexhip_set_error("eig_project_out: n = %d, must be 1..%d", n, EIG_MAXRHS); return QEXHIP_ERR_ARG; }
+  DevField *f[EIG_MAXRHS];
+  for (int k = 0; k < n; k++) {
+    CHK(find_field(c, ids[k], &f[k]));
+    for (int q = 0; q < k; q++)
+      if (ids[q] == ids[k]) { qexhip_set_error("eig_project_out: fields %d and %d are the same (id %d)", q, k, ids[k]); return QEXHIP_ERR_ARG; }
+  }
+  EigBasis *B;
+  CHK(lowmode_args(c, basis, "eig_project_out", &B));
+  HIPCHK(hipSetDevice(c->device));
+  CHK(eig_project_out(c, *B, nev, n, f));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return peer_check(c);
 }
 
 // ---- connected scalar correlator from point sources (conn4d.nim): point sources, translated |phi|^2 accumulation, staggered sign ----

@@ -403,6 +403,121 @@ int eig_block_axpy_mrhs(qexhip_ctx *c, const EigBasis &B, int i0, int n, int nrh
   return 0;
 }
 
+// ---------------- block norm2 accumulate (low-mode averaging) ----------------
+// cf.even(c).re += sum_j wgt_j sum_col |v_j(c, col)|^2: a lane owns site c of the even parity, the three colours of a vector are three
+// lane-contiguous 16-byte loads, the weights are wave-uniform loads, eight vectors' loads in flight.  The arithmetic is k_trace_accum's
+// with a == b (trace.hip), vector after vector in ascending j: n2 by its fma chain over the colours, then acc += wgt_j * n2 with the
+// product and the sum rounded as written -- the bits of n times get_vector + trace_accum.  The imaginary part, the odd parity and the
+// spare lanes of a ragged last tile are not written.
+__global__ void __launch_bounds__(256) k_block_norm2_accum(const double2 *__restrict__ V, size_t n2, int n, const double *__restrict__ wgt,
+                                                           int Vh, double2 *cf) {
+#pragma clang fp contract(off)
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= Vh) return;
+  const double2 *v = V + (size_t)(c >> 6) * 192 + (c & 63);
+  double acc = cf[c].x;
+#pragma unroll 8
+  for (int j = 0; j < n; j++) {
+    const double2 *vj = v + (size_t)j * n2;
+    const double2 x0 = vj[0], x1 = vj[64], x2 = vj[128];
+    double s = 0.0;
+    s = fma(x0.x, x0.x, fma(x0.y, x0.y, s));
+    s = fma(x1.x, x1.x, fma(x1.y, x1.y, s));
+    s = fma(x2.x, x2.x, fma(x2.y, x2.y, s));
+    acc += wgt[j] * s;
+  }
+  cf[c].x = acc;
+}
+// wgt: n doubles on the device
+int eig_block_norm2_accum(qexhip_ctx *c, const EigBasis &B, int i0, int n, const double *wgt, DevCField &cf) {
+  CHK(basis_index_check(B, i0, n, "eig_block_norm2_accum"));
+  CHK(basis_geom_check(c, B));
+  if (cf.half != (size_t)c->g.ntile * 64) { qexhip_set_error("eig_block_norm2_accum: the cfield was allocated for another lattice"); return QEXHIP_ERR_STATE; }
+  ScopedTimer tm(c, "eig_norm2", c->stream);
+  k_block_norm2_accum<<<(c->g.Vh + 255) / 256, 256, 0, c->stream>>>(B.v + (size_t)i0 * B.n2, B.n2, n, wgt, c->g.Vh, cf.par(0));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---------------- low-mode averaging of the scalar trace: L(x) and phi <- (1 - P) phi ----------------
+// P projects onto span{(v_i, 0), (0, D_oe v_i / sqrt(lambda_i)) : i < nev} (lambda_i <= 0: no odd partner).  Both need the Rayleigh
+// quotients and a basis of the operator's present links.
+static int lowmode_check(qexhip_ctx *c, EigBasis &B, int nev, const char *who) {
+  if (nev < 0 || nev > B.nvecs) { qexhip_set_error("%s: nev = %d of a basis of %d vectors", who, nev, B.nvecs); return QEXHIP_ERR_ARG; }
+  CHK(basis_geom_check(c, B));
+  if (B.gen != c->links_gen) { qexhip_set_error("%s: the basis was computed on other links (the operator's links changed since)", who); return QEXHIP_ERR_STATE; }
+  return 0;
+}
+// cf.re += L(x) = sum_i m/(m^2 + lambda_i) |v_i(x)|^2 (x even), ... |(D_oe v_i)(x)|^2 / lambda_i (x odd)
+int eig_lowmode_diag(qexhip_ctx *c, EigBasis &B, int nev, double mass, DevCField &cf) {
+  CHK(lowmode_check(c, B, nev, "eig_lowmode_diag"));
+  if (nev == 0) return 0;
+  CHK(eig_rayleigh(c, B, nev));
+  EigWork *e;
+  CHK(eig_work(c, &e));
+  std::vector<double> w(nev);
+  for (int i = 0; i < nev; i++) w[i] = mass / (mass * mass + B.evals[i]);
+  double *dw = (double *)e->coef;
+  HIPCHK(hipMemcpyAsync(dw, w.data(), sizeof(double) * nev, hipMemcpyHostToDevice, c->stream));
+  CHK(eig_block_norm2_accum(c, B, 0, nev, dw, cf));
+  HIPCHK(hipStreamSynchronize(c->stream));              // (w is read by the copy above)
+  // odd sites, one vector after the other: g.odd = D_oe v_i; g.even = 0 and stays 0 (the odd sweep writes the odd half only).  Every
+  // launch is on the one stream and the accumulation takes one vector at a time, so more work fields would buy nothing.
+  DevField *v, *g;
+  CHK(eig_field(c, EIG_T0, &v));
+  CHK(eig_field(c, EIG_BZ, &g));
+  CHK(blas_zero(c, *g, 0));
+  for (int i = 0; i < nev; i++) {
+    if (!(B.evals[i] > 0)) continue;
+    CHK(eig_get_vector(c, B, i, *v));
+    CHK(op_stagD_pub(c, *g, *v, 1, 0.0, 1.0, 0.0));
+    CHK(trace_accum(c, cf, 1, &g, &g, w[i] / B.evals[i]));
+  }
+  return 0;
+}
+
+// phi_k <- (1 - P) phi_k in place on both parities, k < n <= 4 distinct fields:
+//   even   phi_e -= V V^+ phi_e
+//   odd    phi_o += D_oe V diag(1/lambda) V^+ D_eo phi_o
+// one block_dot_mrhs and one block_axpy_mrhs per parity for all systems, two single-parity sweeps per system.
+int eig_project_out(qexhip_ctx *c, EigBasis &B, int nev, int n, DevField *const *phi) {
+  CHK(lowmode_check(c, B, nev, "eig_project_out"));
+  if (nev == 0) return 0;
+  CHK(eig_rayleigh(c, B, nev));
+  double2 *dots, *coef;
+  CHK(eig_coef_buffers(c, &dots, &coef));
+  DevField *z[EIG_MAXRHS];
+  for (int k = 0; k < n; k++) CHK(eig_field(c, EIG_BZ + k, &z[k]));
+  std::vector<double2> h((size_t)n * nev);
+  // even sites
+  CHK(eig_block_dot_mrhs(c, B, 0, nev, n, phi, dots));
+  HIPCHK(hipMemcpyAsync(h.data(), dots, sizeof(double2) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (size_t q = 0; q < h.size(); q++) { h[q].x = -h[q].x; h[q].y = -h[q].y; }
+  HIPCHK(hipMemcpyAsync(coef, h.data(), sizeof(double2) * h.size(), hipMemcpyHostToDevice, c->stream));
+  CHK(eig_block_axpy_mrhs(c, B, 0, nev, n, coef, 1.0, phi));
+  HIPCHK(hipStreamSynchronize(c->stream));              // (h is read by the copy above)
+  // odd sites
+  for (int k = 0; k < n; k++) CHK(op_stagD_pub(c, *z[k], *phi[k], 0, 0.0, 1.0, 0.0));        // z_k.even = D_eo phi_k.odd
+  CHK(eig_block_dot_mrhs(c, B, 0, nev, n, z, dots));
+  HIPCHK(hipMemcpyAsync(h.data(), dots, sizeof(double2) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < n; k++)
+    for (int i = 0; i < nev; i++) {
+      const double lam = B.evals[i], s = lam > 0 ? 1.0 / lam : 0.0;
+      h[(size_t)k * nev + i].x *= s; h[(size_t)k * nev + i].y *= s;
+    }
+  HIPCHK(hipMemcpyAsync(coef, h.data(), sizeof(double2) * h.size(), hipMemcpyHostToDevice, c->stream));
+  for (int k = 0; k < n; k++) CHK(blas_zero(c, *z[k], 0));
+  CHK(eig_block_axpy_mrhs(c, B, 0, nev, n, coef, 1.0, z));
+  HIPCHK(hipStreamSynchronize(c->stream));              // (h is read by the copy above)
+  for (int k = 0; k < n; k++) {
+    CHK(op_stagD_pub(c, *z[k], *z[k], 1, 0.0, 1.0, 0.0));                                     // z_k.odd = D_oe z_k.even
+    CHK(blas_axpy(c, 1.0, *z[k], *phi[k], 1));
+  }
+  return 0;
+}
+
 // ---------------- in-place rotation ----------------
 // V[:, c] <- sum_j V[:, j] Q[j, c], c < k, j < m, with no second copy of the basis.  A workgroup owns blocks of R consecutive rows
 // (double2 elements): it loads the R x m inputs of a block into LDS ([j][R], 16-byte reads conflict-free), and only after the

@@ -580,6 +580,10 @@ int eig_block_axpy_mrhs(qexhip_ctx *c, const EigBasis &B, int i0, int n, int nrh
 // V[:, 0:k] <- V[:, 0:m] Q, Q real m x k column-major on the host
 int eig_rotate(qexhip_ctx *c, EigBasis &B, int m, int k, const double *Q);
 int eig_rayleigh(qexhip_ctx *c, EigBasis &B, int n);     // fills B.evals[0..n) where missing (one operator application each)
+// low-mode averaging: cf.even.re += sum_j wgt[j] |v_{i0+j}|^2 (wgt on the device); cf.re += L(x) on both parities; phi_k <- (1 - P) phi_k
+int eig_block_norm2_accum(qexhip_ctx *c, const EigBasis &B, int i0, int n, const double *wgt, DevCField &cf);
+int eig_lowmode_diag(qexhip_ctx *c, EigBasis &B, int nev, double mass, DevCField &cf);
+int eig_project_out(qexhip_ctx *c, EigBasis &B, int nev, int n, DevField *const *phi);
 struct qexhip_eig_opts;
 int eig_solve(qexhip_ctx *c, EigBasis &B, const qexhip_eig_opts &o, int *nconv, double *evals, double *resid, long stats[4]);
 
@@ -600,6 +604,7 @@ int meson_read_table(qexhip_ctx *c, const double *dev, size_t n, double *host);
 int cfield_alloc(qexhip_ctx *c, DevCField &f);
 int cfield_zero(qexhip_ctx *c, DevCField &f);
 int cfield_scale(qexhip_ctx *c, DevCField &f, double s);
+int cfield_axpy(qexhip_ctx *c, DevCField &dst, double a, const DevCField &src);       // dst += a src, both components
 int cfield_download(qexhip_ctx *c, const DevCField &f, double *host);                 // [V][2] in the site order of field_download
 int trace_dilute(qexhip_ctx *c, int n, DevField *const *dst, const DevField &src, int kind, const int *idx, const int *t, double scale);
 int trace_accum(qexhip_ctx *c, DevCField &tr, int n, DevField *const *a, DevField *const *b, double coef);

@@ -117,6 +117,15 @@ __global__ void __launch_bounds__(256) k_cfield_scale(int n, double s, double2 *
   *d = make_double2(s * e.x, s * e.y);
 }
 
+// dst += a * src on the body sites of both parities, product and sum rounded as written
+__global__ void __launch_bounds__(256) k_cfield_axpy(int n, double a, double2 *d0, double2 *d1, const double2 *s0, const double2 *s1) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * n) return;
+  double2 *d = i >= n ? d1 + (i - n) : d0 + i;
+  const double2 s = i >= n ? s1[i - n] : s0[i], e = *d;
+  *d = make_double2(e.x + a * s.x, e.y + a * s.y);
+}
+
 // host[p*Vh + c] = trce of parity p, site c: the V=1 even-odd site order of field_download
 __global__ void __launch_bounds__(256) k_cfield_to_host(int n, double2 *__restrict__ host, const double2 *tr0, const double2 *tr1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -141,6 +150,13 @@ int cfield_zero(qexhip_ctx *c, DevCField &f) {
 int cfield_scale(qexhip_ctx *c, DevCField &f, double s) {
   ScopedTimer tm(c, "trace", c->stream);
   k_cfield_scale<<<(2 * c->g.Vh + 255) / 256, 256, 0, c->stream>>>(c->g.Vh, s, f.par(0), f.par(1));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int cfield_axpy(qexhip_ctx *c, DevCField &dst, double a, const DevCField &src) {
+  ScopedTimer tm(c, "trace", c->stream);
+  k_cfield_axpy<<<(2 * c->g.Vh + 255) / 256, 256, 0, c->stream>>>(c->g.Vh, a, dst.par(0), dst.par(1), src.par(0), src.par(1));
   HIPCHK(hipGetLastError());
   return 0;
 }

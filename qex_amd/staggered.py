@@ -448,6 +448,10 @@ class Context:
     def cfield_scale(self, cid, s):
         check(lib().qexhip_cfield_scale(self._h, int(cid), float(s)))
 
+    def cfield_axpy(self, dst, a, src):
+        """dst += a * src on every site, both components (dst != src)"""
+        check(lib().qexhip_cfield_axpy(self._h, int(dst), float(a), int(src)))
+
     def cfield_download(self, cid):
         """(vol, 2) array of (re, im) in the site order of field_download"""
         out = np.zeros((self.vol, 2))
@@ -624,6 +628,25 @@ class EigBasis:
         m, k = Q.shape
         qf = np.asfortranarray(Q)
         check(lib().qexhip_eig_rotate(self.ctx._h, self.id, m, k, qf.ctypes.data))
+
+    # low-mode averaging of the scalar trace (include/qexhip.h "LOW-MODE AVERAGING"; scalar_trace.scalarTrace(lma=True))
+    def block_norm2_accum(self, i0, wgt, cid):
+        """cfield.even(c).re += sum_j wgt[j] sum_col |v_{i0+j}(c,col)|^2 in one pass over the len(wgt) vectors; bit for bit the chain
+        get_vector(i0+j, f) + dev_trace_accum(cid, [f], [f], wgt[j]).  Imaginary part and odd sites are not touched."""
+        w = np.ascontiguousarray(wgt, dtype=np.float64).reshape(-1)
+        check(lib().qexhip_eig_block_norm2_accum(self.ctx._h, self.id, int(i0), len(w), w.ctypes.data, int(cid)))
+
+    def lowmode_diag(self, nev, mass, cid):
+        """cfield.re += L(x), the site diagonal of P (D+m)^-1 for the leading nev modes, on both parities:
+        sum_i m/(m^2+lambda_i) |v_i(x)|^2 on the even and sum_i m/(m^2+lambda_i) |(D_oe v_i)(x)|^2 / lambda_i on the odd sites, with
+        lambda_i the Rayleigh quotients.  Exact for exact eigenpairs; t-sharded: collective."""
+        check(lib().qexhip_eig_lowmode_diag(self.ctx._h, self.id, int(nev), float(mass), int(cid)))
+
+    def project_out(self, nev, ids):
+        """phi_k <- (1 - P) phi_k in place on both parities for 1..4 distinct resident fields, P the orthogonal projector onto the
+        leading nev modes and their odd partners D_oe v_i / sqrt(lambda_i); each field's result is bit for bit what it is alone"""
+        n = len(ids)
+        check(lib().qexhip_eig_project_out(self.ctx._h, self.id, int(nev), n, (C.c_int * max(n, 1))(*[int(v) for v in ids])))
 
     def rayleigh(self, n):
         ev = np.zeros(n)
