@@ -1,27 +1,10 @@
-// batch_f32.hip -- the mixed-precision form of the lock-step batched CG (batch.hip): up to four reliable-update solveXX's on the
-// SAME links, their fp32 iterations advanced together so that the fp32 link copy (dslash_f32.hip) is streamed ONCE per sweep for
-// all of them.  Where QEX's measurement code asks for it: src/observables/conn4d.nim:52 and scalarTrace.nim:42 default to a sloppy
-// solve, which src/quda/qudaWrapperImpl.nim:194-197 hands on as mixed precision.
-//
-// The rule is batch.hip's: every system keeps its own state (SlpScal: sigma, alpha, beta, max|r_s|^2, upd / noupd / done, k, nupd) and
-// its arithmetic is, operation for operation, that of the single-system solve_xx_sloppy_dev (solver.cpp) -- the sweep is
-// k_dslash_mrhs_lowp<StoreF32, ..> (dslash_lowp.h: the single-system body per system), the BLAS kernels are k_slp_* with the system
-// in blockIdx.y and the single-system grid per system, and the reliable update runs the fp64 op_xx per system behind that system's `noupd` word.  A
-// system solved in a batch returns the bits -- solution, iterations, true residual, updates -- it returns alone.
-//
-// One rank without ghost zones by default: t-sharded contexts are refused unless option "batch_ranks" is 1.  With it the sweep takes its
-// HALO form (dslash_lowp.h: sweep_mrhs, all systems' faces in one exchange), every set of partials is summed over the ranks for all
-// systems in ONE collective per reduction point (comm_allreduce_parts_multi: each system's sum formed as comm_allreduce_parts forms it
-// alone) and the n states read back at the end of a chunk are checked for agreement per system (slp_agree) before any rank acts on
-// them.  "Alone" is then the single-system solve_xx_sloppy_dev on the same sharded context, sweep form and transport.  The INVARIANT
-// above slp_update holds per system: rank-global sums, hence the same flags on every rank; the host posts the same exchanges and
-// collectives on every rank whatever the flags say.
+// batch_f32.hip -- the fp32 storage of the reduced-precision lock-step batched CG: the reliable-update CG's BLAS and bookkeeping kernels for
+// n systems, and the instantiations of the one driver and probe for StoreF32.  The rule, the loop and the sharded form: batch_lowp.h.
 #include "qexhip_internal.h"
 #include "site_index.h"
 #include "reduce.h"
 #include "cg_device.h"
-#include "dslash_lowp.h"
-#include <algorithm>
+#include "batch_lowp.h"
 #include <cstring>
 
 // ---- the reliable-update CG's BLAS and bookkeeping kernels (dslash_f32.hip: k_slp_*) for n systems: system = blockIdx.y, each with
@@ -170,38 +153,6 @@ int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb, si
   return 0;
 }
 
-// ---- host ----------------------------------------------------------------------------------------------------------
-enum { BF_R = 0, BF_P, BF_AP, BF_X, BF_T, BF_N };   // fp32 work fields per system
-
-struct BatchF32State {
-  DevFieldF f[BF_N * QX_MAXRHS];
-  SlpScal *s = nullptr;
-  double *partials = nullptr;
-  size_t npart = 0;
-};
-
-void batch_f32_state_free(qexhip_ctx *c) {
-  BatchF32State *S = (BatchF32State *)c->batch_f32;
-  if (!S) return;
-  for (auto &f : S->f) if (f.d) (void)hipFree(f.d);
-  if (S->s) (void)hipFree(S->s);
-  if (S->partials) (void)hipFree(S->partials);
-  delete S;
-  c->batch_f32 = nullptr;
-}
-
-// all systems' <p,Ap> partials, nbd apart, then all systems' |r_s|^2 / |b - A x|^2 partials, nbb apart: one contiguous range per reduction point
-static int bf_partials(BatchF32State *S, int nbd, int nbb) {
-  const size_t need = ((size_t)nbd + nbb) * QX_MAXRHS;
-  if (S->npart < need) {
-    if (S->partials) HIPCHK(hipFree(S->partials));
-    S->partials = nullptr; S->npart = 0;
-    HIPCHK(hipMalloc((void **)&S->partials, need * sizeof(double)));
-    S->npart = need;
-  }
-  return 0;
-}
-
 // what every batched sloppy entry checks before anything is launched
 int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass) {
   if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("batch solve: 1 <= n <= %d", QX_MAXRHS); return -1; }
@@ -215,135 +166,35 @@ int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass) {
   return 0;
 }
 
-// n (1..4) mixed-precision solveXX's in lock-step: solve_xx_batch_dev's semantics (own mass, r2req, iteration count; shared maxits),
-// solve_xx_sloppy_dev's iteration per system.  iters: fp32 iterations; r2_over_b2: the TRUE residual; nupdates: reliable updates.
+// ---- host: batch_lowp.h on fp32 storage -----------------------------------------------------------------------------
+template <>
+struct BatchStore<StoreF32> {
+  static constexpr bool STALL = false;
+  static constexpr const char *PROBE = "dev_op_xx_sloppy_batch",
+                              *PROBE_SHARDED = "the batched fp32 operator runs on one rank without ghost zones (t-sharded: option batch_ranks)";
+  static void *&slot(qexhip_ctx *c) { return c->batch_f32; }
+  static int links(qexhip_ctx *c, int *fmt) { return f32_links(c, fmt, nullptr); }
+  static int ensure(qexhip_ctx *c, DevFieldF &F) { return f32_field_ensure(c, F); }
+  static size_t extent(const qexhip_ctx *c) { return (size_t)c->g.ntile * 192; }      // float2 per parity
+  static int grid(const qexhip_ctx *c) { return slp_grid(extent(c)); }
+  struct Iter {};                                    // the iteration kernels take the bookkeeping's SlpBatch
+  static void iter_args(Iter &, SlpBatch &L, int j, float2 *rs, float2 *ps, const float2 *aps) { L.rs[j] = rs; L.ps[j] = ps; L.aps[j] = aps; }
+  static void xpay(qexhip_ctx *c, const Iter &, const SlpBatch &L, int n) {
+    k_slpb_xpay<<<dim3(grid(c), n), 256, 0, c->stream>>>(L, extent(c));
+  }
+  static void update(qexhip_ctx *c, const Iter &, const SlpBatch &L, int n, int ndot) {
+    k_slpb_update<<<dim3(grid(c), n), 256, 0, c->stream>>>(L, extent(c), ndot);
+  }
+  static int from_f64(qexhip_ctx *c, DevFieldF &y, const DevField &x, int px) { return f32_from_f64(c, y, x, px, 1.0); }
+  static int to_f64(qexhip_ctx *c, DevField &y, const DevFieldF &x, int px) { return f32_to_f64(c, y, x, px, 1.0, 0); }
+};
+
+void batch_f32_state_free(qexhip_ctx *c) { batch_lowp_free<StoreF32>(c); }
+// reports nothing to c->slpb_last itself: its callers do (solve_xx_batch_sloppy_any)
 int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                               int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates) {
-  const Geom &g = c->g;
-  CHK(batch_sloppy_check(c, n, mass));
-  int fmt = 0;
-  CHK(f32_links(c, &fmt, nullptr));
-  BatchF32State *S = (BatchF32State *)c->batch_f32;
-  if (!S) { S = new BatchF32State(); c->batch_f32 = S; }
-  if (!S->s) HIPCHK(hipMalloc((void **)&S->s, sizeof(SlpScal) * QX_MAXRHS));
-  const size_t nvec = (size_t)g.ntile * 192;
-  const int nbd = (g.Vh + 255) / 256 + 4;                                      // room for a sweep's <p,Ap> partials (a split sweep rounds up per range)
-  const int nbb = (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048));   // the k_slp_* grid (grid_for)
-  CHK(bf_partials(S, nbd, nbb));
-  DevField *w64[2 * QX_MAXRHS];
-  CHK(batch_work_fields(c, 2 * QX_MAXRHS, w64));                             // r, A x per system
-  const int par = par_even ? 0 : 1;
-  MrhsArgs<StoreF32> A1, A2;
-  SlpBatch L;
-  memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2); memset(&L, 0, sizeof L);
-  double m2[QX_MAXRHS];
-  DevField *rj[QX_MAXRHS], *axj[QX_MAXRHS];
-  for (int j = 0; j < n; j++) {
-    DevFieldF *const fj = &S->f[BF_N * j];
-    for (int k = 0; k < BF_N; k++) CHK(f32_field_ensure(c, fj[k]));
-    DevFieldF *rs = &fj[BF_R], *ps = &fj[BF_P], *aps = &fj[BF_AP], *xs = &fj[BF_X], *t = &fj[BF_T];
-    rj[j] = w64[2 * j]; axj[j] = w64[2 * j + 1];
-    m2[j] = mass[j] * mass[j];
-    // exactly the start of solve_xx_sloppy_dev: x = 0, b2, r = b, x_s = 0, k_slp_init
-    CHK(blas_zero(c, *x[j], 2));
-    CHK(blas_norm2(c, *b[j], par, &c->dscal[0]));
-    CHK(blas_copy(c, *rj[j], *b[j], par));
-    HIPCHK(hipMemsetAsync(xs->par(par), 0, xs->half * sizeof(float2), c->stream));
-    CHK(slp_init(c, &S->s[j], r2req[j], maxits));
-    A1.in[j] = ps->par(par); A1.out[j] = t->par(1 - par);
-    A2.in[j] = t->par(1 - par); A2.out[j] = aps->par(par); A2.xs[j] = ps->par(par);
-    A2.cb[j] = (float)(4.0 * m2[j]);
-    A2.partials[j] = S->partials + (size_t)nbd * j;
-    L.x[j] = x[j]->par(par); L.r[j] = rj[j]->par(par); L.b[j] = b[j]->par(par); L.Ax[j] = axj[j]->par(par);
-    L.rs[j] = rs->par(par); L.ps[j] = ps->par(par); L.xs[j] = xs->par(par); L.aps[j] = aps->par(par);
-    L.dotp[j] = S->partials + (size_t)nbd * j; L.r2p[j] = S->partials + (size_t)nbd * QX_MAXRHS + (size_t)nbb * j;
-  }
-  L.s = S->s;
-  CHK(mrhs_links(c, n, par, S->s, A1, A2, &fmt));
-  SlpScal h[QX_MAXRHS];
-  auto read_states = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(c->pinned, S->s, sizeof(SlpScal) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(h, c->pinned, sizeof(SlpScal) * n);
-    return 0;
-  };
-  // sharded: every rank holds the same n states before any of them acts on its copy (comm_allreduce_max takes four values: one call per system)
-  auto agree = [&]() -> int { for (int j = 0; j < n; j++) CHK(slp_agree(c, h[j])); return 0; };
-  auto all_done = [&]() { for (int j = 0; j < n; j++) if (!h[j].done) return false; return true; };
-  CHK(read_states());
-  const int every = std::max(1, c->opt_sloppy_check);
-  int k = 0;
-  while (!all_done() && k < maxits) {
-    const int chunk = std::min(32, maxits - k);
-    for (int i = 0; i < chunk; i++, k++) {
-      {
-        ScopedTimer tm(c, "blas", c->stream);
-        k_slpb_xpay<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
-      }
-      int ndot = 0;
-      CHK(sweep_mrhs(c, A1, fmt, false));
-      CHK(sweep_mrhs(c, A2, fmt, true, &ndot));
-      CHK(comm_allreduce_parts_multi(c, n, L.dotp[0], nbd, ndot, L.s, 1, &ndot));
-      CHK(devjoin_flush(c));            // (no-op when the all-reduce has taken the second sweep's join with it)
-      {
-        ScopedTimer tm(c, "blas", c->stream);
-        k_slpb_update<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec, ndot);
-      }
-      HIPCHK(hipGetLastError());
-      CHK(slpb_close(c, L, n, nbb, nbb));
-      // the (device-gated) reliable update of every system whose `upd` is up, posted as solve_xx_sloppy_dev posts its own; a system
-      // that is done counts no further, so the host's k is each live system's own k
-      if ((k + 1) % every == 0 || k + 1 >= maxits) {
-        k_slpb_flush<<<dim3(nbb, n), 256, 0, c->stream>>>(L, nvec);
-        HIPCHK(hipGetLastError());
-        for (int j = 0; j < n; j++) CHK(op_xx(c, *axj[j], *x[j], m2[j], par_even, 0, &S->s[j].noupd));
-        CHK(slpb_resid(c, L, n, nvec, nbb, nbb));
-      }
-    }
-    CHK(read_states());
-    CHK(agree());
-  }
-  for (int j = 0; j < n; j++) {
-    if (iters) iters[j] = h[j].k;
-    if (r2_over_b2) r2_over_b2[j] = (h[j].b2 != 0.0) ? h[j].r2t / h[j].b2 : 0.0;
-    if (nupdates) nupdates[j] = h[j].nupd;
-  }
-  return 0;
+  return solve_xx_batch_lowp<StoreF32>(c, n, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
 }
-
-// fr_j[px] = the batched fp32 operator at m2_j on fx_j[px] rounded to fp32, back in fp64 (qexhip_dev_op_xx_sloppy_batch): the fp32 twin of
-// half_op_xx_batch_probe, on one rank and -- with option "batch_ranks" -- on t-sharded contexts
 int f32_op_xx_batch_probe(qexhip_ctx *c, int n, DevField **fr, DevField **fx, const double *m2, int par_even) {
-  if (n < 1 || n > QX_MAXRHS) { qexhip_set_error("dev_op_xx_sloppy_batch: 1 <= n <= %d", QX_MAXRHS); return -1; }
-  if ((c->nranks > 1 || c->g.halo) && !c->opt_batch_ranks) {
-    qexhip_set_error("the batched fp32 operator runs on one rank without ghost zones (t-sharded: option batch_ranks)");
-    return -1;
-  }
-  int fmt = 0;
-  CHK(f32_links(c, &fmt, nullptr));
-  BatchF32State *S = (BatchF32State *)c->batch_f32;
-  if (!S) { S = new BatchF32State(); c->batch_f32 = S; }
-  if (!S->s) HIPCHK(hipMalloc((void **)&S->s, sizeof(SlpScal) * QX_MAXRHS));
-  const int nbd = (c->g.Vh + 255) / 256 + 4;
-  const size_t nvec = (size_t)c->g.ntile * 192;
-  CHK(bf_partials(S, nbd, (int)std::max<size_t>(1, std::min<size_t>((nvec + 255) / 256, 2048))));
-  HIPCHK(hipMemsetAsync(S->s, 0, sizeof(SlpScal) * QX_MAXRHS, c->stream));       // every system live
-  const int px = par_even ? 0 : 1;
-  MrhsArgs<StoreF32> A1, A2;
-  memset(&A1, 0, sizeof A1); memset(&A2, 0, sizeof A2);
-  for (int j = 0; j < n; j++) {
-    DevFieldF *const fj = &S->f[BF_N * j];
-    for (int k = 0; k < BF_N; k++) CHK(f32_field_ensure(c, fj[k]));
-    CHK(f32_from_f64(c, fj[BF_P], *fx[j], px, 1.0));
-    A1.in[j] = fj[BF_P].par(px); A1.out[j] = fj[BF_T].par(1 - px);
-    A2.in[j] = fj[BF_T].par(1 - px); A2.out[j] = fj[BF_AP].par(px); A2.xs[j] = fj[BF_P].par(px);
-    A2.cb[j] = (float)(4.0 * m2[j]);
-    A2.partials[j] = S->partials + (size_t)nbd * j;
-  }
-  CHK(mrhs_links(c, n, px, S->s, A1, A2, &fmt));
-  CHK(sweep_mrhs(c, A1, fmt, false));
-  CHK(sweep_mrhs(c, A2, fmt, true));
-  CHK(devjoin_flush(c));
-  for (int j = 0; j < n; j++) CHK(f32_to_f64(c, *fr[j], S->f[BF_N * j + BF_AP], px, 1.0, 0));
-  return 0;
+  return op_xx_batch_probe<StoreF32>(c, n, fr, fx, m2, par_even);
 }

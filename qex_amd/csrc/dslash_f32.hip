@@ -399,6 +399,18 @@ int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const De
   HIPCHK(hipGetLastError());
   return 0;
 }
+// one fp32 iteration on the slots F32_R / F32_P / F32_AP: xpay, the two sweeps, the update and its close (slph_iterate's twin)
+int slp_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, const DevField &r, double m2, int par_even) {
+  DevFieldF *rs, *ps, *aps;
+  CHK(f32_field(c, F32_R, &rs));
+  CHK(f32_field(c, F32_P, &ps));
+  CHK(f32_field(c, F32_AP, &aps));
+  const int par = par_even ? 0 : 1;
+  CHK(slp_xpay(c, s, *ps, *rs, r, par));
+  int ndot = 0;
+  CHK(f32_op_xx(c, *aps, *ps, m2, par_even, 1, &s->done, &ndot));
+  return slp_update(c, s, xs, *rs, *ps, *aps, par, ndot);
+}
 // the close of an iteration whose update kernel is another file's (dslash_half.hip): nparts rank-global |r_s|^2 partials in r2p
 int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts) {
   k_slp_close<<<1, 256, 0, c->stream>>>(s, r2p, nparts, SLP_DELTA * SLP_DELTA);

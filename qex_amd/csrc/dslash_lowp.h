@@ -4,7 +4,8 @@
 //   StoreF32   float2 v[tile][3][64] fields and the float4 link copy          (formats: top of dslash_f32.hip)
 //   StoreHalf  one 16-byte element per site and the int16 link copy           (formats: top of dslash_half.hip)
 // dslash_f32.hip, dslash_half.hip, batch_f32.hip and batch_half.hip instantiate these for their storage and keep what is theirs alone:
-// the link encoders, the BLAS and bookkeeping kernels, the solve loops.
+// the link encoders, the BLAS and bookkeeping kernels.  The hosts that drive the sweeps are one per form over the same St: the
+// lock-step batch in batch_lowp.h, the single-system loop in solver.cpp.
 //
 // The operator: out = sgn * (sgn*cb*xs + sum_mu [U in(+mu) - U^+ in(-mu)])  (k_dslash's arithmetic with ca = 0, post = 1): one lane per
 // site, 64-site tiles, links streamed non-temporally with 16-byte loads, fp32 FMAs -- mv3f<false> on the forward link, then mv3f<true>

@@ -247,7 +247,7 @@ struct qexhip_ctx {
   double *meson_buf = nullptr; size_t meson_cap = 0; // workgroup partials + global table of the meson / slice-norm reductions (meson.hip)
   unsigned long links_gen = 0;                       // bumped by every writer of W / Wc (links_compress ends each of them): the fp32 copy's staleness test
   void *f32 = nullptr;                               // F32State (dslash_f32.hip): fp32 links + fields + SlpScal of the mixed-precision CG
-  void *batch_f32 = nullptr;                         // BatchF32State (batch_f32.hip): fp32 fields + SlpScal[4] of the mixed-precision batched CG
+  void *batch_f32 = nullptr;                         // BatchLowpState<StoreF32> (batch_lowp.h): fp32 fields + SlpScal[4] of the mixed-precision batched CG
   void *msf32 = nullptr;                             // MsfState (multishift_f32.hip): fp32 search directions / increments of the mixed-precision multi-shift CG
   void *gfix = nullptr;                              // GfState (gaugefix.hip): transform field t, polish scratch, device loop state
   int opt_gfix_check = 16;                           // option "gfix_check": relax iterations posted between two read-backs of the gauge-fixing state
@@ -262,7 +262,7 @@ struct qexhip_ctx {
   int opt_half = 0;                                  // option "half": 1 = sloppy = 2 runs the 16-bit path (single-system solves, sharded or not)
   int opt_half_stall = 2;                            // option "half_stall": failed reliable updates in a row before the 16-bit solve finishes in fp32
   struct { int precision = 0, half_iters = 0, f32_iters = 0, fell_back = 0; } slp_last;   // the last sloppy solve (qexhip_stag_sloppy_last)
-  void *batch_half = nullptr;                        // BatchHalfState (batch_half.hip): 16-bit fields, x_s, SlpScal[4] and stall guards of the 16-bit lock-step batch
+  void *batch_half = nullptr;                        // BatchLowpState<StoreHalf> (batch_lowp.h): 16-bit fields, x_s, SlpScal[4] and stall guards of the 16-bit lock-step batch
   int opt_half_batch = 0;                            // option "half_batch": 1 = sloppy = 2 on the batched entries runs the 16-bit batch (one rank, no ghost zones)
   // the last batched sloppy call per system (qexhip_stag_sloppy_last_batch); map: system of the entry <- system of the inner batch
   struct { int n = 0, precision[4] = {0, 0, 0, 0}, half_iters[4] = {0, 0, 0, 0}, f32_iters[4] = {0, 0, 0, 0}, fell_back[4] = {0, 0, 0, 0},
@@ -319,7 +319,7 @@ int solve_full_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const
 int batch_work_fields(qexhip_ctx *c, int count, DevField **out);
 int solve_xx_batch_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                        int maxits, int par_even, int *iters, double *r2_over_b2);      // n (1..4) solveXX's in lock-step, fp64
-// ---- batch_f32.hip: the mixed-precision lock-step batch (one rank, no ghost zones) ----
+// ---- batch_f32.hip: the mixed-precision lock-step batch, fp32 storage (the driver of both storages: batch_lowp.h) ----
 void batch_f32_state_free(qexhip_ctx *c);
 int batch_sloppy_check(qexhip_ctx *c, int n, const double *mass);     // n in 1..4, not t-sharded unless option batch_ranks, no mass 0 -- before anything is launched
 int solve_xx_batch_sloppy_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
@@ -335,12 +335,12 @@ struct SlpBatch {
   double *dotp[QX_MAXRHS], *r2p[QX_MAXRHS];      // <p,Ap> partials of the second sweep; |r_s|^2 / |b - A x|^2 partials
   SlpScal *s;
 };
-// k_slpb_close / k_slpb_flush / k_slpb_resid + k_slpb_rclose for n systems, for the 16-bit batch (nvec, nbb: the fp32 batch's BLAS size and grid)
+// k_slpb_close / k_slpb_flush / k_slpb_resid + k_slpb_rclose for n systems, for the driver of both storages (nvec, nbb: the fp64 kernels' size and grid)
 int slpb_close(qexhip_ctx *c, const SlpBatch &L, int n, int nparts, size_t r2stride);      // (r2stride: doubles between two systems' r2p)
 int slpb_flush(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb);
 int slpb_resid(qexhip_ctx *c, const SlpBatch &L, int n, size_t nvec, int nbb, size_t r2stride);
 
-// ---- batch_half.hip: the 16-bit lock-step batch (option "half_batch") ----
+// ---- batch_half.hip: the lock-step batch in 16-bit storage (option "half_batch"; the driver: batch_lowp.h) ----
 void batch_half_state_free(qexhip_ctx *c);
 int solve_xx_batch_half_dev(qexhip_ctx *c, int n, DevField **x, DevField **b, const double *mass, const double *r2req,
                             int maxits, int par_even, int *iters, double *r2_over_b2, int *nupdates);
@@ -452,6 +452,7 @@ int slp_xpay(qexhip_ctx *c, SlpScal *s, DevFieldF &p, DevFieldF &rs, const DevFi
 int slp_update(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, DevFieldF &rs, const DevFieldF &p, const DevFieldF &Ap, int parity, int ndot);
 int slp_flush(qexhip_ctx *c, SlpScal *s, DevField &x, DevFieldF &xs, int parity);
 int slp_resid(qexhip_ctx *c, SlpScal *s, DevField &r, const DevField &b, const DevField &Ax, int parity);
+int slp_iterate(qexhip_ctx *c, SlpScal *s, DevFieldF &xs, const DevField &r, double m2, int par_even);   // one fp32 iteration on F32_R / F32_P / F32_AP
 int slp_close(qexhip_ctx *c, SlpScal *s, const double *r2p, int nparts);     // k_slp_close alone, on rank-global partials
 
 // ---- dslash_half.hip (16-bit storage for the sloppy CG: whole lattice or t-sharded slab, one system) ----

@@ -211,61 +211,9 @@ int slp_agree(qexhip_ctx *c, const SlpScal &h, int stalled) {
   return 0;
 }
 
-int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
-                        int *iters, double *r2_over_b2, int *nupdates) {
-  const int par = par_even ? 0 : 1;
-  DevField *r, *Ax;
-  CHK(get_work(c, WK_R, &r));
-  CHK(get_work(c, WK_AP, &Ax));
-  CHK(f32_links(c, nullptr, nullptr));
-  DevFieldF *rs, *ps, *aps, *xs;
-  CHK(f32_field(c, F32_R, &rs));
-  CHK(f32_field(c, F32_P, &ps));
-  CHK(f32_field(c, F32_AP, &aps));
-  CHK(f32_field(c, F32_X, &xs));
-  SlpScal *s;
-  CHK(slp_alloc(c, &s));
-  const double m2 = mass * mass;
-  if (m2 == 0.0) { qexhip_set_error("sloppy solve: mass 0 unsupported (op_xx's <p,Ap> needs 4 m^2 > 0)"); return -1; }
-  CHK(blas_zero(c, x, 2));                       // (as solve_xx_dev)
-  CHK(blas_norm2(c, b, par, &c->dscal[0]));
-  CHK(blas_copy(c, *r, b, par));
-  HIPCHK(hipMemsetAsync(xs->par(par), 0, xs->half * sizeof(float2), c->stream));
-  CHK(slp_init(c, s, r2req, maxits));
-  SlpScal h;
-  HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  memcpy(&h, c->pinned, sizeof(SlpScal));
-  const int every = std::max(1, c->opt_sloppy_check);
-  const int chunk = 32;
-  int k = 0;
-  while (!h.done && k < maxits) {
-    const int n = std::min(chunk, maxits - k);
-    for (int i = 0; i < n; i++, k++) {
-      CHK(slp_xpay(c, s, *ps, *rs, *r, par));
-      int ndot = 0;
-      CHK(f32_op_xx(c, *aps, *ps, m2, par_even, 1, &s->done, &ndot));
-      CHK(slp_update(c, s, *xs, *rs, *ps, *aps, par, ndot));
-      if ((k + 1) % every == 0 || k + 1 >= maxits) {
-        CHK(slp_flush(c, s, x, *xs, par));
-        CHK(op_xx(c, *Ax, x, m2, par_even, 0, &s->noupd));
-        CHK(slp_resid(c, s, *r, b, *Ax, par));
-      }
-    }
-    HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(&h, c->pinned, sizeof(SlpScal));
-    CHK(slp_agree(c, h));
-  }
-  if (iters) *iters = h.k;
-  if (r2_over_b2) *r2_over_b2 = (h.b2 != 0.0) ? h.r2t / h.b2 : 0.0;
-  if (nupdates) *nupdates = h.nupd;
-  return 0;
-}
-
 // ---- SloppyHalf with option "half": the same loop on 16-bit vectors and links (dslash_half.hip) ----
 // r_s, p_s, Ap_s are stored in the 16-bit format, the increment x_s stays fp32; the update gating, the chunks and the stop on the
-// true fp64 residual are solve_xx_sloppy_dev's, and its fp64 kernels (slp_flush, op_xx, slp_resid) run unchanged.  Stall guard: at a
+// true fp64 residual are the fp32 solve's, and its fp64 kernels (slp_flush, op_xx, slp_resid) run unchanged.  Stall guard: at a
 // light mass cond(A) 2^-15 reaches 1 and the 16-bit recursion can stop improving the true residual; when opt_half_stall reliable
 // updates in a row have not lowered it (0: at the first update) the device ends the 16-bit iteration and the solve finishes in
 // fp32 -- A e = r with solve_xx_sloppy_dev to r2req |b|^2 / |r|^2, x += e, and the true residual recomputed once.  iters and
@@ -273,8 +221,14 @@ int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, do
 // residual, so every rank takes the same updates, the same stop and the same stall; the state read back at the end of a chunk, stall
 // flag included, is checked with slp_agree before any rank acts on it, and the decision to enter half_finish_f32 (itself sharded
 // through solve_xx_sloppy_dev) is taken from that agreed state alone: all ranks enter it or none does.
-int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
-                      int *iters, double *r2_over_b2, int *nupdates) {
+//
+// The one loop of both storages.  HALF: 16-bit storage -- slph_iterate for slp_iterate, the stall guard behind every posted update, its
+// flag read back with the state, the fp32 finish, and the report to c->slp_last (the fp32 solve's callers report for it).  The finish
+// re-enters this loop as solve_xx_sloppy_dev on the same context, same SlpScal and pinned scratch: what the loop holds on the host
+// (h, stalled) is local and final by then.
+template <bool HALF>
+static int solve_xx_lowp(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                         int *iters, double *r2_over_b2, int *nupdates) {
   const int par = par_even ? 0 : 1;
   const double m2 = mass * mass;
   if (m2 == 0.0) { qexhip_set_error("sloppy solve: mass 0 unsupported (op_xx's <p,Ap> needs 4 m^2 > 0)"); return -1; }
@@ -290,17 +244,17 @@ int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, doub
   CHK(blas_copy(c, *r, b, par));
   HIPCHK(hipMemsetAsync(xs->par(par), 0, xs->half * sizeof(float2), c->stream));
   CHK(slp_init(c, s, r2req, maxits));
-  CHK(slph_begin(c, s));                         // (sharded: collective where the 16-bit links are rebuilt)
+  if constexpr (HALF) CHK(slph_begin(c, s));     // (sharded: collective where the 16-bit links are rebuilt)
   SlpScal h;
   int stalled = 0;
   int *const pstall = (int *)((char *)c->pinned + 256);     // (behind the SlpScal)
   static_assert(sizeof(SlpScal) <= 256, "pinned scratch layout");
   auto read_state = [&]() -> int {
     HIPCHK(hipMemcpyAsync(c->pinned, s, sizeof(SlpScal), hipMemcpyDeviceToHost, c->stream));
-    CHK(slph_stalled_async(c, pstall));
+    if constexpr (HALF) CHK(slph_stalled_async(c, pstall));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(&h, c->pinned, sizeof(SlpScal));
-    stalled = *pstall;
+    if constexpr (HALF) stalled = *pstall;
     return 0;
   };
   CHK(read_state());
@@ -310,33 +264,48 @@ int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, doub
   while (!h.done && k < maxits) {
     const int n = std::min(chunk, maxits - k);
     for (int i = 0; i < n; i++, k++) {
-      CHK(slph_iterate(c, s, *xs, *r, m2, par_even));
+      CHK((HALF ? slph_iterate : slp_iterate)(c, s, *xs, *r, m2, par_even));
       if ((k + 1) % every == 0 || k + 1 >= maxits) {
         CHK(slp_flush(c, s, x, *xs, par));
         CHK(op_xx(c, *Ax, x, m2, par_even, 0, &s->noupd));
         CHK(slp_resid(c, s, *r, b, *Ax, par));
-        CHK(slph_stall(c, s, c->opt_half_stall));
+        if constexpr (HALF) CHK(slph_stall(c, s, c->opt_half_stall));
       }
     }
     CHK(read_state());
     CHK(slp_agree(c, h, stalled));
   }
-  int its = h.k, nupd = h.nupd, its32 = 0;
+  int its = h.k, nupd = h.nupd;
   double r2t = h.r2t;
-  if (stalled && r2t > h.r2stop && its < maxits) {
-    // (x holds every increment: the update that tripped the guard flushed x_s; r is its true residual)
-    int nu32 = 0;
-    CHK(half_finish_f32(c, x, b, *r, *Ax, mass, h.r2stop, maxits - its, par_even, &r2t, &its32, &nu32));
-    nupd += nu32;
-    c->slp_last.fell_back = 1;
+  if constexpr (HALF) {
+    int its32 = 0;
+    if (stalled && r2t > h.r2stop && its < maxits) {
+      // (x holds every increment: the update that tripped the guard flushed x_s; r is its true residual)
+      int nu32 = 0;
+      CHK(half_finish_f32(c, x, b, *r, *Ax, mass, h.r2stop, maxits - its, par_even, &r2t, &its32, &nu32));
+      nupd += nu32;
+      c->slp_last.fell_back = 1;
+    }
+    c->slp_last.precision = 2;
+    c->slp_last.half_iters += its;
+    c->slp_last.f32_iters += its32;
+    its += its32;
   }
-  c->slp_last.precision = 2;
-  c->slp_last.half_iters += its;
-  c->slp_last.f32_iters += its32;
-  if (iters) *iters = its + its32;
+  if (iters) *iters = its;
   if (r2_over_b2) *r2_over_b2 = (h.b2 != 0.0) ? r2t / h.b2 : 0.0;
   if (nupdates) *nupdates = nupd;
   return 0;
+}
+
+// (the fp32 links before anything else, the mass-0 refusal included, as this entry always had them)
+int solve_xx_sloppy_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                        int *iters, double *r2_over_b2, int *nupdates) {
+  CHK(f32_links(c, nullptr, nullptr));
+  return solve_xx_lowp<false>(c, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
+}
+int solve_xx_half_dev(qexhip_ctx *c, DevField &x, DevField &b, double mass, double r2req, int maxits, int par_even,
+                      int *iters, double *r2_over_b2, int *nupdates) {
+  return solve_xx_lowp<true>(c, x, b, mass, r2req, maxits, par_even, iters, r2_over_b2, nupdates);
 }
 
 // the fp32 finish of a 16-bit solve whose stall guard tripped, for solve_xx_half_dev above and for every stalled system of the 16-bit batch
