@@ -27,7 +27,7 @@ def kernels(d, f):
     """demangled name -> (resources, [normalised instruction lines])"""
     res, cur = {}, None
     for line in open("%s/%s.rpass" % (d, f)):
-        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\S+)", line)
+        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
         if m and m.group(1) == "Function Name":
             cur = res.setdefault(m.group(2), {})
         elif m:
@@ -46,7 +46,7 @@ def kernels(d, f):
             if t:
                 body[name].append(t)
     dm = demangle(list(res))
-    return {re.sub(r"^void |\(.*$", "", dm[k]): (res[k], body[k]) for k in res}
+    return {re.sub(r"^void |\(.*$", "", dm[k].replace("(anonymous namespace)::", "")): (res[k], body[k]) for k in res}
 
 
 def new_name(old):

@@ -39,7 +39,7 @@ struct PointArgs {
 __global__ void __launch_bounds__(256) k_point_source(Geom g, PointArgs A, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const SiteXYZT s = site_coord(g, c, p);
   const int x = 2 * s.xh + s.o;
   for (int k = 0; k < n; k++) {
@@ -76,7 +76,7 @@ __device__ __forceinline__ int translated(const Geom &g, const SiteXYZT &s, int 
 __global__ void __launch_bounds__(256) k_conn_accum(Geom g, ConnArgs A, int n, double scal, double2 *tr0, double2 *tr1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const SiteXYZT s = site_coord(g, c, p);
   double *tr = &((p ? tr1 : tr0) + c)->x;
   double acc = *tr;
@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) k_conn_accum(Geom g, ConnArgs A, int n, d
 __global__ void __launch_bounds__(256) k_conn_w(Geom g, ConnArgs A, int n, double scal, double *w) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   for (int k = 0; k < n; k++) {
     const double n2 = site_norm2(A.phi[p][k], c);
     w[(size_t)k * g.V + i] = scal * n2;
@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) k_conn_w(Geom g, ConnArgs A, int n, doubl
 __global__ void __launch_bounds__(256) k_conn_add(Geom g, ConnArgs A, int n, int toff, int nt, const double *all, double2 *tr0, double2 *tr1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const SiteXYZT s = site_coord(g, c, p);
   double *tr = &((p ? tr1 : tr0) + c)->x;
   double acc = *tr;
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(256) k_conn_add(Geom g, ConnArgs A, int n, int
 __global__ void __launch_bounds__(256) k_stag_sign(Geom g, double2 *tr0, double2 *tr1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const SiteXYZT s = site_coord(g, c, p);
   if ((s.o + s.y + s.z) & 1) {          // x0 = 2 xh + o
     double2 *d = (p ? tr1 : tr0) + c;

@@ -8,14 +8,14 @@
 // products of a site are written as contiguous 576-double2 rows of the natural-layout force field
 // F[parity][tile][mu][9][64].  Pure streaming: 96 B read, 576 B written per site.
 #include "qexhip_internal.h"
-#include "site_index.h"
+#include "gauge_index.h"
 
 template <bool HALO>
 __global__ void __launch_bounds__(256) k_outer(Geom g, const double2 *__restrict__ x0, const double2 *__restrict__ x1,
                                                double2 *F, double se, double so, int accumulate, int hop) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const double2 *xs = p ? x1 : x0;       // this parity
   const double2 *xn = p ? x0 : x1;       // the neighbours' parity
   const double sc = p ? so : se;
@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(256) k_outer(Geom g, const double2 *__restrict
     double2 b[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) b[k] = xn[vec_off(pos, k)];
-    double2 *w = F + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
+    double2 *w = F + link_tile_off(g, p, c, mu);
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
@@ -38,25 +38,6 @@ __global__ void __launch_bounds__(256) k_outer(Geom g, const double2 *__restrict
         if (accumulate) { double2 o = w[(r * 3 + q) * 64]; v.x += o.x; v.y += o.y; }
         w[(r * 3 + q) * 64] = v;
       }
-  }
-}
-
-__global__ void __launch_bounds__(256) k_force_to_tiles(Geom g, const double2 *__restrict__ host, double2 *F) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
-  for (int mu = 0; mu < 4; mu++) {
-    double2 *w = F + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
-    for (int k = 0; k < 9; k++) w[k * 64] = host[((size_t)i * 4 + mu) * 9 + k];
-  }
-}
-__global__ void __launch_bounds__(256) k_force_from_tiles(Geom g, double2 *__restrict__ host, const double2 *F) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
-  for (int mu = 0; mu < 4; mu++) {
-    const double2 *w = F + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
-    for (int k = 0; k < 9; k++) host[((size_t)i * 4 + mu) * 9 + k] = w[k * 64];
   }
 }
 
@@ -92,13 +73,7 @@ int stag_outer_host(qexhip_ctx *c, double *f_host, const double *x_host, double 
     c->outer_Fn = n2;
   }
   double2 *Fd = c->outer_F;
-  const size_t gbytes = (size_t)g.V * 72 * sizeof(double);
-  if (accumulate) {
-    CHK(ensure_stage(c, gbytes));
-    HIPCHK(hipMemcpyAsync(c->stage, f_host, gbytes, hipMemcpyHostToDevice, c->stream));
-    k_force_to_tiles<<<(g.V + 255) / 256, 256, 0, c->stream>>>(g, (const double2 *)c->stage, Fd);
-    HIPCHK(hipGetLastError());
-  }
+  if (accumulate) CHK(gauge_upload_nat(c, Fd, f_host, false));
   if (g.halo) {
     // neighbours across the t-faces: refresh the ghost zones of both parity halves
     for (int par = 0; par < 2; par++) CHK(comm_halo_exchange(c, *fx, par, 0));
@@ -109,10 +84,5 @@ int stag_outer_host(qexhip_ctx *c, double *f_host, const double *x_host, double 
     k_outer<false><<<(g.V + 255) / 256, 256, 0, c->stream>>>(g, fx->par(0), fx->par(1), Fd, se, so, accumulate, 1);
   }
   HIPCHK(hipGetLastError());
-  CHK(ensure_stage(c, gbytes));
-  k_force_from_tiles<<<(g.V + 255) / 256, 256, 0, c->stream>>>(g, (double2 *)c->stage, Fd);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(f_host, c->stage, gbytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return gauge_download_nat(c, Fd, f_host);
 }

@@ -23,29 +23,22 @@
 
 static int ordered_sites(qexhip_ctx *c, const int **order, int *chunk, int *nb, double **part);
 
-__device__ __forceinline__ size_t link_off(const Geom &g, const int x[4], int mu) {
-  return g.halo ? link_off_t<true>(g, x, mu) : link_off_t<false>(g, x, mu);
-}
-__device__ __forceinline__ void shifted(const Geom &g, const int x[4], int mu, int d, int y[4]) {
-  if (g.halo) shifted_t<true>(g, x, mu, d, y); else shifted_t<false>(g, x, mu, d, y);
-}
-
-// host [idx][mu][9] <-> tiles
+// host [idx][mu][9] <-> tiles: the one kernel pair behind gauge_upload_nat / gauge_download_nat
 __global__ void __launch_bounds__(256) k_gauge_to_tiles(Geom g, const double2 *__restrict__ host, double2 *G) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   for (int mu = 0; mu < 4; mu++) {
-    double2 *w = G + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
+    double2 *w = G + link_tile_off(g, p, c, mu);
     for (int k = 0; k < 9; k++) w[k * 64] = host[((size_t)i * 4 + mu) * 9 + k];
   }
 }
 __global__ void __launch_bounds__(256) k_gauge_from_tiles(Geom g, double2 *__restrict__ host, const double2 *G) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   for (int mu = 0; mu < 4; mu++) {
-    const double2 *w = G + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
+    const double2 *w = G + link_tile_off(g, p, c, mu);
     for (int k = 0; k < 9; k++) host[((size_t)i * 4 + mu) * 9 + k] = w[k * 64];
   }
 }
@@ -65,8 +58,7 @@ __global__ void __launch_bounds__(256) k_gauge_from_tiles(Geom g, double2 *__res
 template <bool HALO, bool S4 = false>
 __global__ void __launch_bounds__(256) k_plaq(Geom g, const double2 *__restrict__ G, double *partials, const int *order, int chunk) {
   double pl[S4 ? 8 : 6] = {0, 0, 0, 0, 0, 0};
-  const int slot = 4 * (blockIdx.x >> 3) + (threadIdx.x >> 6);
-  const int e = slot < chunk ? order[(blockIdx.x & 7) * chunk + slot] : -1;
+  const int e = order_wave_entry(order, chunk);
   const int p = e & 1, c = (e >> 1) * 64 + (threadIdx.x & 63);
   if (e >= 0 && c < g.Vh) {
     int x[4], y[4];
@@ -158,7 +150,7 @@ template <bool CLOSED, bool HALO>
 __global__ void __launch_bounds__(256) k_force_lds(Geom g, const double2 *__restrict__ G, double2 *F, double cp,
                                                    double2 *Pm, double cf, double cpm, double2 *Uout, const int *order, int chunk) {
   extern __shared__ double2 smU[];                    // [2 nu + (0: U_nu(x) | 1: U_nu(x-nu))][9][64]
-  const int e = order[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];
+  const int e = order_block_entry(order, chunk);
   if (e < 0) return;                                  // the whole workgroup together
   const int mu = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p = e & 1;
@@ -353,8 +345,7 @@ __device__ __forceinline__ double m3_retr_mul(const M3 &a, const M3 &b) {
 __global__ void __launch_bounds__(256) k_flow_obs(Geom g, const double2 *__restrict__ G, const ObsTable *T, double *partials,
                                                   const int *order, int chunk) {
   double es = 0, et = 0, q = 0;
-  const int slot = 4 * (blockIdx.x >> 3) + (threadIdx.x >> 6);     // visiting order: tile_order_table, as k_plaq
-  const int e = slot < chunk ? order[(blockIdx.x & 7) * chunk + slot] : -1;
+  const int e = order_wave_entry(order, chunk);     // visiting order: tile_order_table, as k_plaq
   const int p = e & 1, c = (e >> 1) * 64 + (threadIdx.x & 63);
   if (e >= 0 && c < g.Vh) {
     int x[4];
@@ -387,7 +378,7 @@ __global__ void __launch_bounds__(384, 3) k_flow_obs_clover(Geom g, const double
                                                             const int *order, int chunk) {
   extern __shared__ double2 smO[];                    // [2 mu + (0: U_mu(x) | 1: U_mu(x-mu))][9][64], later F[plane][9][64]
   __shared__ double red[4][6];
-  const int e = order[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];
+  const int e = order_block_entry(order, chunk);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double es = 0, et = 0, q = 0, pl = 0;               // pl: Re tr of the plaquette of this wavefront's plane at x
   if (e >= 0) {                                       // the whole workgroup together
@@ -744,7 +735,7 @@ template <bool CLOSED>
 __global__ void __launch_bounds__(256) k_force_gen(Geom g, const double2 *__restrict__ G, double2 *F, double cp,
                                                    double c2, int kind, double2 *Pm, double cf, double cpm, int raw, double2 *Uout,
                                                    const int *order, int chunk) {
-  const int e = order[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];   // tile_order_table
+  const int e = order_block_entry(order, chunk);   // tile_order_table
   if (e < 0) return;
   const int mu = threadIdx.x >> 6;
   const int p = e & 1;
@@ -863,7 +854,7 @@ template <bool CLOSED, bool HALO>
 __global__ void __launch_bounds__(256, 2) k_force_rect(Geom g, const double2 *__restrict__ G, const double2 *__restrict__ D, double2 *F,
                                                     double cp, double c2, double2 *Pm, double cf, double cpm, int raw, double2 *Uout,
                                                     const int *order, int chunk) {
-  const int e = order[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];   // tile_order_table
+  const int e = order_block_entry(order, chunk);   // tile_order_table
   if (e < 0) return;
   const int mu = threadIdx.x >> 6;
   const int p = e & 1;
@@ -982,18 +973,10 @@ int gauge_field_ghosts(qexhip_ctx *c, double2 *field, int depth) {
   const Geom &g = c->g;
   if (!g.halo) return 0;
   if (g.X[3] < depth) { qexhip_set_error("local t extent %d < ghost depth %d needed by this kernel", g.X[3], depth); return -1; }
-  const size_t tile2 = (size_t)4 * 576 * 2;                 // doubles per link-tile
-  const size_t ft = (size_t)g.F / 64;                       // tiles per t-slice
   double *bottom[2], *top[2], *ghi[2], *glo[2];
-  for (int p = 0; p < 2; p++) {
-    double *base = (double *)field + (size_t)p * g.etile * tile2;
-    bottom[p] = base;
-    top[p] = base + ((size_t)g.ntile - depth * ft) * tile2;
-    ghi[p] = base + (size_t)g.ntile * tile2;
-    glo[p] = base + ((size_t)g.ntile + 3 * ft + (3 - depth) * ft) * tile2;
-  }
+  const size_t face = ghost_faces(g, field, 4 * 576, depth, bottom, top, ghi, glo);
   ScopedTimer tm(c, "gauge_halo", c->stream);
-  return comm_faces_exchange(c, 2, bottom, top, ghi, glo, (size_t)depth * ft * tile2);
+  return comm_faces_exchange(c, 2, bottom, top, ghi, glo, face);
 }
 // refresh the ghost slices of the resident links to at least `depth` (1..3); no-op unless t is sharded
 int gauge_ghosts(qexhip_ctx *c, int depth) {
@@ -1033,17 +1016,22 @@ void gauge_free(qexhip_ctx *c) {
 int gauge_set(qexhip_ctx *c, const double *g) {
   HIPCHK(hipSetDevice(c->device));
   CHK(gn_alloc(c));
-  size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
-  CHK(ensure_stage(c, bytes));
-  HIPCHK(hipMemcpyAsync(c->stage, g, bytes, hipMemcpyHostToDevice, c->stream));
-  k_gauge_to_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (const double2 *)c->stage, c->gn->U);
-  HIPCHK(hipGetLastError());
+  CHK(gauge_upload_nat(c, c->gn->U, g));
   c->gn->ghost_valid = 0;
-  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
-static int download_nat(qexhip_ctx *c, const double2 *G, double *host) {
-  size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
+// host [idx][mu][9] <-> any gauge-shaped device field
+int gauge_upload_nat(qexhip_ctx *c, double2 *G, const double *host, bool sync) {
+  const size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
+  CHK(ensure_stage(c, bytes));
+  HIPCHK(hipMemcpyAsync(c->stage, host, bytes, hipMemcpyHostToDevice, c->stream));
+  k_gauge_to_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (const double2 *)c->stage, G);
+  HIPCHK(hipGetLastError());
+  if (sync) HIPCHK(hipStreamSynchronize(c->stream));          // the caller may reuse `host` (f aliasing chain)
+  return 0;
+}
+int gauge_download_nat(qexhip_ctx *c, const double2 *G, double *host) {
+  const size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
   CHK(ensure_stage(c, bytes));
   k_gauge_from_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (double2 *)c->stage, G);
   HIPCHK(hipGetLastError());
@@ -1053,7 +1041,7 @@ static int download_nat(qexhip_ctx *c, const double2 *G, double *host) {
 }
 int gauge_get(qexhip_ctx *c, double *g) {
   if (!c->gn) { qexhip_set_error("gauge field not set (qexhip_gauge_set)"); return -3; }
-  return download_nat(c, c->gn->U, g);
+  return gauge_download_nat(c, c->gn->U, g);
 }
 
 // one lane per site in the blocked visiting order, 4 table slots per workgroup; `part` holds 6 doubles per workgroup
@@ -1181,7 +1169,7 @@ int gauge_force(qexhip_ctx *c, double *f_host, double cplaq, double c2, int kind
   if (!c->gn) { qexhip_set_error("gauge field not set (qexhip_gauge_set)"); return -3; }
   if (kind == 0 && c2 != 0.0) for (int d = 0; d < 4; d++) if (c->g.X[d] < 4) { qexhip_set_error("rectangle action needs extents >= 4"); return -1; }
   CHK(force_dev(c, cplaq, 0, 0, 0, c2, kind));
-  return download_nat(c, c->gn->F, f_host);
+  return gauge_download_nat(c, c->gn->F, f_host);
 }
 
 int gauge_wflow(qexhip_ctx *c, int nsteps, double eps, double cplaq, double c2, int kind) {
@@ -1214,17 +1202,6 @@ int gauge_stout_stage(qexhip_ctx *c, double2 *Uin, double2 *V, double2 *Uout, do
   if (!Uin && !c->gn) { qexhip_set_error("gauge field not set (qexhip_gauge_set)"); return -3; }
   return force_dev(c, 1.0, 1, -alpha * 3.0, 0.0, 0.0, 0, Uout, Uin ? Uin : c->gn->U, V);
 }
-// host [idx][mu][9] <-> any gauge-shaped device field
-int gauge_upload_nat(qexhip_ctx *c, double2 *G, const double *host) {
-  const size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
-  CHK(ensure_stage(c, bytes));
-  HIPCHK(hipMemcpyAsync(c->stage, host, bytes, hipMemcpyHostToDevice, c->stream));
-  k_gauge_to_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (const double2 *)c->stage, G);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));          // the caller may reuse `host` (f aliasing chain)
-  return 0;
-}
-int gauge_download_nat(qexhip_ctx *c, const double2 *G, double *host) { return download_nat(c, G, host); }
 // the resident links become *buf, *buf the old resident buffer (both gauge-shaped); creates the resident field if there is none
 int gauge_swap_resident(qexhip_ctx *c, double2 **buf) {
   CHK(gn_alloc(c));
@@ -1238,7 +1215,7 @@ int gauge_swap_resident(qexhip_ctx *c, double2 **buf) {
 __global__ void __launch_bounds__(256) k_action(Geom g, const double2 *__restrict__ G, int rect, double *partials) {
   double sp = 0, sa = 0, sr = 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < g.V; i += gridDim.x * 256) {
-    int p = i >= g.Vh, c = i - p * g.Vh;
+    int p, c; linear_site(g, i, p, c);
     int x[4];
     coords_of(g, c, p, x);
 #pragma unroll 1
@@ -1299,10 +1276,7 @@ int gauge_action(qexhip_ctx *c, double cplaq, double c2, int kind, double *out) 
 int gauge_md_update(qexhip_ctx *c, const double *p_host, double t) {
   if (!c->gn) { qexhip_set_error("gauge field not set (qexhip_gauge_set)"); return -3; }
   CHK(gn_alloc_fp(c));
-  const size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
-  CHK(ensure_stage(c, bytes));
-  HIPCHK(hipMemcpyAsync(c->stage, p_host, bytes, hipMemcpyHostToDevice, c->stream));
-  k_gauge_to_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (const double2 *)c->stage, c->gn->P);
+  CHK(gauge_upload_nat(c, c->gn->P, p_host, false));
   const size_t ltiles = (size_t)2 * c->g.ntile * 4;
   ScopedTimer tm(c, "expupdate", c->stream);
   k_exp_update<<<(unsigned)((ltiles * 64 + 255) / 256), 256, 0, c->stream>>>(ltiles, c->gn->U, c->gn->P, t, (size_t)c->g.ntile * 4, (size_t)c->g.etile * 4);
@@ -1360,13 +1334,7 @@ int md_begin(qexhip_ctx *c, const double *g, const double *p) {
   CHK(gn_alloc_fp(c));
   const size_t nbytes = c->gn->n2 * sizeof(double2);
   if (!c->gn->M) { HIPCHK(hipMalloc((void **)&c->gn->M, nbytes)); HIPCHK(hipMemsetAsync(c->gn->M, 0, nbytes, c->stream)); }
-  if (p) {          // p == NULL: keep the resident momenta (qexhip_md_refresh_momenta draws them on the device)
-    const size_t bytes = (size_t)c->g.V * 72 * sizeof(double);
-    CHK(ensure_stage(c, bytes));
-    HIPCHK(hipMemcpyAsync(c->stage, p, bytes, hipMemcpyHostToDevice, c->stream));
-    k_gauge_to_tiles<<<(c->g.V + 255) / 256, 256, 0, c->stream>>>(c->g, (const double2 *)c->stage, c->gn->M);
-    HIPCHK(hipGetLastError());
-  }
+  if (p) CHK(gauge_upload_nat(c, c->gn->M, p, false));          // p == NULL: keep the resident momenta (qexhip_md_refresh_momenta draws them on the device)
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1379,8 +1347,8 @@ int md_momenta_dev(qexhip_ctx *c, double2 **M) {
 }
 int md_end(qexhip_ctx *c, double *g, double *p) {
   CHK(md_ready(c));
-  if (g) CHK(download_nat(c, c->gn->U, g));
-  if (p) CHK(download_nat(c, c->gn->M, p));
+  if (g) CHK(gauge_download_nat(c, c->gn->U, g));
+  if (p) CHK(gauge_download_nat(c, c->gn->M, p));
   return 0;
 }
 int md_momentum_norm2(qexhip_ctx *c, double *out) {
@@ -1468,7 +1436,7 @@ int gauge_reunit(qexhip_ctx *c) {
 __global__ void __launch_bounds__(256) k_wline(Geom g, const double2 *__restrict__ G, const int *path, int n, double *partials) {
   double sr = 0, si = 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < g.V; i += gridDim.x * 256) {
-    int p = i >= g.Vh, c = i - p * g.Vh;
+    int p, c; linear_site(g, i, p, c);
     int x[4];
     coords_of(g, c, p, x);
     M3 m;

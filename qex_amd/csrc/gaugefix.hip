@@ -102,8 +102,7 @@ __global__ void __launch_bounds__(256) k_gf_sweep(Geom g, const double2 *__restr
     const int active = (s->its + 1) & 1;
     par = RELAX ? active : 1 - active;
   }
-  const int slot = 4 * (blockIdx.x >> 3) + (threadIdx.x >> 6);
-  const int e = slot < chunk ? order[(blockIdx.x & 7) * chunk + slot] : -1;
+  const int e = order_wave_entry(order, chunk);
   const int c = (e >> 1) * 64 + (threadIdx.x & 63);
   double mt = 0, gr = 0;
   if (e >= 0 && (e & 1) == par && c < g.Vh) {
@@ -126,7 +125,7 @@ __global__ void __launch_bounds__(256) k_gf_sweep(Geom g, const double2 *__restr
         m3_mac_aa(gd, u, tb);
       }
     }
-    const size_t to = ((size_t)par * g.etile + (c >> 6)) * 576 + (c & 63);
+    const size_t to = tile_off(g, par, c, 576);
     M3 t = m3_load(T + to, 64);
     M3 m = m3_mul(t, gd);
     mt = m.e[0].x + m.e[4].x + m.e[8].x;
@@ -260,15 +259,15 @@ __global__ void __launch_bounds__(256) k_gf_sum1(const double *parts, int nb, do
 __global__ void __launch_bounds__(256) k_gf_to_tiles(Geom g, const double2 *__restrict__ host, double2 *T) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
-  double2 *w = T + ((size_t)p * g.etile + (c >> 6)) * 576 + (c & 63);
+  int p, c; linear_site(g, i, p, c);
+  double2 *w = T + tile_off(g, p, c, 576);
   for (int k = 0; k < 9; k++) w[k * 64] = host ? host[(size_t)i * 9 + k] : make_double2((k & 3) == 0 ? 1.0 : 0.0, 0.0);
 }
 __global__ void __launch_bounds__(256) k_gf_from_tiles(Geom g, double2 *__restrict__ host, const double2 *T) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
-  const double2 *w = T + ((size_t)p * g.etile + (c >> 6)) * 576 + (c & 63);
+  int p, c; linear_site(g, i, p, c);
+  const double2 *w = T + tile_off(g, p, c, 576);
   for (int k = 0; k < 9; k++) host[(size_t)i * 9 + k] = w[k * 64];
 }
 
@@ -286,16 +285,9 @@ int field_ensure(qexhip_ctx *c, GfState *S, double2 **f) {
 int t_faces(qexhip_ctx *c, GfState *S) {
   const Geom &g = c->g;
   if (!g.halo) return 0;
-  const size_t tile2 = (size_t)576 * 2, ft = (size_t)g.F / 64;
   double *bottom[2], *top[2], *ghi[2], *glo[2];
-  for (int p = 0; p < 2; p++) {
-    double *base = (double *)S->T + (size_t)p * g.etile * tile2;
-    bottom[p] = base;
-    top[p] = base + ((size_t)g.ntile - ft) * tile2;
-    ghi[p] = base + (size_t)g.ntile * tile2;
-    glo[p] = base + ((size_t)g.ntile + 5 * ft) * tile2;
-  }
-  return comm_faces_exchange(c, 2, bottom, top, ghi, glo, ft * tile2);
+  const size_t face = ghost_faces(g, S->T, 576, 1, bottom, top, ghi, glo);
+  return comm_faces_exchange(c, 2, bottom, top, ghi, glo, face);
 }
 
 struct Sweep {

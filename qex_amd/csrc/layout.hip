@@ -53,14 +53,14 @@ int field_alloc(qexhip_ctx *c, DevField &f) {
 __global__ void __launch_bounds__(256) k_vec_to_tiles(Geom g, const double2 *__restrict__ host, double2 *dev, size_t half) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   double2 *d = dev + (size_t)p * half;
   for (int k = 0; k < 3; k++) d[vec_off(c, k)] = host[(size_t)i * 3 + k];
 }
 __global__ void __launch_bounds__(256) k_vec_from_tiles(Geom g, double2 *__restrict__ host, const double2 *dev, size_t half) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const double2 *d = dev + (size_t)p * half;
   for (int k = 0; k < 3; k++) host[(size_t)i * 3 + k] = d[vec_off(c, k)];
 }
@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(256) k_links_to_tiles(Geom g, const double2 *_
                                                         int ndir, int dbase, int hop) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   SiteXYZT s = site_coord(g, c, p);
   double2 *w = W + ((size_t)p * g.ntile + (c >> 6)) * ndir * 576 + (c & 63);
   for (int mu = 0; mu < 4; mu++) {
@@ -351,7 +351,8 @@ int links_compress(qexhip_ctx *c) {
 __global__ void __launch_bounds__(256) k_links_from_nat(Geom g, const double2 *__restrict__ N, double2 *W, int ndir, int dbase, int hop) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
+  int p = i >= g.Vh, c = i - p * g.Vh;     // (inline, as the two link offsets below: already with linear_site hipcc emits another
+                                           // instruction stream for this kernel, profiles/gauge_index_resources.txt)
   SiteXYZT s = site_coord(g, c, p);
   double2 *w = W + ((size_t)p * g.ntile + (c >> 6)) * ndir * 576 + (c & 63);
   for (int mu = 0; mu < 4; mu++) {

@@ -80,7 +80,7 @@ __global__ void __launch_bounds__(256) k_sym_shift(Geom g, const double2 *W, con
                                                    const double2 *x0, const double2 *x1, double2 *r0, double2 *r1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const SiteXYZT s = site_coord(g, c, p);
   constexpr int LROW = LinkFormat<RECON>::LROW;   // double2 per (tile, direction)
   const size_t row = ((size_t)p * g.ntile + (c >> 6)) * ndir + 2 * mu;  // (parity, tile, dir 2mu)

@@ -45,6 +45,20 @@ __host__ __device__ inline size_t body_tile_off(size_t tile, size_t ntile4, size
   const size_t p = tile >= ntile4;
   return (p * etile4 + (tile - p * ntile4)) * 576;
 }
+// The t-faces of the two parity halves of a tiled field (tstride double2 per tile: 576 one matrix per site, 4*576 gauge-shaped) for
+// comm_faces_exchange at ghost depth `depth` (1..3): my bottom and top `depth` slices, the start of ghost_hi, and the last `depth`
+// of ghost_lo's three slices.  Fills [0] and [1] of each array; returns the doubles per face.
+inline size_t ghost_faces(const Geom &g, const double2 *field, int tstride, int depth, double **bottom, double **top, double **ghi, double **glo) {
+  const size_t tile2 = (size_t)tstride * 2, ft = (size_t)g.F / 64;   // doubles per tile, tiles per t-slice
+  for (int p = 0; p < 2; p++) {
+    double *base = (double *)field + (size_t)p * g.etile * tile2;
+    bottom[p] = base;
+    top[p] = base + ((size_t)g.ntile - depth * ft) * tile2;
+    ghi[p] = base + (size_t)g.ntile * tile2;
+    glo[p] = base + ((size_t)g.ntile + 3 * ft + (3 - depth) * ft) * tile2;
+  }
+  return (size_t)depth * ft * tile2;
+}
 
 struct DevField {  // full-volume colour vector: parity halves, each with its ghost tiles
   double2 *d = nullptr;
@@ -675,6 +689,11 @@ int gauge_plaq_s4(qexhip_ctx *c, double out[8]);
 void gauge_free(qexhip_ctx *c);
 void gauge_release_scratch(qexhip_ctx *c);
 const double2 *gauge_links_dev(qexhip_ctx *c);   // resident natural-layout links (nullptr before qexhip_gauge_set)
+// host [idx][mu][9] <-> any gauge-shaped device field, through the staging buffer.  The download waits for the stream; the upload does with
+// sync (the caller may reuse `host` at once), else `host` must stay untouched until the stream has passed the copy
+int gauge_upload_nat(qexhip_ctx *c, double2 *G, const double *host, bool sync = true);
+int gauge_download_nat(qexhip_ctx *c, const double2 *G, double *host);
+int gauge_field_ghosts(qexhip_ctx *c, double2 *field, int depth);   // refresh the depth-`depth` ghost slices of any gauge-shaped device field
 int gauge_ghosts(qexhip_ctx *c, int depth);      // refresh the ghost slices of the resident links to at least `depth` (no-op unless t is sharded)
 int read_global(qexhip_ctx *c, double *dev, int n, double *host);   // rank-sum of n device scalars, then read back
 // ---- gaugefix.hip (src/gauge/gaugefix.nim) ----

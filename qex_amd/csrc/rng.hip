@@ -286,6 +286,7 @@ extern "C" int qexhip_rng_set_state(qexhip_rng *R, const unsigned *in) {
 // differs from the host's (by one float32 ulp) only when the double lands within ~1e-16 of a float32 rounding boundary:
 // about once per 1e8 deviates (tests/test_rng_product.py counts them).  u1 phases carry no float32 rounding: 1e-16 agreement.
 #include "qexhip_internal.h"
+#include "gauge_index.h"
 
 __device__ __forceinline__ uint32_t milc6_next(uint32_t *w) {     // w: r0..r6, ic, mult (milcrng.nim:120-133)
   const uint32_t t = (((w[5] >> 7) | (w[6] << 17)) ^ ((w[4] >> 1) | (w[5] << 23))) & 0x00FFFFFFu;
@@ -309,7 +310,7 @@ __global__ void __launch_bounds__(256) k_rng_milc6(Geom g, uint32_t *__restrict_
   uint32_t w[9];
 #pragma unroll
   for (int k = 0; k < 9; k++) w[k] = state[(size_t)9 * i + k];
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   if (what == 2) {
     const double s2 = 0.70710678118654752440, s3 = 0.57735026918962576450;
 #pragma unroll 1
@@ -318,7 +319,7 @@ __global__ void __launch_bounds__(256) k_rng_milc6(Geom g, uint32_t *__restrict_
       const double r8 = s2 * s3 * milc6_gaussian(w);
       const double r01 = s2 * milc6_gaussian(w), r02 = s2 * milc6_gaussian(w), r12 = s2 * milc6_gaussian(w);
       const double i01 = s2 * milc6_gaussian(w), i02 = s2 * milc6_gaussian(w), i12 = s2 * milc6_gaussian(w);
-      double2 *d = P + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
+      double2 *d = P + link_tile_off(g, p, c, mu);
       d[0 * 64] = make_double2(0.0, r8 + r3); d[1 * 64] = make_double2(r01, i01); d[2 * 64] = make_double2(r02, i02);
       d[3 * 64] = make_double2(-r01, i01);    d[4 * 64] = make_double2(0.0, r8 - r3); d[5 * 64] = make_double2(r12, i12);
       d[6 * 64] = make_double2(-r02, i02);    d[7 * 64] = make_double2(-r12, i12);    d[8 * 64] = make_double2(0.0, -2 * r8);

@@ -21,6 +21,12 @@ __host__ __device__ __forceinline__ SiteXYZT site_coord(const Geom &g, int c, in
   return s;
 }
 
+// linear site i in [0, V) = both parities back to back -> (parity, checkerboard index)
+__host__ __device__ __forceinline__ void linear_site(const Geom &g, int i, int &p, int &c) {
+  p = i >= g.Vh;
+  c = i - p * g.Vh;
+}
+
 __host__ __device__ __forceinline__ int wrap(int v, int n) { return v >= n ? v - n : (v < 0 ? v + n : v); }
 
 // position, in the field of the OPPOSITE parity, of the site s + hop*mu (hop = +-1, +-3).

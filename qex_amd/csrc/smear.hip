@@ -12,9 +12,11 @@
 // (A: side links of direction nu, B: any matrix field standing for the mu link), plus scale,
 // projectU and the 3-link Naik product.  One lane per site; matrix fields use the tile layout
 // [parity][tile][9][64] (a gauge field is four of them interleaved: [parity][tile][mu][9][64]).
-// Single GPU (periodic wrap), like the flow kernels.
+// Sites, shifts and tile offsets are gauge_index.h's: periodic on one GPU; on a t-sharded lattice a t-hop lands in the ghost
+// tiles.  HALO is a template parameter for the two register-tight staple kernels, a runtime flag (g.halo) everywhere else.
 #include "qexhip_internal.h"
 #include "su3.h"
+#include "gauge_index.h"
 #include <cmath>
 #include <algorithm>
 
@@ -26,40 +28,6 @@ struct MViewW {
   double2 *p;
   int tstride;
 };
-
-__device__ __forceinline__ void coords_sm(const Geom &g, int c, int p, int x[4]) {
-  unsigned r = (unsigned)c;
-  int xh = r % (unsigned)g.Xh; r /= (unsigned)g.Xh;
-  x[1] = r % (unsigned)g.X[1]; r /= (unsigned)g.X[1];
-  x[2] = r % (unsigned)g.X[2];
-  x[3] = r / (unsigned)g.X[2];
-  x[0] = 2 * xh + ((x[1] + x[2] + x[3] + p) & 1);
-}
-// t-sharded runs: every parity half of a matrix field is [body ntile | ghost_hi 3F/64 tiles | ghost_lo 3F/64 tiles]
-// (the layout of gauge.hip); a t-hop never wraps, virtual slices Xt..Xt+2 / -3..-1 map to the ghost tiles.  HALO is a
-// template parameter for the two register-tight staple kernels, a runtime flag (g.halo) everywhere else.
-template <bool HALO>
-__device__ __forceinline__ size_t site_off_t(const Geom &g, const int x[4], int tstride) {
-  int t = x[3];
-  if (HALO) t = t < 0 ? t + g.X[3] + 6 : t;
-  int lex = x[0] + g.X[0] * (x[1] + g.X[1] * (x[2] + g.X[2] * t));
-  int p = (x[0] + x[1] + x[2] + x[3]) & 1;
-  int c = lex >> 1;
-  return ((size_t)p * g.etile + (c >> 6)) * tstride + (c & 63);
-}
-template <bool HALO>
-__device__ __forceinline__ void shift_sm_t(const Geom &g, const int x[4], int mu, int d, int y[4]) {
-  y[0] = x[0]; y[1] = x[1]; y[2] = x[2]; y[3] = x[3];
-  int v = y[mu] + d;
-  if (HALO && mu == 3) { y[3] = v; return; }
-  y[mu] = v >= g.X[mu] ? v - g.X[mu] : (v < 0 ? v + g.X[mu] : v);
-}
-__device__ __forceinline__ size_t site_off(const Geom &g, const int x[4], int tstride) {
-  return g.halo ? site_off_t<true>(g, x, tstride) : site_off_t<false>(g, x, tstride);
-}
-__device__ __forceinline__ void shift_sm(const Geom &g, const int x[4], int mu, int d, int y[4]) {
-  if (g.halo) shift_sm_t<true>(g, x, mu, d, y); else shift_sm_t<false>(g, x, mu, d, y);
-}
 
 // blocked visiting order for the gather kernels (tile_order_table / tile_order_plane, layout.hip)
 static int smear_order(qexhip_ctx *c, const Geom &g, const int **order, int *chunk, int *nblk, int mu = -1, int nu = -1) {
@@ -82,9 +50,8 @@ __global__ void __launch_bounds__(256) k_gen_staple(Geom g, MView A, MView B, in
     const int n = gc1 - gc0, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 2 * n) return;
     p = i >= n; c = gc0 + i - p * n;
-  } else if (order) {   // blocked visiting order (tile_order_table): wavefront w takes slot 4*(b>>3)+w of XCD b&7
-    const int slot = 4 * (blockIdx.x >> 3) + (threadIdx.x >> 6);
-    const int e = slot < chunk ? order[(blockIdx.x & 7) * chunk + slot] : -1;
+  } else if (order) {   // blocked visiting order: one wavefront per table slot
+    const int e = order_wave_entry(order, chunk);
     if (e < 0) return;
     p = e & 1; c = (e >> 1) * 64 + (threadIdx.x & 63);
     if (c >= g.Vh) return;
@@ -93,15 +60,15 @@ __global__ void __launch_bounds__(256) k_gen_staple(Geom g, MView A, MView B, in
     if (swz && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);   // contiguous site range per XCD
     int i = bid * 256 + threadIdx.x;
     if (i >= g.V) return;
-    p = i >= g.Vh; c = i - p * g.Vh;
+    linear_site(g, i, p, c);
   }
   int x[4], xpn[4], xpm[4], xmn[4], xmnpm[4];
-  coords_sm(g, c, p, x);
+  coords_of(g, c, p, x);
   if (HALO && x[3] >= g.X[3] + 3) x[3] -= g.X[3] + 6;     // a position in ghost_lo: virtual slice -3..-1 (Xt + 6 is even: same parity)
-  shift_sm_t<HALO>(g, x, nu, 1, xpn);
-  shift_sm_t<HALO>(g, x, mu, 1, xpm);
-  shift_sm_t<HALO>(g, x, nu, -1, xmn);
-  shift_sm_t<HALO>(g, xmn, mu, 1, xmnpm);
+  shifted_t<HALO>(g, x, nu, 1, xpn);
+  shifted_t<HALO>(g, x, mu, 1, xpm);
+  shifted_t<HALO>(g, x, nu, -1, xmn);
+  shifted_t<HALO>(g, xmn, mu, 1, xmnpm);
   M3 t = m3_mul_na(m3_load(B.p + site_off_t<HALO>(g, xpn, B.tstride), 64), m3_load(A.p + site_off_t<HALO>(g, xpm, A.tstride), 64));
   M3 s = m3_mul(m3_load(A.p + site_off_t<HALO>(g, x, A.tstride), 64), t);
   t = m3_mul_an(m3_load(A.p + site_off_t<HALO>(g, xmn, A.tstride), 64), m3_load(B.p + site_off_t<HALO>(g, xmn, B.tstride), 64));
@@ -131,9 +98,8 @@ __global__ void __launch_bounds__(256) k_gen_staple(Geom g, MView A, MView B, in
 __global__ void __launch_bounds__(256) k_maxpy(Geom g, MViewW dst, double coef, MView src) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
-  const size_t od = ((size_t)p * g.etile + (c >> 6)) * dst.tstride + (c & 63);
-  const size_t os = ((size_t)p * g.etile + (c >> 6)) * src.tstride + (c & 63);
+  int p, c; linear_site(g, i, p, c);
+  const size_t od = tile_off(g, p, c, dst.tstride), os = tile_off(g, p, c, src.tstride);
   M3 o = m3_load(dst.p + od, 64);
   m3_axpy(o, coef, m3_load(src.p + os, 64));
   m3_store(dst.p + od, 64, o);
@@ -142,9 +108,8 @@ __global__ void __launch_bounds__(256) k_maxpy(Geom g, MViewW dst, double coef, 
 __global__ void __launch_bounds__(256) k_mscale(Geom g, MViewW dst, double coef, MView src) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
-  const size_t od = ((size_t)p * g.etile + (c >> 6)) * dst.tstride + (c & 63);
-  const size_t os = ((size_t)p * g.etile + (c >> 6)) * src.tstride + (c & 63);
+  int p, c; linear_site(g, i, p, c);
+  const size_t od = tile_off(g, p, c, dst.tstride), os = tile_off(g, p, c, src.tstride);
   M3 m = m3_load(src.p + os, 64);
 #pragma unroll
   for (int k = 0; k < 9; k++) { m.e[k].x *= coef; m.e[k].y *= coef; }
@@ -316,7 +281,7 @@ __global__ void __launch_bounds__(256) k_projUderiv(Geom g, MViewW dst, MView U,
                                                     int accumulate) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const size_t t = (size_t)p * g.etile + (c >> 6);
   const int l = c & 63;
   // U (the stored projection of X) is accepted for the call sites' sake and not read: x (x^+x)^(-1/2) is rebuilt from the
@@ -355,7 +320,7 @@ __global__ void __launch_bounds__(256, 2) k_projUderiv_batch(Geom g, ProjBatch B
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
   const int mu = blockIdx.y;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const size_t t = (size_t)p * g.etile + (c >> 6);
   const int l = c & 63;
   // LDS column = the LANE, not the site's position in its tile: where the parity halves meet inside a wavefront (Vh not a
@@ -392,9 +357,8 @@ __global__ void __launch_bounds__(256, WPE) k_staple_deriv(Geom g, MViewW f1, MV
                                                       int z1, int z2,      // z1 / z2: f1 / f2 start from zero (first contribution)
                                                       double coef, const int *order, int chunk) {
   int p, c;
-  if (order) {   // blocked visiting order (tile_order_table): wavefront w takes slot 4*(b>>3)+w of XCD b&7
-    const int slot = 4 * (blockIdx.x >> 3) + (threadIdx.x >> 6);
-    const int e = slot < chunk ? order[(blockIdx.x & 7) * chunk + slot] : -1;
+  if (order) {   // blocked visiting order: one wavefront per table slot
+    const int e = order_wave_entry(order, chunk);
     if (e < 0) return;
     p = e & 1; c = (e >> 1) * 64 + (threadIdx.x & 63);
     if (c >= g.Vh) return;
@@ -403,16 +367,16 @@ __global__ void __launch_bounds__(256, WPE) k_staple_deriv(Geom g, MViewW f1, MV
     if (swz && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);   // contiguous site range per XCD
     int i = bid * 256 + threadIdx.x;
     if (i >= g.V) return;
-    p = i >= g.Vh; c = i - p * g.Vh;
+    linear_site(g, i, p, c);
   }
   int x[4], xpm[4], xpn[4], xmm[4], xmn[4], xmmpn[4], xmnpm[4];
-  coords_sm(g, c, p, x);
-  shift_sm_t<HALO>(g, x, mu, 1, xpm);
-  shift_sm_t<HALO>(g, x, nu, 1, xpn);
-  shift_sm_t<HALO>(g, x, mu, -1, xmm);
-  shift_sm_t<HALO>(g, x, nu, -1, xmn);
-  shift_sm_t<HALO>(g, xmm, nu, 1, xmmpn);
-  shift_sm_t<HALO>(g, xmn, mu, 1, xmnpm);
+  coords_of(g, c, p, x);
+  shifted_t<HALO>(g, x, mu, 1, xpm);
+  shifted_t<HALO>(g, x, nu, 1, xpn);
+  shifted_t<HALO>(g, x, mu, -1, xmm);
+  shifted_t<HALO>(g, x, nu, -1, xmn);
+  shifted_t<HALO>(g, xmm, nu, 1, xmmpn);
+  shifted_t<HALO>(g, xmn, mu, 1, xmnpm);
   const size_t o0 = ((size_t)p * g.etile + (c >> 6));
   const int l = c & 63;
   {
@@ -478,7 +442,7 @@ template <bool HALO>
 __global__ void __launch_bounds__(256) k_staple_deriv_pair(Geom g, MViewW F1, MViewW F2, MView g1, MView g2, MView cA, MView cB, int mu, int nu,
                                                           int z1, int z2, const int *order, int chunk, int nt, int tsel = 0) {
   const int wv = threadIdx.x >> 6;
-  const int slot = 2 * (blockIdx.x >> 3) + (wv >> 1);
+  const int slot = 2 * (blockIdx.x >> 3) + (wv >> 1);      // a wavefront pair per table slot: the one use of this form stays inline
   const int e = slot < chunk ? order[(blockIdx.x & 7) * chunk + slot] : -1;
   if (e < 0) return;
   const int p = e & 1, c = (e >> 1) * 64 + (threadIdx.x & 63);
@@ -496,11 +460,11 @@ __global__ void __launch_bounds__(256) k_staple_deriv_pair(Geom g, MViewW F1, MV
   const int m = second ? nu : mu, n = second ? mu : nu;
   const int zo = second ? z2 : z1;
   int x[4], xpm[4], xpn[4], xmm[4], xmmpn[4];
-  coords_sm(g, c, p, x);
-  shift_sm_t<HALO>(g, x, m, 1, xpm);
-  shift_sm_t<HALO>(g, x, n, 1, xpn);
-  shift_sm_t<HALO>(g, x, m, -1, xmm);
-  shift_sm_t<HALO>(g, xmm, n, 1, xmmpn);
+  coords_of(g, c, p, x);
+  shifted_t<HALO>(g, x, m, 1, xpm);
+  shifted_t<HALO>(g, x, n, 1, xpn);
+  shifted_t<HALO>(g, x, m, -1, xmm);
+  shifted_t<HALO>(g, xmm, n, 1, xmmpn);
   const size_t o0 = ((size_t)p * g.etile + (c >> 6));
   const int l = c & 63;
 #define LD(F, X) m3_load((F).p + site_off_t<HALO>(g, X, (F).tstride), 64)
@@ -549,20 +513,19 @@ __global__ void __launch_bounds__(256) k_staple_deriv_pair(Geom g, MViewW F1, MV
 __global__ void __launch_bounds__(256) k_projectU(Geom g, MViewW dst, MView src) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
-  const size_t od = ((size_t)p * g.etile + (c >> 6)) * dst.tstride + (c & 63);
-  const size_t os = ((size_t)p * g.etile + (c >> 6)) * src.tstride + (c & 63);
+  int p, c; linear_site(g, i, p, c);
+  const size_t od = tile_off(g, p, c, dst.tstride), os = tile_off(g, p, c, src.tstride);
   m3_store(dst.p + od, 64, m3_projectU(m3_load(src.p + os, 64)));
 }
 // ll(x) = naik * U(x) U(x+d) U(x+2d)   (fat7l.nim:146-156)
 __global__ void __launch_bounds__(256) k_naik(Geom g, MViewW dst, MView U, int dir, double naik) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   int x[4], x1[4], x2[4];
-  coords_sm(g, c, p, x);
-  shift_sm(g, x, dir, 1, x1);
-  shift_sm(g, x1, dir, 1, x2);
+  coords_of(g, c, p, x);
+  shifted(g, x, dir, 1, x1);
+  shifted(g, x1, dir, 1, x2);
   M3 t = m3_mul(m3_load(U.p + site_off(g, x1, U.tstride), 64), m3_load(U.p + site_off(g, x2, U.tstride), 64));
   M3 m = m3_mul(m3_load(U.p + site_off(g, x, U.tstride), 64), t);
 #pragma unroll
@@ -570,38 +533,18 @@ __global__ void __launch_bounds__(256) k_naik(Geom g, MViewW dst, MView U, int d
   m3_store(dst.p + site_off(g, x, dst.tstride), 64, m);
 }
 
-// host [idx][mu][9] <-> gauge tiles (same as gauge.hip; local copies keep this file self-contained)
-__global__ void __launch_bounds__(256) k_sm_to_tiles(Geom g, const double2 *__restrict__ host, double2 *G) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
-  for (int mu = 0; mu < 4; mu++) {
-    double2 *w = G + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
-    for (int k = 0; k < 9; k++) w[k * 64] = host[((size_t)i * 4 + mu) * 9 + k];
-  }
-}
-__global__ void __launch_bounds__(256) k_sm_from_tiles(Geom g, double2 *__restrict__ host, const double2 *G) {
-  int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= g.V) return;
-  int p = i >= g.Vh, c = i - p * g.Vh;
-  for (int mu = 0; mu < 4; mu++) {
-    const double2 *w = G + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
-    for (int k = 0; k < 9; k++) host[((size_t)i * 4 + mu) * 9 + k] = w[k * 64];
-  }
-}
-
 // derivative of ll(x) = naik U(x) U(x+d) U(x+2d) (fat7l.nim:146-156) w.r.t. the three places of a link:
 //   F(x) += naik [ C(x) U(x+2d)^+ U(x+d)^+ + U(x-d)^+ C(x-d) U(x+d)^+ + U(x-d)^+ U(x-2d)^+ C(x-2d) ]
 __global__ void __launch_bounds__(256) k_naik_deriv(Geom g, MViewW F, MView U, MView Cl, int dir, double naik) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   int x[4], xp[4], xpp[4], xm[4], xmm[4];
-  coords_sm(g, c, p, x);
-  shift_sm(g, x, dir, 1, xp);
-  shift_sm(g, xp, dir, 1, xpp);
-  shift_sm(g, x, dir, -1, xm);
-  shift_sm(g, xm, dir, -1, xmm);
+  coords_of(g, c, p, x);
+  shifted(g, x, dir, 1, xp);
+  shifted(g, xp, dir, 1, xpp);
+  shifted(g, x, dir, -1, xm);
+  shifted(g, xm, dir, -1, xmm);
   const M3 up = m3_load(U.p + site_off(g, xp, U.tstride), 64), um = m3_load(U.p + site_off(g, xm, U.tstride), 64);
   M3 acc = m3_mul_na(m3_mul_na(m3_load(Cl.p + site_off(g, x, Cl.tstride), 64), m3_load(U.p + site_off(g, xpp, U.tstride), 64)), up);
   m3_mac_na(acc, m3_mul_an(um, m3_load(Cl.p + site_off(g, xm, Cl.tstride), 64)), up);
@@ -688,19 +631,12 @@ struct Smear {
   int ghosts_many(const double2 *const *fields, int n, int tstride, int depth, int async) {
     if (!g.halo) return 0;
     if (n < 1 || n > 12) { qexhip_set_error("internal: ghosts_many takes 1..12 fields"); return -3; }
-    const size_t tile2 = (size_t)tstride * 2, ft = (size_t)g.F / 64;
     double *bottom[24], *top[24], *ghi[24], *glo[24];
-    for (int k = 0; k < n; k++)
-      for (int p = 0; p < 2; p++) {
-        double *base = (double *)fields[k] + (size_t)p * g.etile * tile2;
-        bottom[2 * k + p] = base;
-        top[2 * k + p] = base + ((size_t)g.ntile - depth * ft) * tile2;
-        ghi[2 * k + p] = base + (size_t)g.ntile * tile2;
-        glo[2 * k + p] = base + ((size_t)g.ntile + 3 * ft + (3 - depth) * ft) * tile2;
-      }
+    size_t face = 0;
+    for (int k = 0; k < n; k++) face = ghost_faces(g, fields[k], tstride, depth, bottom + 2 * k, top + 2 * k, ghi + 2 * k, glo + 2 * k);
     if (async) HIPCHK(hipEventRecord(c->ev_ready, c->stream));
     ScopedTimer tm(c, "smear_halo", async ? c->cstream : c->stream);
-    return comm_faces_exchange(c, 2 * n, bottom, top, ghi, glo, (size_t)depth * ft * tile2, async);
+    return comm_faces_exchange(c, 2 * n, bottom, top, ghi, glo, face, async);
   }
   int ghosts_f_async(const double2 *f) { return ghosts_many(&f, 1, 576, 1, 1); }
   int ghosts_join() {
@@ -732,23 +668,8 @@ struct Smear {
   MViewW gvw(double2 *G, int mu) const { return MViewW{G + (size_t)mu * 576, 4 * 576}; }
   MView fv(const double2 *F) const { return MView{F, 576}; }
   MViewW fvw(double2 *F) const { return MViewW{F, 576}; }
-  int upload(double2 *G, const double *host) {
-    const size_t bytes = (size_t)g.V * 72 * sizeof(double);
-    CHK(ensure_stage(c, bytes));
-    HIPCHK(hipMemcpyAsync(c->stage, host, bytes, hipMemcpyHostToDevice, c->stream));
-    k_sm_to_tiles<<<nb(), 256, 0, c->stream>>>(g, (const double2 *)c->stage, G);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  int download(double *host, const double2 *G) {
-    const size_t bytes = (size_t)g.V * 72 * sizeof(double);
-    CHK(ensure_stage(c, bytes));
-    k_sm_from_tiles<<<nb(), 256, 0, c->stream>>>(g, (double2 *)c->stage, G);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host, c->stage, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-  }
+  int upload(double2 *G, const double *host) { return gauge_upload_nat(c, G, host, false); }
+  int download(double *host, const double2 *G) { return gauge_download_nat(c, G, host); }
   // ext > 0 (t-sharded only): also on the `ext` ghost slices either side of the slab -- the operands must be valid `ext + 1`
   // slices out (communication-avoiding smearing levels: nhyp() below)
   // ext_acc = false: on the ghost slices only the staple field `st` is wanted (fat7: the accumulator is read on the slab only)
@@ -1397,16 +1318,16 @@ __global__ void __launch_bounds__(256) k_rephase(Geom g, double2 *G, int bcmask,
   // tlast: this rank holds the last global t slice (the t boundary condition lives there; local t parity = global)
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= g.V) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   int x[4];
-  coords_sm(g, c, p, x);
+  coords_of(g, c, p, x);
   const int ph[4] = {ph0, ph1, ph2, ph3};
   for (int mu = 0; mu < 4; mu++) {
     int s = 0;
     for (int k = 0; k < 4; k++) s += (ph[mu] >> k) & x[k];
     if (((bcmask >> mu) & 1) && x[mu] == g.X[mu] - 1 && (mu != 3 || tlast)) s += 1;
     if (s & 1) {
-      double2 *w = G + (((size_t)p * g.etile + (c >> 6)) * 4 + mu) * 576 + (c & 63);
+      double2 *w = G + link_tile_off(g, p, c, mu);
       for (int k = 0; k < 9; k++) { double2 v = w[k * 64]; w[k * 64] = make_double2(-v.x, -v.y); }
     }
   }

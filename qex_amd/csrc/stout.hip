@@ -23,10 +23,7 @@
 #include <utility>
 
 int gauge_stout_stage(qexhip_ctx *c, double2 *Uin, double2 *V, double2 *Uout, double alpha);        // gauge.hip
-int gauge_upload_nat(qexhip_ctx *c, double2 *G, const double *host);
-int gauge_download_nat(qexhip_ctx *c, const double2 *G, double *host);
 int gauge_swap_resident(qexhip_ctx *c, double2 **buf);
-int gauge_field_ghosts(qexhip_ctx *c, double2 *field, int depth);
 
 // expm1Deriv (matexp.nim:686-713) with scale 20 and expm1Poly4Deriv (:100-117): the reference's recursion, operation by operation
 __device__ __forceinline__ void m3_half_sym_acc(M3 &we, const M3 &e) {
@@ -109,7 +106,7 @@ __global__ void __launch_bounds__(256) k_stout_link(size_t nlinks_tiles, const d
 template <bool HALO>
 __global__ void __launch_bounds__(256) k_stout_stencil(Geom g, const double2 *__restrict__ G, const double2 *__restrict__ CG,
                                                        const double2 *__restrict__ T, double2 *D, const int *order, int chunk) {
-  const int e = order[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];
+  const int e = order_block_entry(order, chunk);
   if (e < 0) return;
   const int mu = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p = e & 1;
@@ -179,7 +176,7 @@ template <bool HALO>
 __global__ void __launch_bounds__(256) k_stout_inv(Geom g, const double2 *__restrict__ G, const double2 *__restrict__ FL, double2 *Gout,
                                                    double2 *Fb, double a, double *partials, const StoutInv *S, const int *order, int chunk) {
   if (S->done) return;
-  const int e = order[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];
+  const int e = order_block_entry(order, chunk);
   double df2 = 0.0, f2 = 0.0;
   if (e >= 0) {                                       // (the whole workgroup together)
     const int mu = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) k_dilute(Geom g, DiluteArgs A, int n, int
                                                 const double2 *s1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   const SiteXYZT s = site_coord(g, c, p);
   const int tg = s.t + toff;
   const int pat = kind == 0 ? ((2 * s.xh + s.o + s.y + s.z + tg) & 1) : (s.o | ((s.y & 1) << 1) | ((s.z & 1) << 2));
@@ -66,7 +66,7 @@ struct AccumArgs {
 __global__ void __launch_bounds__(256) k_trace_accum(Geom g, AccumArgs A, int n, double coef, double2 *tr0, double2 *tr1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 2 * g.Vh) return;
-  const int p = i >= g.Vh, c = i - p * g.Vh;
+  int p, c; linear_site(g, i, p, c);
   double2 *tr = (p ? tr1 : tr0) + c;
   double2 acc = *tr;
   for (int k = 0; k < n; k++) {
